@@ -12,7 +12,14 @@ that would replicate the table is timed separately (apsp_detail.allgather_ms).
 per step, packets/s; at N > 1 delivered records go to the destination's owner
 by RCCL all-to-all.  Inputs are resident in HBM when the timed region starts.
 
-Single GPU:  python bench.py [--steps K --warmup W]
+A plain run times the primary line alone: set-up, the warm-up and the timed
+builds, the result line.  `--full` adds every other leg (the delivery round, the
+lane kernels, C2, GML ingest, the CPU baselines and parity checks, rooflines,
+comparison builds); the `--no-*` options choose among those legs.
+`--dump-outputs DIR` writes the table of the last timed build (a fixed, seeded
+sample of its cells when the table is large) as DIR/<name>.npy.
+
+Single GPU:  python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]
 N GPUs:      python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -38,6 +45,10 @@ ARC_BYTES_PER_RELAX = 12  # LDS search: one 12-B out-arc record (head, latency, 
 FAITHFUL_ROWS = 400  # sources in the reference-faithful CPU sample (~10 s of CPU work at C3 on 16 threads)
 C5_CPU_ROWS = 1024  # C5 dense-port sample (the first rows, scaled by 50k / 1,024)
 C5_FAITHFUL_ROWS = 96  # C5 reference-faithful sample (~5x C3's cost per source)
+FULL_LEG_STEPS = 20  # --full: the legs beside the primary line take at most this many timed steps
+FULL_LEG_WARMUP = 5  # and this many warm-up steps (the outbound leg holds one pipeline state per step)
+DUMP_CELLS = 4_000_000  # --dump-outputs: at most this many table cells (12 B each in the files: 48 MB)
+DUMP_SEED = 20240229
 
 
 def _cpu_info():
@@ -89,6 +100,15 @@ def parse_args():
     p.add_argument("--rank-blocks", default="2,4,8",
                    help="at one GPU: time every rank's one-shot row-block build of these N-way splits "
                         "(apsp_detail.rank_block_ms; '' skips)")
+    p.add_argument("--full", action="store_true",
+                   help="after the primary line's timed builds, run every other leg (delivery, lanes, C2, GML, CPU "
+                        f"baselines, parity checks, rooflines, comparison builds), each on at most {FULL_LEG_STEPS} "
+                        f"timed and {FULL_LEG_WARMUP} warm-up steps; the --no-* options below, --cpu-rows, "
+                        "--rank-blocks and --pmc-json apply to these legs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the routing table of the last timed build (this rank's row block; a fixed, seeded "
+                        "sample of its cells when it is large) to DIR/latency_ns.npy (float64) and "
+                        "DIR/packet_loss.npy (float32)")
     p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     p.add_argument("--no-delivery", action="store_true")
     p.add_argument("--no-e2e", action="store_true",
@@ -109,6 +129,8 @@ def parse_args():
                    help="PMC summary (HBM bytes per launch) written by tools/pmc_summary.py (C5: "
                         "profiles/pmc_c5_latest.json)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     if a.config == "c5":
         a.nodes, a.hosts, a.packets = 50000, 100000, 10000000
     if a.cpu_rows is None:  # C5: ~25x C3's CPU work per row; a sample of ~20-30 s on the 16-CPU share
@@ -666,6 +688,32 @@ def c2_leg(a, ctx, torch, NetworkGraph, synth, with_cpu, pmc=None):
     return leg
 
 
+def dump_outputs(path, D, torch, lat, loss, n_rows, n_cols):
+    """The table a caller of the timed build receives (this rank's n_rows x n_cols block of
+    the device table) as path/latency_ns.npy (float64) and path/packet_loss.npy (float32):
+    every cell in row-major order, or, past DUMP_CELLS cells, the cells at a fixed seeded
+    sample of flat indices (ascending).  At N > 1 each rank's files carry its rank."""
+    total = n_rows * n_cols
+    lat, loss = lat[:total], loss[:total]
+    if total > DUMP_CELLS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_CELLS, dtype=np.int64))
+        idx = torch.from_numpy(idx).cuda()
+        lat, loss = lat[idx], loss[idx]
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{D.rank}" if D.world > 1 else ""
+    np.save(os.path.join(path, f"latency_ns{tag}.npy"), lat.cpu().numpy().view(np.uint64).astype(np.float64))
+    np.save(os.path.join(path, f"packet_loss{tag}.npy"), loss.cpu().numpy().astype(np.float32, copy=False))
+
+
+def finish(D, comm, result):
+    if D.rank == 0:
+        print(json.dumps(result), flush=True)
+    if comm:
+        comm.close()
+    if D.dist:
+        D.dist.destroy_process_group()
+
+
 def main():
     a = parse_args()
     D = Dist(a.gpus)
@@ -746,6 +794,29 @@ def main():
     t_cold = time.perf_counter() - t0
     # the headline: one-shot builds in a warm process, each on a fresh graph with its own plan
     t_build = timed(D, build_fresh, a.steps, a.warmup)
+    if a.dump_outputs:  # the table the last timed build left in this rank's row block
+        dump_outputs(a.dump_outputs, D, torch, my_lat, my_loss, r1 - r0, nu)
+    n_arcs = int(net.edge_src.size * 2 - 2 * np.count_nonzero(net.edge_src == net.edge_dst))
+    result = {
+        "metric": METRIC, "value": round(t_build, 6), "unit": "s", "n_gpus": D.world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(t_build * 1e3, 4), "higher_is_better": False,
+        "scaling": "strong", "vs_baseline": None, "dtype": "u64+f32",
+        "data": f"synthetic (seeded ring+chords graph, SURVEY §8d {'C5' if c5 else 'C3'})",
+        "config": {"workload": f"{'C5' if c5 else 'C3'} APSP routing build: {a.nodes // 1000}k-node undirected "
+                               "ring+chords graph, mean degree 8, "
+                               "latency U[1,100] ms (integer us), loss 0 w.p. 0.8 else U(0,0.02); all nodes used; "
+                               "source rows sharded across ranks (each rank keeps its row block; the optional RCCL "
+                               "all-gather of the blocks is timed separately in apsp_detail.allgather_ms)",
+                   "nodes": a.nodes, "arcs": n_arcs, "parallelism": f"rows{D.world}"},
+        "full": a.full,
+    }
+    if not a.full:  # the primary line alone; the legs below (and these two objects) come with --full
+        result.update({"roofline": None, "cpu_baseline": None, "collectives": collectives})
+        finish(D, comm, result)
+        return
+    # the legs beside the primary line: a bounded number of steps each, whatever the primary line took
+    a.steps, a.warmup = min(a.steps, FULL_LEG_STEPS), min(a.warmup, FULL_LEG_WARMUP)
+    result["leg_steps"], result["leg_warmup"] = a.steps, a.warmup
     # beside it: rebuilds on the same device graph (the plan is rebuilt too; nothing is cached)
     t_warm = timed(D, build, a.steps, a.warmup)
     t_allgather = timed(D, allgather, max(1, a.steps // 2), 1) if D.dist else 0.0
@@ -785,7 +856,6 @@ def main():
     build()
     works = {k: ctx.read_timer(k)[2] for k in ("sssp", "relax", "sssp_bucket", "sssp_bucket_entries")}
     ctx.enable_timers(False)
-    n_arcs = int(net.edge_src.size * 2 - 2 * np.count_nonzero(net.edge_src == net.edge_dst))
     rows_mine = r1 - r0
     dijkstra_relax = float(rows_mine) * n_arcs  # per-source Dijkstra: every arc of every source once
     lds = timers["sssp"][1] > 0
@@ -952,17 +1022,7 @@ def main():
             cpu_all = {"threads": tv, "share": threads, "what": "all logical cores are the share: the runs above"}
         cpu_faithful["all_cores"] = cpu_all
 
-    result = {
-        "metric": METRIC, "value": round(t_build, 6), "unit": "s", "n_gpus": D.world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": round(t_build * 1e3, 4), "higher_is_better": False,
-        "scaling": "strong", "vs_baseline": None, "dtype": "u64+f32",
-        "data": f"synthetic (seeded ring+chords graph, SURVEY §8d {'C5' if c5 else 'C3'})",
-        "config": {"workload": f"{'C5' if c5 else 'C3'} APSP routing build: {a.nodes // 1000}k-node undirected "
-                               "ring+chords graph, mean degree 8, "
-                               "latency U[1,100] ms (integer us), loss 0 w.p. 0.8 else U(0,0.02); all nodes used; "
-                               "source rows sharded across ranks (each rank keeps its row block; the optional RCCL "
-                               "all-gather of the blocks is timed separately in apsp_detail.allgather_ms)",
-                   "nodes": a.nodes, "arcs": n_arcs, "parallelism": f"rows{D.world}"},
+    result.update({
         "roofline": roofline, "cpu_baseline": cpu,
         "parity_vs_cpu": parity,
         "apsp_detail": {"kernel": roofline["kernel"],
@@ -981,7 +1041,7 @@ def main():
                         "table_bytes": 12 * nu * nu,
                         "end_to_end": e2e,
                         "cpu_baseline_faithful": cpu_faithful},
-    }
+    })
     if cpu:
         result["apsp_detail"]["speedup_vs_cpu"] = round(cpu["value"] / t_build, 1)
     if cpu_faithful:
@@ -1164,12 +1224,7 @@ def main():
             result["outbound"] = outbound_leg(a, D, ctx, torch, pk, hosts, ht, table, round_end, sharded, pmc)
 
     result["collectives"] = collectives
-    if D.rank == 0:
-        print(json.dumps(result), flush=True)
-    if comm:
-        comm.close()
-    if D.dist:
-        D.dist.destroy_process_group()
+    finish(D, comm, result)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@ set -u
 OUT=$1; REPS=$2; A=$3; B=$4
 for r in $(seq $REPS); do
   for lib in $A $B; do
-    SHADOW_GPU_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --no-cpu --no-gml --no-delivery --no-codel --no-compare \
+    SHADOW_GPU_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --full --no-cpu --no-gml --no-delivery --no-codel --no-compare \
       --no-e2e --rank-blocks= --steps 20 2>/dev/null | grep metric > /tmp/ab_c2l.json || { echo "run failed: $lib"; exit 1; }
     python3 -c "
 import json,sys; d=json.load(open('/tmp/ab_c2l.json'))['c2']; r=d['roofline'] or {}

@@ -6,7 +6,7 @@ mkdir -p $(dirname $OUT)
 for r in $(seq $REPS); do
   for e in "$@"; do
     if [ "$e" = "-" ]; then envs=""; else envs="$e"; fi
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu --no-gml --no-c2 --rank-blocks 8 --steps 10 2>/dev/null | grep metric > /tmp/ab_env.json || { echo "run failed: $e"; exit 1; }
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu --no-gml --no-c2 --rank-blocks 8 --steps 10 2>/dev/null | grep metric > /tmp/ab_env.json || { echo "run failed: $e"; exit 1; }
     python3 - "$e" >> $OUT << 'PY'
 import json, sys
 d = json.load(open("/tmp/ab_env.json"))

@@ -5,7 +5,7 @@ set -u
 TAG=$1
 O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u bench.py --config c5 --no-cpu --no-gml --no-c2 --steps 3 --warmup 1 --rank-blocks 8 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u bench.py --full --config c5 --no-cpu --no-gml --no-c2 --steps 3 --warmup 1 --rank-blocks 8 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 - $O <<'PY'
 import csv, glob, json, sys
 o = sys.argv[1]

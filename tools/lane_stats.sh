@@ -7,7 +7,7 @@ TAG=${1:-x}
 export TMPDIR=/tmp
 OUT=gpurun_out/lane_$TAG
 mkdir -p $OUT
-timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python3 bench.py --no-cpu --no-gml --no-c2 --steps 5 --warmup 2 > $OUT/bench.log 2>&1 || { echo "stats run failed"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python3 bench.py --full --no-cpu --no-gml --no-c2 --steps 5 --warmup 2 > $OUT/bench.log 2>&1 || { echo "stats run failed"; tail -5 $OUT/bench.log; exit 1; }
 python3 - $OUT <<'PY'
 import csv, glob, re, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]

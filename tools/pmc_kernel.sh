@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (one rocprofv3 run per counter group) over a command, summarised per kernel.
-# usage: bash tools/pmc_kernel.sh TAG "KERNEL_SUBSTRING[,KERNEL_SUBSTRING...]" python3 bench.py --no-cpu --steps 2
+# usage: bash tools/pmc_kernel.sh TAG "KERNEL_SUBSTRING[,KERNEL_SUBSTRING...]" python3 bench.py --full --no-cpu --steps 2
 set -u
 TAG=$1; KF=$2; shift 2
 export TMPDIR=/tmp

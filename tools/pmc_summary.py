@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Summarise rocprofv3 output into profiles/ JSON.
 
-  kernel stats : rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python bench.py ...
-  PMC passes   : rocprofv3 --pmc FETCH_SIZE  --output-format csv -d DIR_F -- python bench.py ...
-                 rocprofv3 --pmc WRITE_SIZE  --output-format csv -d DIR_W -- python bench.py ...
+  kernel stats : rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python bench.py --full ...
+  PMC passes   : rocprofv3 --pmc FETCH_SIZE  --output-format csv -d DIR_F -- python bench.py --full ...
+                 rocprofv3 --pmc WRITE_SIZE  --output-format csv -d DIR_W -- python bench.py --full ...
 
     python tools/pmc_summary.py --stats DIR --fetch DIR_F --write DIR_W -o profiles/pmc_r01.json
 

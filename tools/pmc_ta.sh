@@ -1,5 +1,5 @@
 #!/bin/bash
-# TA / TCP utilisation of one kernel (two PMC passes), e.g. bash tools/pmc_ta.sh "k_relax_w2<" python3 bench.py --no-cpu --no-delivery --steps 1
+# TA / TCP utilisation of one kernel (two PMC passes), e.g. bash tools/pmc_ta.sh "k_relax_w2<" python3 bench.py --full --no-cpu --no-delivery --steps 1
 set -u
 KF=$1; shift
 export TMPDIR=/tmp

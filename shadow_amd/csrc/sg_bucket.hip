@@ -3,7 +3,7 @@
 // Replaces, for sparse graphs whose distance row no longer fits a CU's LDS, the
 // per-source petgraph::algo::dijkstra of NetworkGraph::compute_shortest_paths
 // (graph/mod.rs:190-208).  sg_sssp.hip keeps a whole row of 8-B keys in LDS, which
-// stops at ~10.9k nodes; the batched-source slab (sg_routing.hip k_relax_w2) goes
+// stops at ~10.9k nodes; the batched-source slab (sg_slab.hip k_relax_w2) goes
 // on past it but re-gathers a row whenever any of its 64 sources improved it:
 // 10.5x Dijkstra's relaxations at C5.  This search does Dijkstra's work at any
 // size by keeping in LDS only what one distance band needs.
@@ -33,7 +33,7 @@
 // (latency, loss) of sg_sssp.hip, the fold applies the edge on the right
 // (sg_device.h fold_loss), so the settled key is petgraph's.  A candidate whose
 // latency saturates (LAT32_SAT) is never offered: its node stays unsettled, and
-// an unsettled node flags the row for the wide kernel (sg_routing.hip run_wide),
+// an unsettled node flags the row for the wide kernel (sg_slab.hip run_wide),
 // as unreachable nodes do.
 //
 // Memory.  LDS holds the band: the hash (HS slots of node id + flagged key), the
@@ -56,6 +56,7 @@
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 namespace sg {
 
@@ -1441,15 +1442,67 @@ __global__ void k_band_used(const uint32_t* __restrict__ used, uint32_t n_used, 
 struct BkShape {
   uint32_t nt, hs_log2, nch;
 };
-static int bk_env(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s && *s ? atoi(s) : dflt;
-}
 static BkShape bk_shape() {
   BkShape k;
-  k.nt = bk_env("SG_BUCKET_THREADS", 256) == 1024 ? 1024u : 256u;
-  k.hs_log2 = (uint32_t)std::max(6, std::min(14, bk_env("SG_BUCKET_HASH", k.nt == 1024 ? 12 : 11)));
-  k.nch = (uint32_t)std::max(4, std::min(65534, bk_env("SG_BUCKET_CHUNKS", 1024)));
+  k.nt = knob_int("SG_BUCKET_THREADS", 256) == 1024 ? 1024u : 256u;
+  k.hs_log2 = (uint32_t)knob_int("SG_BUCKET_HASH", k.nt == 1024 ? 12 : 11, 6, 14);
+  k.nch = (uint32_t)knob_int("SG_BUCKET_CHUNKS", 1024, 4, 65534);
+  return k;
+}
+// The other knobs of a bucketed or banded search, read once per launch_sssp_bucket.
+struct BkKnobs {
+  BkShape shape;
+  // Bucket width: the smallest arc latency, so that a band never relaxes into itself (one pass
+  // over its nodes, no re-queued node); where that is tiny next to the arcs' mean (1-ns arcs
+  // beside millisecond ones), mean / 128, and the band relaxes its own arcs through the queue.
+  // SG_BUCKET_DELTA (ns) overrides.  C5 (w_min 1 ms, mean 50 ms): 1-ms bands, ~270 per row.
+  uint32_t delta;
+  uint32_t ring;      // ring slots: a power of two <= BK_R (SG_BUCKET_RING; tests: small rings use the far lists)
+  uint32_t spin_max;  // SG_SSSP_SPIN_MAX (sg_knobs.h)
+  bool queue_mode;    // SG_BUCKET_MODE=queue forces the general kernel over the exact-band one
+  size_t per_cu;      // SG_BUCKET_PER_CU: workgroups per CU, at most
+  // SG_BUCKET_STAGE, bucketed: lowers the entries a workgroup stages in LDS (tests: 0 stores
+  // every entry straight to the arena, small values overflow to it)
+  uint32_t stage_max;
+  // the exact-band kernel's: hash slots and arena chunks (its own defaults), entries staged per
+  // slot (SG_BUCKET_STAGE again), band nodes per wave, the append filter
+  uint32_t band_hs_log2, band_nch, band_stg, band_npw;
+  bool band_filter;
+};
+static BkKnobs bk_knobs(const sg_net* net) {
+  BkKnobs k;
+  k.shape = bk_shape();
+  const double dl = knob_double("SG_BUCKET_DELTA", std::max<double>(std::max<uint32_t>(net->arc_lat_min, 1u),
+                                                                    net->arc_lat_mean / 128.0));
+  k.delta = (uint32_t)std::max(1.0, std::min(4294967295.0, dl));
+  k.ring = 2;
+  for (const uint32_t want = (uint32_t)std::max(2, knob_int("SG_BUCKET_RING", (int)BK_R)); k.ring < BK_R && k.ring < want;)
+    k.ring <<= 1;
+  k.spin_max = sssp_spin_max();
+  const char* md = knob_str("SG_BUCKET_MODE");
+  k.queue_mode = md && strcmp(md, "queue") == 0;
+  k.per_cu = (size_t)knob_int("SG_BUCKET_PER_CU", 8);
+  k.stage_max = (uint32_t)std::max(0, knob_int("SG_BUCKET_STAGE", INT_MAX));
+  k.band_hs_log2 = (uint32_t)knob_int("SG_BUCKET_HASH", 11, 6, 14);
+  k.band_nch = (uint32_t)knob_int("SG_BUCKET_CHUNKS", 384, 4, 65534);
+  // per-slot staging of the band's appends: off by default -- it coalesces the entry stores but
+  // measured slower at C5 (8,192 rows: 47.5 ms with 8 entries per slot, 64.2 ms with 16 (three
+  // rows per CU), 45.8 ms without; profiles/r05/ab_band_stage.txt): the kernel is bound by the
+  // texture-address unit's lane accesses, not by write requests
+  k.band_stg = (uint32_t)knob_int("SG_BUCKET_STAGE", 0, 0, (int)BD_E_MAX);
+  // band nodes per wave: about 448 arcs, so that a wave's arcs nearly always fit one step of
+  // BD_K x 64 slots (C5, mean out-degree 8: 56 nodes, 59.8 against 61.2 ms at 64 for 12,800
+  // rows; 48: 60.8, 40: 62.7; profiles/r05/ab_c5_band_npw_r8g.txt); SG_BAND_NPW overrides
+  const double mdeg = (double)net->n_arcs / std::max(1u, net->n_nodes);
+  k.band_npw = (uint32_t)knob_int("SG_BAND_NPW", (int)std::max(16.0, std::min(64.0, 448.0 / std::max(mdeg, 1.0))), 1, 64);
+  // The append filter (SG_BAND_FILTER=1; off by default): n bytes per workgroup, 256-B aligned.
+  // Measured at C5 (r6, tools/apsp_ab.py, tables identical; profiles/r06/ab_c5_band_filter_r6d.txt):
+  // arena entries 3.98 -> 1.80 per cell, but 287 against 226.5 ms per build -- each filter read is
+  // one more dependent L2 / Infinity-Cache round trip on the relaxation's chain (the relax step per
+  // band 20.5k -> 34.1k cycles), while the load step it shortens gained only 1.2k (10.8k -> 9.6k):
+  // the kernel is bound by the requests each CU keeps in flight (TCP_PENDING_STALL_CYCLES ~0.8 of
+  // its cycles, profiles/r05/pmc_band_r06h.txt), and the filter adds a read per live candidate
+  k.band_filter = knob_int("SG_BAND_FILTER", 0) != 0;
   return k;
 }
 static size_t bk_fixed_lds(uint32_t n, const BkShape& k) {
@@ -1461,7 +1514,7 @@ bool sssp_bucket_fits(uint32_t n) {
   return bk_fixed_lds(n, bk_shape()) <= 160 * 1024;
 }
 
-static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used, uint32_t rows);
+static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used, const BkKnobs& knobs);
 
 void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                         uint32_t row_end, uint64_t* out_lat, float* out_loss, uint32_t* sat_row,
@@ -1471,7 +1524,8 @@ void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32
   if ((uint64_t)net->n_arcs * 12 >= (1ull << 31)) throw Error(SG_ERR_INVALID_ARG, "too many arcs for 32-bit offsets");
   if (!rows) return;
   hipStream_t st = ctx->stream;
-  const BkShape k = bk_shape();
+  const BkKnobs knobs = bk_knobs(net);
+  const BkShape& k = knobs.shape;
   BkArgs a{};
   a.out_off = net->out_off;
   a.out_arc = net->out_arc;
@@ -1487,33 +1541,17 @@ void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32
   a.out_lat = out_lat;
   a.out_loss = out_loss;
   a.sat_row = sat_row;
-  // Bucket width: the smallest arc latency, so that a band never relaxes into itself (one pass
-  // over its nodes, no re-queued node); where that is tiny next to the arcs' mean (1-ns arcs
-  // beside millisecond ones), mean / 128, and the band relaxes its own arcs through the queue.
-  // SG_BUCKET_DELTA (ns) overrides.  C5 (w_min 1 ms, mean 50 ms): 1-ms bands, ~270 per row.
-  double dl = std::max<double>(std::max<uint32_t>(net->arc_lat_min, 1u), net->arc_lat_mean / 128.0);
-  const char* ds = getenv("SG_BUCKET_DELTA");
-  if (ds && *ds) dl = atof(ds);
-  a.delta = (uint32_t)std::max(1.0, std::min(4294967295.0, dl));
+  a.delta = knobs.delta;
   a.dmul = (uint32_t)(0xFFFFFFFFull / a.delta);
-  // ring slots: a power of two <= BK_R (SG_BUCKET_RING; tests: small rings use the far lists)
-  const char* rs = getenv("SG_BUCKET_RING");
-  uint32_t ring = BK_R;
-  if (rs && *rs) {
-    ring = 2;
-    while (ring < BK_R && ring < (uint32_t)std::max(2, atoi(rs))) ring <<= 1;
-  }
-  a.ring = ring;
-  const char* sm = getenv("SG_SSSP_SPIN_MAX");
-  a.spin_max = sm && *sm ? (uint32_t)std::max(1, atoi(sm)) : (1u << 22);
+  a.ring = knobs.ring;
+  a.spin_max = knobs.spin_max;
   a.vec_out = n_used % 4 == 0 && ((uintptr_t)out_lat & 15) == 0 && ((uintptr_t)out_loss & 15) == 0;
   a.work = work;
   a.diag = diag;
   // Bands no wider than the smallest arc (the default width wherever that is at least mean / 128):
   // the exact-band kernel; SG_BUCKET_MODE=queue forces the general one
-  const char* md = getenv("SG_BUCKET_MODE");
-  if (a.delta <= std::max<uint32_t>(net->arc_lat_min, 1u) && !(md && strcmp(md, "queue") == 0)) {
-    launch_sssp_band(ctx, net, a, n_used, rows);
+  if (a.delta <= std::max<uint32_t>(net->arc_lat_min, 1u) && !knobs.queue_mode) {
+    launch_sssp_band(ctx, net, a, n_used, knobs);
     return;
   }
   a.hs_log2 = k.hs_log2;
@@ -1523,13 +1561,8 @@ void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32
   // to the arena, small values overflow to it)
   const size_t fixed = bk_fixed_lds(n, k);
   const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(
-      (size_t)bk_env("SG_BUCKET_PER_CU", 8), 32 / (k.nt / 64)), (160 * 1024) / fixed));
-  {
-    uint32_t cap = (uint32_t)std::min<size_t>(8192, ((160 * 1024) / per_cu - fixed) / 16);
-    const char* sg = getenv("SG_BUCKET_STAGE");
-    if (sg && *sg) cap = std::min<uint32_t>(cap, (uint32_t)std::max(0, atoi(sg)));
-    a.stg_cap = cap;
-  }
+      knobs.per_cu, 32 / (k.nt / 64)), (160 * 1024) / fixed));
+  a.stg_cap = std::min(knobs.stage_max, (uint32_t)std::min<size_t>(8192, ((160 * 1024) / per_cu - fixed) / 16));
   const uint32_t grid = (uint32_t)ctx->n_cu * per_cu;
   uint32_t* ctr = ctx->r_items.get<uint32_t>(2);
   SG_HIP(hipMemsetAsync(ctr, 0, 8, st));
@@ -1555,25 +1588,16 @@ void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32
 }
 
 // Exact bands (k_sssp_band): bands no wider than the smallest arc latency.
-static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used, uint32_t rows) {
+static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used, const BkKnobs& knobs) {
   hipStream_t st = ctx->stream;
   const uint32_t n = net->n_nodes;
-  a.hs_log2 = (uint32_t)std::max(6, std::min(14, bk_env("SG_BUCKET_HASH", 11)));
-  a.nch = (uint32_t)std::max(4, std::min(65534, bk_env("SG_BUCKET_CHUNKS", 384)));
-  // per-slot staging of the band's appends: off by default -- it coalesces the entry stores but
-  // measured slower at C5 (8,192 rows: 47.5 ms with 8 entries per slot, 64.2 ms with 16 (three
-  // rows per CU), 45.8 ms without; profiles/r05/ab_band_stage.txt): the kernel is bound by the
-  // texture-address unit's lane accesses, not by write requests
-  a.stg_cap = (uint32_t)std::max(0, std::min((int)BD_E_MAX, bk_env("SG_BUCKET_STAGE", 0)));
-  // band nodes per wave: about 448 arcs, so that a wave's arcs nearly always fit one step of
-  // BD_K x 64 slots (C5, mean out-degree 8: 56 nodes, 59.8 against 61.2 ms at 64 for 12,800
-  // rows; 48: 60.8, 40: 62.7; profiles/r05/ab_c5_band_npw_r8g.txt); SG_BAND_NPW overrides
-  const double mdeg = (double)net->n_arcs / std::max(1u, n);
-  a.npw = (uint32_t)std::max(1, std::min(64, bk_env("SG_BAND_NPW", (int)std::max(16.0, std::min(64.0, 448.0 / std::max(mdeg, 1.0))))));
+  a.hs_log2 = knobs.band_hs_log2;
+  a.nch = knobs.band_nch;
+  a.stg_cap = knobs.band_stg;
+  a.npw = knobs.band_npw;
   const size_t lds = BdLds(n, 1u << a.hs_log2, a.nch, 4, a.stg_cap).bytes;
   if (lds + 256 > 160 * 1024) throw Error(SG_ERR_INVALID_ARG, "graph too large for the banded search");
-  const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)bk_env("SG_BUCKET_PER_CU", 8),
-                                                                         (160 * 1024) / (lds + 256)));
+  const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(knobs.per_cu, (160 * 1024) / (lds + 256)));
   const uint32_t grid = (uint32_t)ctx->n_cu * per_cu;
   // the graph in the degree-class numbering: built once per sg_net (the workspace remembers its
   // owner, as sg_dense.hip's sorted arcs); the used list mapped every build
@@ -1608,14 +1632,7 @@ static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used
   // per-workgroup strides (skewing them by 4-33 KB measured the same, r8d)
   a.arena_words = a.nch * BD_CH * 3;
   a.scr_stride = n;
-  // The append filter (SG_BAND_FILTER=1; off by default): n bytes per workgroup, 256-B aligned.
-  // Measured at C5 (r6, tools/apsp_ab.py, tables identical; profiles/r06/ab_c5_band_filter_r6d.txt):
-  // arena entries 3.98 -> 1.80 per cell, but 287 against 226.5 ms per build -- each filter read is
-  // one more dependent L2 / Infinity-Cache round trip on the relaxation's chain (the relax step per
-  // band 20.5k -> 34.1k cycles), while the load step it shortens gained only 1.2k (10.8k -> 9.6k):
-  // the kernel is bound by the requests each CU keeps in flight (TCP_PENDING_STALL_CYCLES ~0.8 of
-  // its cycles, profiles/r05/pmc_band_r06h.txt), and the filter adds a read per live candidate
-  const bool filt = bk_env("SG_BAND_FILTER", 0) != 0;
+  const bool filt = knobs.band_filter;  // n bytes per workgroup, 256-B aligned
   a.filt_stride = filt ? (n + 255u) / 256u * 256u : 0u;
   const size_t arena_b = ((size_t)grid * a.arena_words * 4 + 255) / 256 * 256, scr_b = (size_t)grid * a.scr_stride * 8;
   const size_t filt_b = (size_t)grid * a.filt_stride;
@@ -1624,7 +1641,6 @@ static void launch_sssp_band(sg_ctx* ctx, sg_net* net, BkArgs a, uint32_t n_used
   a.scratch = (unsigned long long*)(wsp + arena_b);
   a.filt = filt ? (uint8_t*)(wsp + arena_b + scr_b) : nullptr;
   a.item_ctr = ctr;
-  (void)rows;
   auto go = [&](auto kern) {
     SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);

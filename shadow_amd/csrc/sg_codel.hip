@@ -18,6 +18,7 @@
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 struct sg_codel {
   sg_ctx* ctx = nullptr;
@@ -1648,8 +1649,7 @@ struct sg_inbound {
 // SG_LANE_MAJOR: the chunk layout of the lane kernels (ChunkMap): 0 contiguous, 1 lane-major,
 // unset / 2 by each block's event count (tests force both on the same events)
 int lane_major_env() {
-  const char* e = getenv("SG_LANE_MAJOR");
-  return e && *e ? std::max(0, std::min(2, atoi(e))) : 2;
+  return sg::knob_int("SG_LANE_MAJOR", 2, 0, 2);
 }
 
 // The lane-major layout is compiled into a launch when forced (SG_LANE_MAJOR=1) or when
@@ -1662,8 +1662,7 @@ int lane_major_launch(int mode, size_t n_events, uint32_t nb, uint32_t ch) {
 // SG_LANE_DIAG=1: per-block timing of the lane-per-host kernels on stderr (a
 // diagnostic: a synchronous copy after the launch; never set in a measured run)
 unsigned long long* lane_diag_alloc(uint32_t nb) {
-  const char* e = getenv("SG_LANE_DIAG");
-  if (!e || atoi(e) == 0) return nullptr;
+  if (sg::knob_int("SG_LANE_DIAG", 0) == 0) return nullptr;
   unsigned long long* d = nullptr;
   SG_HIP(hipMalloc(&d, (size_t)nb * 32));
   SG_HIP(hipMemset(d, 0, (size_t)nb * 32));

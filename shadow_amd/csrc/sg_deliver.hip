@@ -30,6 +30,7 @@
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 struct sg_hosts {
   sg_ctx* ctx = nullptr;
@@ -1547,8 +1548,7 @@ static bool bucket_sort(sg_ctx* ctx, E src, uint32_t n, uint32_t n_slots, uint32
   SbMap sm{((1ull << 40) + spb64 - 1) / spb64, (uint32_t)spb64};
   const uint32_t n_sb = (uint32_t)((n_slots + spb64 - 1) / spb64);
   const uint32_t n_tiles = std::max<uint32_t>(1, (n + SB_TILE - 1) / SB_TILE);
-  const char* env = getenv("SG_BUCKET_REGION");
-  region = region && n > 0 && !(env && env[0] == '0');
+  region = region && n > 0 && !knob_off("SG_BUCKET_REGION");
   if (!region) stats_alone();
   const uint32_t reg = SB_CAP<E::KK>;  // a region is sorted in LDS in one piece
   const size_t cap = region ? std::max<size_t>((size_t)n_sb * reg, n) : n;
@@ -1571,8 +1571,7 @@ static bool bucket_sort(sg_ctx* ctx, E src, uint32_t n, uint32_t n_slots, uint32
     // atomic per entry).  The first level scatters into at most 256 coarse
     // buckets of cpb consecutive super-buckets (runs of 16+ entries), the second
     // level scatters each coarse bucket's tiles into its cpb super-buckets.
-    const char* tl_env = getenv("SG_BUCKET_TWO_LEVEL");  // 0 never, 1 always (tests), else when runs are short
-    const int two_env = tl_env && *tl_env ? atoi(tl_env) : -1;
+    const int two_env = knob_int("SG_BUCKET_TWO_LEVEL", -1);  // 0 never, 1 always (tests), else when runs are short
     const bool two = two_env == 1 || (two_env != 0 && n_sb > 512);
     if (two) {
       const uint32_t cpb = std::max<uint32_t>(2, (n_sb + CB_MAX - 1) / CB_MAX), n_cb = (n_sb + cpb - 1) / cpb;

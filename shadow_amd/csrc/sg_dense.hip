@@ -34,12 +34,13 @@
 //
 // Keys saturate at LAT32_SAT like every 32-bit kernel: a saturated candidate is
 // never offered, and a row with a saturated (unreachable or >= 4.29 s) key is
-// flagged for the wide kernel (sg_routing.hip run_wide).
+// flagged for the wide kernel (sg_slab.hip run_wide).
 #include <algorithm>
 #include <vector>
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 namespace sg {
 
@@ -679,22 +680,41 @@ __global__ void __launch_bounds__(TH) k_sssp_dense_lazy(const uint32_t* __restri
 
 bool sssp_dense_fits(uint32_t n) { return n > 0 && n <= DENSE_MAX; }
 
-// rounds with fewer settled rows than this split each row over several waves (SG_DENSE_SPLIT;
-// C2: 0.363 ms without, 0.320 below 4 rows, 0.305 below 8, 0.299 below 16, r8u)
-static uint32_t dense_split_below(int waves) {
-  const char* v = getenv("SG_DENSE_SPLIT");
-  const int x = v && *v ? atoi(v) : waves;
-  return (uint32_t)std::max(0, std::min(waves, x));
-}
-
-// threads per row (SG_DENSE_THREADS, SG_DENSE_SEED_THREADS for the seeded launches: 512 or 1024)
-// and lanes per settled row in the relaxation (SG_DENSE_SW, SG_DENSE_SEED_SW: 8, 16, 32 or 64).
+// The launch shapes, read where a launch is made.  T-cut search: threads per row (SG_DENSE_THREADS,
+// SG_DENSE_SEED_THREADS for the seeded launches: 512 or 1024) and lanes per settled row in the
+// relaxation (SG_DENSE_SW, SG_DENSE_SEED_SW: 8, 16, 32 or 64).
 // C2 with 256 seed rows (r6, `profiles/r06/ab_c2_seed_r6.txt`): seeded 1024 threads x 64 lanes
 // 0.261 ms, 512 x 64 0.243, 1024 x 16 0.222, 512 x 32 0.211, 512 x 16 0.195, 512 x 8 0.191; the
 // unseeded launch at 32 lanes 0.198 against 0.196, at 16 lanes 0.218 (its early rounds read whole rows)
-static int dense_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
+struct DenseKnobs {
+  int th, sw;
+  // rounds with fewer settled rows than this split each row over several waves (SG_DENSE_SPLIT;
+  // C2: 0.363 ms without, 0.320 below 4 rows, 0.305 below 8, 0.299 below 16, r8u)
+  uint32_t split_below;
+};
+static DenseKnobs dense_knobs(bool seeded) {
+  DenseKnobs k;
+  k.th = knob_int(seeded ? "SG_DENSE_SEED_THREADS" : "SG_DENSE_THREADS", seeded ? 512 : DENSE_THREADS) == 512 ? 512 : 1024;
+  k.sw = knob_int(seeded ? "SG_DENSE_SEED_SW" : "SG_DENSE_SW", seeded ? 8 : 64);
+  k.split_below = (uint32_t)knob_int("SG_DENSE_SPLIT", k.th / 64, 0, k.th / 64);
+  return k;
+}
+// The lazy search (the measurements are at its launch below): threads per row (256, 384 or 512),
+// lanes per settled row (4, 8 or 16), rows in flight per lane group (2 or 4), whole chunks
+// (SG_DENSE_SPEC), the atomic's returned key instead of a settled-bit read (SG_DENSE_RTN)
+struct DenseLazyKnobs {
+  int th, sw, gg;
+  bool spec, rtn;
+};
+static DenseLazyKnobs dense_lazy_knobs() {
+  DenseLazyKnobs k;
+  const int th0 = knob_int("SG_DENSE_THREADS", 256);
+  k.th = th0 == 512 || th0 == 384 ? th0 : 256;
+  k.sw = knob_int("SG_DENSE_SW", 8);
+  k.gg = knob_int("SG_DENSE_G", 2) == 4 ? 4 : 2;
+  k.spec = knob_int("SG_DENSE_SPEC", 1) != 0;
+  k.rtn = knob_int("SG_DENSE_RTN", 1) != 0 && k.spec && k.sw == 8 && k.gg == 2;
+  return k;
 }
 
 // rows of the launches before the last (SG_DENSE_SEED, a comma list, e.g. "32,224"; 0: one launch,
@@ -704,7 +724,7 @@ static int dense_env(const char* name, int dflt) {
 // 0.389 (every level costs one row's latency, ~75-85 us, whatever its size)
 static std::vector<uint32_t> dense_seed_levels(uint32_t rows, uint32_t n_cu) {
   std::vector<uint32_t> lv;
-  const char* v = getenv("SG_DENSE_SEED");
+  const char* v = knob_str("SG_DENSE_SEED");
   if (!v || !*v) {
     if (rows >= 2 * n_cu) lv.push_back(n_cu);
     return lv;
@@ -760,15 +780,15 @@ void launch_sssp_dense(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_
     TimedLaunch tl(ctx, "sssp_dense", 0.0);
     const size_t o = (size_t)(r0 - row_begin) * n_used;
     const bool seeded = sd.mode & DENSE_SEED_USE;
-    const int th = dense_env(seeded ? "SG_DENSE_SEED_THREADS" : "SG_DENSE_THREADS", seeded ? 512 : DENSE_THREADS) == 512 ? 512 : 1024;
-    const int sw = dense_env(seeded ? "SG_DENSE_SEED_SW" : "SG_DENSE_SW", seeded ? 8 : 64);
+    const DenseKnobs k = dense_knobs(seeded);
+    const int th = k.th, sw = k.sw;
     auto pick = [](auto k8, auto k16, auto k32, auto k64, int w) { return w == 8 ? k8 : w == 16 ? k16 : w == 32 ? k32 : k64; };
     auto kern = th == 512 ? pick(k_sssp_dense<512, 8>, k_sssp_dense<512, 16>, k_sssp_dense<512, 32>, k_sssp_dense<512, 64>, sw)
                           : pick(k_sssp_dense<1024, 8>, k_sssp_dense<1024, 16>, k_sssp_dense<1024, 32>, k_sssp_dense<1024, 64>, sw);
     hipLaunchKernelGGL(kern, dim3(nr), dim3(th), lds, st, net->out_off, (const uint32_t*)sa,
                        (const uint8_t*)sorted, n, net->n_arcs, (const uint32_t*)wmin, d_used, n_used, r0,
                        net->self_edge, net->e_lat, net->e_loss, out_lat + o, out_loss + o, sat_row + (r0 - row_begin),
-                       work, dense_split_below(th / 64), sd);
+                       work, k.split_below, sd);
     SG_CHECK_LAUNCH();
   };
   // the lazy search (default; SG_DENSE_LAZY=0: the T-cut search with seed rows).  Latency-bound:
@@ -785,13 +805,13 @@ void launch_sssp_dense(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_
   // `profiles/r06/ab_c2_lazy_r6.txt`): T cut 0.297 ms, with 256 seed rows 0.190; lazy 512 threads x
   // 8 lanes 0.171, 256 x 4 0.151; lazy whole chunks (SG_DENSE_SPEC) 256 x 4 0.130, 256 x 8 0.124,
   // 256 x 16 0.126, 512 x 8 0.136; 4 rows in flight per lane group (SG_DENSE_G=4) 0.132-0.136
-  if (dense_env("SG_DENSE_LAZY", 1)) {
-    const int th0 = dense_env("SG_DENSE_THREADS", 256), th = th0 == 512 || th0 == 384 ? th0 : 256;
-    const int sw = dense_env("SG_DENSE_SW", 8), gg = dense_env("SG_DENSE_G", 2) == 4 ? 4 : 2;
-    const bool spec = dense_env("SG_DENSE_SPEC", 1) != 0;
+  if (knob_int("SG_DENSE_LAZY", 1)) {
+    const DenseLazyKnobs k = dense_lazy_knobs();
+    const int th = k.th, sw = k.sw, gg = k.gg;
+    const bool spec = k.spec;
 #define SG_LAZY_K(T_, S_, G_) (spec ? k_sssp_dense_lazy<T_, S_, G_, true> : k_sssp_dense_lazy<T_, S_, G_, false>)
     auto pick = [&](auto k4, auto k8, auto k16) { return sw == 4 ? k4 : sw == 16 ? k16 : k8; };
-    const bool rtn = dense_env("SG_DENSE_RTN", 1) != 0 && spec && sw == 8 && gg == 2;
+    const bool rtn = k.rtn;
     auto kern = rtn ? (th == 384 ? k_sssp_dense_lazy<384, 8, 2, true, true> : th == 512 ? k_sssp_dense_lazy<512, 8, 2, true, true>
                                                                                : k_sssp_dense_lazy<256, 8, 2, true, true>)
               : th == 256 ? (gg == 4 ? pick(SG_LAZY_K(256, 4, 4), SG_LAZY_K(256, 8, 4), SG_LAZY_K(256, 16, 4))

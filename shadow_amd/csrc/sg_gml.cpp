@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/shadow_gpu.h"
+#include "sg_knobs.h"
 
 struct sg_gml {
   bool directed = false;
@@ -517,7 +518,7 @@ const char* resync(const char* q, const char* end) {
 }
 
 unsigned default_threads() {
-  if (const char* e = getenv("SG_GML_THREADS")) return (unsigned)std::max(1, atoi(e));
+  if (const char* e = sg::knob_str("SG_GML_THREADS")) return (unsigned)std::max(1, atoi(e));
   const unsigned h = std::thread::hardware_concurrency();
   return std::max(1u, std::min(h ? h : 1u, 16u));  // a GPU's CPU share on the box
 }

@@ -161,7 +161,7 @@ struct sg_ctx {
   std::vector<hipEvent_t> event_pool;
 };
 
-// Device-resident network graph (sg_routing.hip builds it).
+// Device-resident network graph (sg_net.hip builds it).
 struct sg_net {
   sg_ctx* ctx = nullptr;
   uint64_t serial = 0;  // unique per context: who owns the context's sorted-arc workspace (sg_dense.hip)
@@ -336,17 +336,51 @@ void launch_sssp_bucket(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32
 constexpr int SSSP_KB_MAX = 8;
 constexpr uint32_t SSSP_UB_EXACT = 0x80000000u;  // bound rows per bounded search (sg_sssp.hip SSSP_KB)
 bool sssp_lds_fits(uint32_t n_nodes);
-// build the in-arc CSC of a net on its first use (sg_routing.hip; the upload writes the out-arcs only)
-void ensure_csc(sg_ctx* ctx, sg_net* net);
 
-void launch_sssp_lds(sg_ctx* ctx, const uint32_t* out_off, const uint32_t* out_arc, uint32_t n, uint32_t n_arcs,
-                     const uint32_t* d_used, uint32_t n_used, uint32_t row_begin, uint32_t row_end,
-                     const uint32_t* self_edge, const uint64_t* e_lat, const float* e_loss, uint64_t* out_lat,
-                     float* out_loss, uint32_t* sat_row, uint32_t delta, unsigned long long* work,
-                     unsigned long long* diag, const uint32_t* blk_rows = nullptr, uint32_t n_blk = 0,
-                     const uint32_t* ub_row = nullptr, const uint32_t* ub_w = nullptr,
-                     const uint32_t* plan_ctl = nullptr, int plan_ph = 0, uint32_t* plan_ctr = nullptr,
-                     uint32_t* done = nullptr);
+// One launch of the LDS search on a net (the graph arrays come from it).
+struct SsspLdsLaunch {
+  // the row block: rows [row_begin, row_end) of the table (out_* device, row-major from
+  // row_begin); sat_row (row_end - row_begin u32) receives 1 for rows needing the wide kernel;
+  // delta the bucket width in ns; work / diag optional (relaxations; 8 words per row)
+  const uint32_t* d_used = nullptr;
+  uint32_t n_used = 0, row_begin = 0, row_end = 0;
+  uint64_t* out_lat = nullptr;
+  float* out_loss = nullptr;
+  uint32_t* sat_row = nullptr;
+  uint32_t delta = 0;
+  unsigned long long* work = nullptr;
+  unsigned long long* diag = nullptr;
+  // the plan (optional): the rows to run (blk_rows, n_blk) and their bound rows (ub_row, ub_w),
+  // as described above; plan_ctl / plan_ph: the device plan's phase to run (n_blk then bounds
+  // its row count, which only the device knows); plan_ctr: the launch's claim counters, zeroed
+  // by the caller (null: the launch zeroes its own); done: per-row flags of the flagged
+  // one-launch plan (sg_sssp.hip "Flagged rows")
+  const uint32_t* blk_rows = nullptr;
+  uint32_t n_blk = 0;
+  const uint32_t* ub_row = nullptr;
+  const uint32_t* ub_w = nullptr;
+  const uint32_t* plan_ctl = nullptr;
+  int plan_ph = 0;
+  uint32_t* plan_ctr = nullptr;
+  uint32_t* done = nullptr;
+};
+void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l);
+
+// sg_net.hip: the in-arc CSC of a net, built on its first use (the upload writes the out-arcs
+// only); a node's GML id as text, for error messages; two zero fills as one launch on the
+// context stream
+void ensure_csc(sg_ctx* ctx, sg_net* net);
+std::string node_name(const sg_net* net, uint32_t idx);
+void launch_zero2(sg_ctx* ctx, uint32_t* a, uint32_t na, uint32_t* b, uint32_t nb);
+
+// sg_slab.hip: the batched-source slab search of rows [row_begin, row_end) (any graph whose
+// slab offsets fit 32 bits), and the wide (u64 latency) recomputation of the listed rows
+// (absolute row indices) every search falls back to
+constexpr int WORK_SHARDS = 64;  // relaxation counter shards (measurement only)
+void shortest_paths_slab(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
+                         uint32_t row_end, uint64_t* out_lat, float* out_loss);
+void run_wide(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, const std::vector<uint32_t>& rows,
+              uint32_t out_row0, uint64_t* out_lat, float* out_loss);
 
 // The LDS search's phase plan, built on the device (sg_plan.hip) on the context
 // stream: phase p's rows are list[ctl[2p] .. + ctl[2p + 1]) (absolute row indices),

@@ -43,6 +43,7 @@
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 namespace sg {
 
@@ -542,7 +543,7 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
                        p.ub_row, p.ub_w);
     SG_CHECK_LAUNCH();
   }
-  if (getenv("SG_PLAN_DIAG") && atoi(getenv("SG_PLAN_DIAG"))) {  // phase sizes on stderr
+  if (knob_int("SG_PLAN_DIAG", 0) != 0) {  // phase sizes on stderr
     uint32_t h[2 * SSSP_PHASES_MAX];
     copy_to_host(ctx, h, p.ctl, sizeof(h));
     fprintf(stderr, "[plan] %u rows:", rows);

@@ -7,7 +7,7 @@
 // record per relaxation), and the finished row is written straight into the
 // caller's row-major table.
 //
-// Why not the batched-source slab kernel (sg_routing.hip k_relax_w2) here: a
+// Why not the batched-source slab kernel (sg_slab.hip k_relax_w2) here: a
 // 64-source batch gathers whole 512-B rows, and Bellman-Ford re-gathers a row
 // whenever any of its 64 sources improved it -- about 10x the n_used * arcs
 // relaxations of Dijkstra at C3.  A per-source search relaxes only what its own
@@ -20,7 +20,7 @@
 // edge applied on the right (sg_device.h fold_loss); any relaxation order
 // reaches it.  Keys whose latency saturates at LAT32_SAT (>= 4.29 s, or
 // unreachable) are never propagated and flag the row for the wide kernel
-// (sg_routing.hip run_wide), as in the slab kernel.
+// (sg_slab.hip run_wide), as in the slab kernel.
 //
 // Flagged key.  key = (latency u32 << 32) | (bits(loss) << 1) | dirty.  Loss is
 // in [0, 1], so bits(loss) < 2^31 and the 64-bit integer order of the key is the
@@ -60,7 +60,7 @@
 // D[s][v] from above.  A bounded search starts key[v] at (that bound + 1, loss
 // 1.0, clean) instead of infinity: still above the optimum, so the fixed point
 // and the proof above are unchanged, but every candidate slower than the bound
-// loses its first atomic min and is never queued.  sg_routing.hip sssp_plan
+// loses its first atomic min and is never queued.  sg_plan.hip sssp_device_plan
 // orders the rows in phases, one launch each, so the bound rows of a phase are
 // final (an earlier launch) before any search reads them.  A one-launch variant
 // with per-row flags (searches reading rows other workgroups had just published)
@@ -87,17 +87,18 @@
 
 #include "sg_device.h"
 #include "sg_internal.h"
+#include "sg_knobs.h"
 
 namespace sg {
 
-constexpr int SSSP_THREADS = 1024;  // the largest workgroup (SG_SSSP_THREADS selects 512 or 1024)
+constexpr int SSSP_THREADS = 1024;  // the largest workgroup (template NT; every launch uses 1024)
 constexpr int SSSP_WAVES = SSSP_THREADS / 64;
 constexpr int SSSP_K = 4;            // expansion path: chunks of 64 arc slots a wave handles at once
-constexpr int SSSP_KB = SSSP_KB_MAX;  // bound rows per bounded search (sg_routing.hip sssp_plan)
+constexpr int SSSP_KB = SSSP_KB_MAX;  // bound rows per bounded search (sg_plan.hip sssp_device_plan)
 // static LDS of k_sssp_lds: ctl[8] + red[SSSP_WAVES] (u32), hb (u64), own[SSSP_WAVES][64 * SSSP_K] (u8),
 // sink[64] (u64), s_ub[SSSP_KB][3] + s_nub (u32)
 constexpr size_t SSSP_STATIC_LDS = 4 * (8 + SSSP_WAVES) + 16 + SSSP_WAVES * 64 * SSSP_K + 512 + 4 * (3 * SSSP_KB + 1) + 16;
-// lane path: arcs a lane has in flight (template LA: 8 or 16, SG_SSSP_LANE_ARCS);
+// lane path: arcs a lane has in flight (template LA; every launch uses 8);
 // used up to out-degree lane_deg_max (SG_SSSP_LANE_DEG, default 64; the arcs past LA arc-parallel)
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
@@ -760,50 +761,47 @@ bool sssp_lds_fits(uint32_t n) {
   return sssp_lds_bytes(n) + SSSP_STATIC_LDS <= LDS_PER_CU;
 }
 
-// Rows [row_begin, row_end) of the table (out_* device, row-major from out_row0).
-// sat_row (device, row_end - row_begin u32) receives 1 for rows needing the wide kernel.
-void launch_sssp_lds(sg_ctx* ctx, const uint32_t* out_off, const uint32_t* out_arc, uint32_t n, uint32_t n_arcs,
-                     const uint32_t* d_used, uint32_t n_used, uint32_t row_begin, uint32_t row_end,
-                     const uint32_t* self_edge, const uint64_t* e_lat, const float* e_loss, uint64_t* out_lat,
-                     float* out_loss, uint32_t* sat_row, uint32_t delta, unsigned long long* work,
-                     unsigned long long* diag, const uint32_t* blk_rows, uint32_t n_blk, const uint32_t* ub_row,
-                     const uint32_t* ub_w, const uint32_t* plan_ctl, int plan_ph, uint32_t* plan_ctr,
-                     uint32_t* done) {
-  const size_t lds = sssp_lds_bytes(n);
-  if (!sssp_lds_fits(n)) throw Error(SG_ERR_INVALID_ARG, "graph too large for the LDS-resident search");
-  if ((uint64_t)n_arcs * 12 >= (1ull << 31)) throw Error(SG_ERR_INVALID_ARG, "too many arcs for 32-bit offsets");
-  // entries a wave claims at once (SG_SSSP_CLAIM, 1..64)
-  const char* cs = getenv("SG_SSSP_CLAIM");
-  const uint32_t claim = (uint32_t)std::min(64, std::max(1, cs && *cs ? atoi(cs) : 64));
-  const int vec = n_used % 4 == 0 && ((uintptr_t)out_lat & 15) == 0 && ((uintptr_t)out_loss & 15) == 0;
-  // with a device plan (plan_ctl), n_blk bounds the phase's row count, which only the device knows
-  const uint32_t rows = blk_rows ? n_blk : row_end - row_begin;
-  if (!rows) return;
-  const char* ts = getenv("SG_SSSP_THREADS");
-  const int nt = ts && atoi(ts) == 512 ? 512 : 1024;
-  const char* ss = getenv("SG_SSSP_SLEEP");  // idle back-off, units of ~512 cycles
-  const uint32_t idle_sleep = ss && *ss ? (uint32_t)std::max(0, atoi(ss)) : 0u;
-  const char* ls = getenv("SG_SSSP_LANE_DEG");
-  // (with the remainder arc-parallel, every wave takes the lane path unless SG_SSSP_LANE_DEG
-  // lowers it: C3 2.83 ms at 16, 2.79 at 24 and 64)
-  const uint32_t lane_deg = ls && *ls ? (uint32_t)std::max(0, atoi(ls)) : 64u;
-  const char* la = getenv("SG_SSSP_LANE_ARCS");
-  const int la16 = la && atoi(la) == 16, la4 = la && atoi(la) == 4;
+struct SsspKnobs {
+  uint32_t claim;       // SG_SSSP_CLAIM: entries a wave claims at once (1..64)
+  uint32_t idle_sleep;  // SG_SSSP_SLEEP: idle back-off, units of ~512 cycles
+  // SG_SSSP_LANE_DEG (with the remainder arc-parallel, every wave takes the lane path unless
+  // it is lowered: C3 2.83 ms at 16, 2.79 at 24 and 64)
+  uint32_t lane_deg;
   // One persistent workgroup per CU claims rows from a counter: out_off is
   // staged once per CU instead of once per row, and no workgroup is launched and
   // torn down per row.  C3: 3.92 -> 3.54 ms (same box).  SG_SSSP_PERSIST=0: a
   // workgroup per row.
-  const char* ps = getenv("SG_SSSP_PERSIST");
-  const bool persist = done || (!(ps && ps[0] == '0') && (rows > (uint32_t)ctx->n_cu || plan_ctl));
+  bool persist;
   // spin budget per wave (sleeps of ~128 cycles): a safety valve against a queue
   // bug, never reached by a correct search; SG_SSSP_SPIN_MAX (tests) lowers it so
   // that searches give up and their rows take the wide kernel
-  const char* sm = getenv("SG_SSSP_SPIN_MAX");
-  const uint32_t spin_max = sm && *sm ? (uint32_t)std::max(1, atoi(sm)) : (1u << 22);
+  uint32_t spin_max;
+};
+static SsspKnobs sssp_knobs() {
+  SsspKnobs k;
+  k.claim = (uint32_t)knob_int("SG_SSSP_CLAIM", 64, 1, 64);
+  k.idle_sleep = (uint32_t)std::max(0, knob_int("SG_SSSP_SLEEP", 0));
+  k.lane_deg = (uint32_t)std::max(0, knob_int("SG_SSSP_LANE_DEG", 64));
+  k.persist = !knob_off("SG_SSSP_PERSIST");
+  k.spin_max = sssp_spin_max();
+  return k;
+}
+
+void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
+  const SsspKnobs k = sssp_knobs();
+  const uint32_t n = net->n_nodes;
+  const size_t lds = sssp_lds_bytes(n);
+  if (!sssp_lds_fits(n)) throw Error(SG_ERR_INVALID_ARG, "graph too large for the LDS-resident search");
+  if ((uint64_t)net->n_arcs * 12 >= (1ull << 31)) throw Error(SG_ERR_INVALID_ARG, "too many arcs for 32-bit offsets");
+  const int vec = l.n_used % 4 == 0 && ((uintptr_t)l.out_lat & 15) == 0 && ((uintptr_t)l.out_loss & 15) == 0;
+  // with a device plan (plan_ctl), n_blk bounds the phase's row count, which only the device knows
+  const uint32_t rows = l.blk_rows ? l.n_blk : l.row_end - l.row_begin;
+  if (!rows) return;
+  const bool persist = l.done || (k.persist && (rows > (uint32_t)ctx->n_cu || l.plan_ctl));
   // [claims, waves done] (sg_sssp.hip wave_exit); a device plan's counters are zeroed by the plan kernel
   uint32_t* item_ctr = nullptr;
-  if (persist && plan_ctr) {
-    item_ctr = plan_ctr;
+  if (persist && l.plan_ctr) {
+    item_ctr = l.plan_ctr;
   } else if (persist) {
     item_ctr = ctx->r_items.get<uint32_t>(2);
     SG_HIP(hipMemsetAsync(item_ctr, 0, 8, ctx->stream));
@@ -812,28 +810,26 @@ void launch_sssp_lds(sg_ctx* ctx, const uint32_t* out_off, const uint32_t* out_a
   auto go = [&](auto kern) {
     SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)(LDS_PER_CU - SSSP_STATIC_LDS)));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, ctx->stream, out_off, out_arc, n, n_arcs, d_used, n_used,
-                       row_begin, row_begin, self_edge, e_lat, e_loss, out_lat, out_loss, sat_row, delta, vec, work,
-                       diag, claim, idle_sleep, lane_deg, blk_rows, ub_row, ub_w, item_ctr, rows, spin_max, plan_ctl,
-                       plan_ph, done);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, ctx->stream, net->out_off, net->out_arc, n, net->n_arcs,
+                       l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
+                       l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
+                       k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
+                       l.done);
   };
-  if (done) {  // the flagged one-launch plan (the default kernel shape only)
-    if (work) go(k_sssp_lds<true, 1024, 8, 0, true>);
+  // <counting, threads, lane arcs, fill symbol, flagged>
+  if (l.done) {  // the flagged one-launch plan
+    if (l.work) go(k_sssp_lds<true, 1024, 8, 0, true>);
     else if (ctx->in_fill) go(k_sssp_lds<false, 1024, 8, 1, true>);
     else go(k_sssp_lds<false, 1024, 8, 0, true>);
-  } else if (work) {
-    if (nt == 512) go(k_sssp_lds<true, 512, 8, 0>);
-    else if (la16) go(k_sssp_lds<true, 1024, 16, 0>);
-    else go(k_sssp_lds<true, 1024, 8, 0>);
+  } else if (l.work) {
+    go(k_sssp_lds<true, 1024, 8, 0>);
   } else if (ctx->in_fill) {
     go(k_sssp_lds<false, 1024, 8, 1>);
   } else {
-    if (nt == 512) go(k_sssp_lds<false, 512, 8, 0>);
-    else if (la16) go(k_sssp_lds<false, 1024, 16, 0>);
-    else if (la4) go(k_sssp_lds<false, 1024, 4, 0>);
-    else go(k_sssp_lds<false, 1024, 8, 0>);
+    go(k_sssp_lds<false, 1024, 8, 0>);
   }
   SG_CHECK_LAUNCH();
 }
+
 
 }  // namespace sg

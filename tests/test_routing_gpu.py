@@ -278,7 +278,7 @@ def test_edge_array_validation(oracle, ctx):
 @pytest.mark.parametrize("threads", ["1", "4"])
 def test_edge_array_validation_threaded(oracle, ctx, monkeypatch, request, threads):
     """Edge lists of 2^18 edges and more are checked and staged by up to 4 host threads
-    (sg_routing.hip build_net): the first bad edge in edge order still names the error when
+    (sg_net.hip build_net): the first bad edge in edge order still names the error when
     bad edges sit in several threads' ranges, and a valid graph builds the oracle's table."""
     if request.node.callspec.params["apsp_kernel"] != "lds":
         pytest.skip("host-side upload: runs once, under the lds fixture")

@@ -1,7 +1,7 @@
 //! Raw bindings to `libshadow_gpu.so`, the MI355X network core for Shadow 3.2.0.
 //!
-//! Every declaration mirrors `include/shadow_gpu.h` (ABI 7) one to one: the 73 entry
-//! points, the 15 `#[repr(C)]` structs, the opaque handles and the constants.
+//! Every declaration mirrors `include/shadow_gpu.h` (ABI 7) one to one: the 80 entry
+//! points, the 17 `#[repr(C)]` structs, the opaque handles and the constants.
 //! `tests/test_rust_binding_cpu.py` parses both files and fails on any difference in
 //! names, argument counts, argument and field types, or constant values, and on any
 //! export of the built library that this file does not declare.
@@ -52,6 +52,11 @@ pub struct sg_routing_info {
 /// One RCCL communicator bound to an `sg_ctx` (ABI 7).
 #[repr(C)]
 pub struct sg_comm {
+    _private: [u8; 0],
+}
+/// Every host's in-flight Packet events (the per-host `EventQueue`, on the device).
+#[repr(C)]
+pub struct sg_wire {
     _private: [u8; 0],
 }
 /// Every host's router `CoDelQueue` (router/codel_queue.rs).
@@ -265,6 +270,32 @@ pub struct sg_outbound_queue_state {
     pub ring_dst: *mut u32,
 }
 
+/// A window's arrivals out of the wire (device arrays of capacity `cap`): the first four
+/// arrays are an `sg_inbound_arrivals`; `src_host` / `event_id` both, or both null.
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct sg_wire_arrivals {
+    pub cap: u32,
+    pub host: *mut u32,
+    pub time_ns: *mut u64,
+    pub packet: *mut u32,
+    pub len: *mut u32,
+    pub src_host: *mut u32,
+    pub event_id: *mut u64,
+}
+
+/// The wire's events (host arrays), in canonical order (host, time, src_host, event_id).
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct sg_wire_state {
+    pub host: *mut u32,
+    pub src_host: *mut u32,
+    pub packet: *mut u32,
+    pub len: *mut u32,
+    pub time_ns: *mut u64,
+    pub event_id: *mut u64,
+}
+
 // ---------------------------------------------------------------------------
 // Constants
 // ---------------------------------------------------------------------------
@@ -473,4 +504,18 @@ unsafe extern "C" {
 
     /// The device array of the hosts' event-id counters (Host::event_id_counter).
     pub fn sg_hosts_event_ctr(hosts: *mut sg_hosts) -> *mut u64;
+
+    // ---- packets in flight: push_packet_to_host -> Host::execute's pops (worker.rs:597-607, host.rs:753-757) ----
+    pub fn sg_wire_create(ctx: *mut sg_ctx, n_hosts: u32, capacity: u64, bin_ns: u64, n_bins: u32,
+                          out: *mut *mut sg_wire) -> i32;
+    pub fn sg_wire_destroy(w: *mut sg_wire);
+    pub fn sg_wire_count(w: *const sg_wire) -> u64;
+    /// One event per delivered packet of a round; does not synchronise.
+    pub fn sg_wire_push(ctx: *mut sg_ctx, w: *mut sg_wire, packets: *const sg_packets, out: *const sg_deliveries,
+                        packet_id: *const u32, id_base: u32, len: *const u32) -> i32;
+    /// Every event with time < window_end_ns, grouped by host in EventQueue order; synchronises.
+    pub fn sg_wire_pop(ctx: *mut sg_ctx, w: *mut sg_wire, window_end_ns: u64, out: *mut sg_wire_arrivals,
+                       n_out: *mut u32, next_time_ns: *mut u64) -> i32;
+    pub fn sg_wire_get_state(w: *mut sg_wire, cap: u64, out: *mut sg_wire_state, n: *mut u64) -> i32;
+    pub fn sg_wire_set_state(w: *mut sg_wire, n: u64, input: *const sg_wire_state) -> i32;
 }

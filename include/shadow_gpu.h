@@ -658,6 +658,88 @@ int32_t sg_outbound_get_state(sg_outbound* ob, sg_outbound_queue_state* queue, s
 /* The device array of the hosts' event-id counters (Host::event_id_counter). */
 uint64_t* sg_hosts_event_ctr(sg_hosts* hosts);
 
+/* ---- packets in flight: every host's Packet events between delivery and arrival ----
+ * The reference's per-host EventQueue restricted to Packet events, on the device:
+ * WorkerShared::push_packet_to_host (worker.rs:597-607) puts a delivered packet
+ * into its destination's queue; Host::execute(until) pops every event with
+ * time < until (host.rs:753-757) in the order of event.rs:84-155, which for
+ * Packet events of one host is (time, src_host, event_id).  A delivery round's
+ * output goes in with sg_wire_push, a window's arrivals come out with
+ * sg_wire_pop in the form sg_inbound_run_ordered takes, and no packet crosses
+ * the bus while it waits (a 50 ms latency under a 1 ms runahead: ~50 rounds).
+ * The key (host, time, src_host, event_id) is unique, so what a pop returns
+ * depends only on the set of events held, never on the order they were pushed
+ * in.  Single-GPU: the sharded path's sg_record carries neither len nor a
+ * caller packet id.  Additive to ABI 7. */
+typedef struct sg_wire sg_wire; /* every host's in-flight Packet events, on the device */
+
+/* capacity: events the store may hold (at most 2^31).  bin_ns >= 1 and n_bins
+ * (rounded up to a power of two, at least 2, at most 1024): the geometry of the
+ * store's calendar -- a ring of n_bins bins of bin_ns each, later events on a far
+ * list that is re-binned as the ring advances; they affect speed only, never
+ * results (fastest with n_bins * bin_ns past the largest latency, the far list
+ * empty, and bin_ns about a round).  One exception, which only a calendar
+ * shorter than the latencies can meet: re-binning writes the far list again
+ * beside itself, and the store's memory is 1.25 x capacity records, so a pop
+ * that must re-bin (window_end has reached the ring's end) while events held +
+ * events on the far list exceed about 1.1 x capacity fails with
+ * SG_ERR_CAPACITY, the store unchanged; size capacity for both then.
+ * SG_ERR_INVALID_ARG for a zero n_hosts, capacity or bin_ns. */
+int32_t sg_wire_create(sg_ctx* ctx, uint32_t n_hosts, uint64_t capacity, uint64_t bin_ns, uint32_t n_bins,
+                       sg_wire** out);
+void sg_wire_destroy(sg_wire* w);
+/* Events held, as the host knows it without a device call: exact after
+ * sg_wire_pop / get_state / set_state; each push since adds its n_packets. */
+uint64_t sg_wire_count(const sg_wire* w);
+
+/* WorkerShared::push_packet_to_host for a whole delivery round: one event per
+ * packet i with out->status[i] == SG_PKT_DELIVERED, i.e. per entry of
+ * out->dst_order: (destination host = the bucket of out->dst_order /
+ * dst_offsets holding i, time = out->deliver_time_ns[i], src_host =
+ * packets->src_host[i], event_id = out->event_id[i], packet = packet_id ?
+ * packet_id[i] : id_base + i, len = len[i]).  packet_id (device, n_packets, may
+ * be NULL); len (device, n_packets): PacketRc::len() (packet.rs:388-390).
+ * w was created for the hosts table's n_hosts.  SG_ERR_INVALID_ARG for NULL
+ * arguments; SG_ERR_CAPACITY when sg_wire_count + packets->n_packets exceeds
+ * the capacity (checked on the host, so dropped packets count: conservative);
+ * on either the store is unchanged.  Does not synchronise. */
+int32_t sg_wire_push(sg_ctx* ctx, sg_wire* w, const sg_packets* packets, const sg_deliveries* out,
+                     const uint32_t* packet_id, uint32_t id_base, const uint32_t* len);
+
+typedef struct sg_wire_arrivals { /* device arrays of capacity cap */
+  uint32_t cap;
+  uint32_t* host;
+  uint64_t* time_ns;
+  uint32_t* packet;
+  uint32_t* len;      /* host, time_ns, packet, len: an sg_inbound_arrivals */
+  uint32_t* src_host; /* src_host and event_id: both, or both NULL */
+  uint64_t* event_id;
+} sg_wire_arrivals;
+
+/* Host::execute(until)'s pops, for every host: removes every event with
+ * time < window_end_ns (one at window_end_ns stays) and writes them grouped by
+ * ascending host, each host's in EventQueue order (time, src_host, event_id).
+ * window_end_ns need not grow from call to call; UINT64_MAX drains the store.
+ * *n_out (host): their number.  *next_time_ns (host, may be NULL): the smallest
+ * time left in the store, UINT64_MAX when empty (EventQueue::next_event_time
+ * over all hosts: an input of the manager's min_next_event_time).  With more
+ * due events than out->cap: SG_ERR_CAPACITY, *n_out = the number needed, the
+ * store unchanged.  SG_ERR_CAPACITY with a message in sg_ctx_last_error also
+ * when the store's arena has no room left.  Synchronises. */
+int32_t sg_wire_pop(sg_ctx* ctx, sg_wire* w, uint64_t window_end_ns, sg_wire_arrivals* out, uint32_t* n_out,
+                    uint64_t* next_time_ns);
+
+/* Checkpoint: all events in canonical order (host, time, src_host, event_id)
+ * into host arrays of capacity cap (SG_ERR_CAPACITY, *n = the number needed,
+ * if too small); set_state replaces the contents with n events given in any
+ * order.  Both synchronise. */
+typedef struct sg_wire_state {
+  uint32_t *host, *src_host, *packet, *len;
+  uint64_t *time_ns, *event_id;
+} sg_wire_state;
+int32_t sg_wire_get_state(sg_wire* w, uint64_t cap, sg_wire_state* out, uint64_t* n);
+int32_t sg_wire_set_state(sg_wire* w, uint64_t n, const sg_wire_state* in);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,14 +6,17 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 * routing-table build (NetworkGraph::compute_shortest_paths / get_direct_paths,
   src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`;
 * per-round packet delivery (Worker::send_packet, src/main/core/worker.rs:322-397)
-  -> `worker.deliver_round`.
+  -> `worker.deliver_round`;
+* the packets in flight between a delivery round and their arrival (the per-host
+  EventQueue, worker.rs:597-607 / host.rs:753-757) -> `wire.PacketWire`.
 
 There is no CPU fallback: if libshadow_gpu.so is missing, `load()` raises.
 """
 from ._capi import LIB_PATH, ShadowGpuError, ShadowGpuUnavailable, load  # noqa: F401
 from .graph import (Context, IpAssignment, NetworkGraph, PathProperties, PathTable,  # noqa: F401
                     RoutingInfo, default_context, generate_routing_info, ipv4_to_u32, u32_to_ipv4)
+from .wire import PacketWire  # noqa: F401
 
 __all__ = ["Context", "NetworkGraph", "PathProperties", "PathTable", "RoutingInfo", "IpAssignment",
            "generate_routing_info", "default_context", "load", "ShadowGpuError", "ShadowGpuUnavailable",
-           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH"]
+           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire"]

@@ -52,6 +52,8 @@ EXPORTED = [
     "sg_worker_get_latency", "sg_worker_get_reliability", "sg_worker_is_routable",
     "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_comm_allgather_rows", "sg_comm_exchange_padded",
     "sg_comm_alltoallv_records", "sg_comm_allgather_u64",
+    "sg_wire_create", "sg_wire_destroy", "sg_wire_count", "sg_wire_push", "sg_wire_pop", "sg_wire_get_state",
+    "sg_wire_set_state",
 ]
 
 
@@ -132,6 +134,15 @@ class sg_packets(C.Structure):
 class sg_deliveries(C.Structure):
     _fields_ = [("status", C.c_void_p), ("deliver_time_ns", C.c_void_p), ("event_id", C.c_void_p),
                 ("dst_order", C.c_void_p), ("dst_offsets", C.c_void_p)]
+
+
+class sg_wire_arrivals(C.Structure):
+    _fields_ = [("cap", C.c_uint32)] + [(k, C.c_void_p) for k in ("host", "time_ns", "packet", "len", "src_host",
+                                                                    "event_id")]
+
+
+class sg_wire_state(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("host", "src_host", "packet", "len", "time_ns", "event_id")]
 
 
 class sg_round_stats(C.Structure):
@@ -259,6 +270,13 @@ def load(path: str | None = None):
         "sg_comm_exchange_padded": (i32, [vp, vp, vp, u32, vp, vp]),
         "sg_comm_alltoallv_records": (i32, [vp, vp, u32p, vp, u32p]),
         "sg_comm_allgather_u64": (i32, [vp, vp, vp, u32]),
+        "sg_wire_create": (i32, [vp, u32, u64, u64, u32, C.POINTER(vp)]),
+        "sg_wire_destroy": (None, [vp]),
+        "sg_wire_count": (u64, [vp]),
+        "sg_wire_push": (i32, [vp, vp, C.POINTER(sg_packets), C.POINTER(sg_deliveries), vp, u32, vp]),
+        "sg_wire_pop": (i32, [vp, vp, u64, C.POINTER(sg_wire_arrivals), u32p, u64p]),
+        "sg_wire_get_state": (i32, [vp, u64, C.POINTER(sg_wire_state), u64p]),
+        "sg_wire_set_state": (i32, [vp, u64, C.POINTER(sg_wire_state)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

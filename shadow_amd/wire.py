@@ -1,0 +1,127 @@
+"""Packets in flight, on the device: host-side mirror of the per-host EventQueue
+between WorkerShared::push_packet_to_host (src/main/core/worker.rs:597-607) and
+Host::execute's pops (src/main/host/host.rs:753-757), restricted to Packet events.
+
+`PacketWire.push` takes a delivery round's output (`deliver_round`), `pop` returns
+the arrivals of a window grouped by host in EventQueue order (time, src_host,
+event_id; core/work/event.rs:84-155) as device tensors, ready for
+`InboundPipeline.run_ordered`.  Nothing crosses the bus while a packet waits.
+Every computation is a HIP kernel in libshadow_gpu.so (csrc/sg_wire.hip).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _capi
+from ._capi import check, load
+from .graph import Context, default_context
+
+# The sort tiers' limits (csrc/sg_wire.hip WR_RANK_SORT_MAX / WR_LDS_SORT_MAX): a host's due
+# segment up to RANK_SORT_MAX events is rank-sorted in a wave, up to LDS_SORT_MAX sorted in one
+# workgroup's LDS, beyond that cut into such pieces and merged.  tests/test_wire_cpu.py keeps
+# them equal to the kernel's.
+RANK_SORT_MAX = 64
+LDS_SORT_MAX = 2048
+NEVER = 2**64 - 1  # next_time_ns of an empty wire (UINT64_MAX)
+
+_STATE_KEYS = ("host", "src_host", "packet", "len", "time_ns", "event_id")
+_STATE_TYPES = (np.uint32, np.uint32, np.uint32, np.uint32, np.uint64, np.uint64)
+
+
+class PacketWire:
+    """Every host's in-flight Packet events (sg_wire_*).  capacity: events it may hold;
+    bin_ns / n_bins: the calendar's geometry, which affects speed only."""
+
+    def __init__(self, n_hosts: int, capacity: int, bin_ns: int, n_bins: int, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.n = int(n_hosts)
+        self.capacity = int(capacity)
+        h = C.c_void_p()
+        check(self.ctx.handle, load().sg_wire_create(self.ctx.handle, self.n, self.capacity, int(bin_ns), int(n_bins),
+                                                     C.byref(h)))
+        self.handle = h
+        self._out = None
+
+    @property
+    def count(self) -> int:
+        """Events held as the host knows it (exact after pop / get_state / set_state; a push adds
+        its whole batch, dropped packets included)."""
+        return int(load().sg_wire_count(self.handle))
+
+    def push(self, packets, out, length, packet_id=None, id_base: int = 0) -> None:
+        """One event per delivered packet of the round (`packets`: PacketBatch, `out`: its
+        Deliveries).  length: int32 device tensor, PacketRc::len() per packet; packet_id: int32
+        device tensor or None (then id_base + the packet's index).  Asynchronous."""
+        check(self.ctx.handle, load().sg_wire_push(
+            self.ctx.handle, self.handle, C.byref(packets.c_struct()), C.byref(out.c_struct()),
+            packet_id.data_ptr() if packet_id is not None else None, int(id_base), length.data_ptr()))
+
+    def _buffers(self, cap: int):
+        import torch
+
+        if self._out is None or self._out["host"].numel() < cap:
+            i32 = dict(dtype=torch.int32, device="cuda")
+            i64 = dict(dtype=torch.int64, device="cuda")
+            self._out = dict(host=torch.empty(cap, **i32), time_ns=torch.empty(cap, **i64),
+                             packet=torch.empty(cap, **i32), len=torch.empty(cap, **i32),
+                             src_host=torch.empty(cap, **i32), event_id=torch.empty(cap, **i64))
+        return self._out
+
+    def pop(self, window_end_ns: int, cap: Optional[int] = None) -> dict:
+        """Every event with time < window_end_ns, removed: dict(n, next_time_ns, host, time_ns,
+        packet, len, src_host, event_id), device tensors sliced to n (views of buffers the next
+        pop reuses), grouped by ascending host, each host's in EventQueue order.  cap: the output
+        capacity (default: the events held); with more due, ShadowGpuError(SG_ERR_CAPACITY)
+        whose `needed` is their number, and the wire is unchanged."""
+        cap = max(int(self.count if cap is None else cap), 0)
+        b = self._buffers(max(cap, 1))
+        o = _capi.sg_wire_arrivals(cap, *(b[k].data_ptr() for k in ("host", "time_ns", "packet", "len", "src_host",
+                                                                    "event_id")))
+        n, nxt = C.c_uint32(), C.c_uint64(NEVER)
+        rc = load().sg_wire_pop(self.ctx.handle, self.handle, int(window_end_ns), C.byref(o), C.byref(n),
+                                C.byref(nxt))
+        try:
+            check(self.ctx.handle, rc)
+        except _capi.ShadowGpuError as e:
+            e.needed = int(n.value)
+            raise
+        k = int(n.value)
+        res = dict(n=k, next_time_ns=int(nxt.value))
+        res.update({key: b[key][:k] for key in ("host", "time_ns", "packet", "len", "src_host", "event_id")})
+        return res
+
+    @staticmethod
+    def _struct(st) -> _capi.sg_wire_state:
+        return _capi.sg_wire_state(*(st[k].ctypes.data_as(C.c_void_p) for k in _STATE_KEYS))
+
+    def get_state(self) -> dict:
+        """All events in canonical order (host, time_ns, src_host, event_id): numpy arrays
+        host, src_host, packet, len (uint32), time_ns, event_id (uint64)."""
+        cap = max(self.count, 1)
+        while True:
+            st = {k: np.zeros(cap, t) for k, t in zip(_STATE_KEYS, _STATE_TYPES)}
+            n = C.c_uint64()
+            rc = load().sg_wire_get_state(self.handle, cap, C.byref(self._struct(st)), C.byref(n))
+            if rc == _capi.SG_ERR_CAPACITY and n.value > cap:
+                cap = int(n.value)
+                continue
+            check(self.ctx.handle, rc)
+            return {k: v[:n.value] for k, v in st.items()}
+
+    def set_state(self, st: dict) -> None:
+        """Replace the contents with the events of `st` (get_state's keys), in any order."""
+        a = {k: np.ascontiguousarray(st[k], dtype=t) for k, t in zip(_STATE_KEYS, _STATE_TYPES)}
+        n = len(a["host"])
+        assert all(len(v) == n for v in a.values())
+        check(self.ctx.handle, load().sg_wire_set_state(self.handle, n, C.byref(self._struct(a))))
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                load().sg_wire_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass

@@ -166,6 +166,19 @@ void timer_add_work(sg_ctx* ctx, const char* name, double work) {
   ctx->timers.back().second.work = work;
 }
 
+void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n) {
+  if (!ctx->timing) return;
+  KernelTimer* t = nullptr;
+  for (auto& kv : ctx->timers)
+    if (kv.first == name) t = &kv.second;
+  if (!t) {
+    ctx->timers.emplace_back(name, KernelTimer());
+    t = &ctx->timers.back().second;
+  }
+  t->work = work;
+  t->launches = n;
+}
+
 TimedLaunch::~TimedLaunch() {
   if (!timer) return;
   (void)hipEventRecord(e1, ctx->stream);

@@ -292,6 +292,8 @@ void stage_release(sg_ctx* ctx, int slot);
 
 // Add algorithmic work to a timer after the fact (e.g. a device-side count).
 void timer_add_work(sg_ctx* ctx, const char* name, double work);
+// A counter pair of the last build under a timer's name: read_timer gives (0, n, work).
+void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n);
 
 // RAII bracket for one instrumented launch: `TimedLaunch t(ctx, "k_walk", work);`
 // before the launch; the end event is recorded when `t` goes out of scope.
@@ -337,6 +339,20 @@ constexpr int SSSP_KB_MAX = 8;
 constexpr uint32_t SSSP_UB_EXACT = 0x80000000u;  // bound rows per bounded search (sg_sssp.hip SSSP_KB)
 bool sssp_lds_fits(uint32_t n_nodes);
 
+// Chained rows (sg_sssp.hip), in device memory: claim, one word per row of the block (0: free);
+// rel[node] its relative row (~0: not a row of the block); with a plan, phase_of / pos: a relative
+// row's phase and its place in the plan's list (null without one); exact: SG_SSSP_EXACT;
+// check_rows: 0, or the block's row count when rel was written for the block's rows only and
+// holds anything elsewhere -- an entry then counts only if used[] maps it back to its node
+// (a row block without a plan: no fill of rel on a one-shot build's path).
+struct SsspChainDesc {
+  uint32_t* claim;
+  const uint32_t* rel;
+  const uint8_t* phase_of;
+  const uint32_t* pos;
+  uint32_t exact, check_rows;
+};
+
 // One launch of the LDS search on a net (the graph arrays come from it).
 struct SsspLdsLaunch {
   // the row block: rows [row_begin, row_end) of the table (out_* device, row-major from
@@ -363,6 +379,9 @@ struct SsspLdsLaunch {
   int plan_ph = 0;
   uint32_t* plan_ctr = nullptr;
   uint32_t* done = nullptr;
+  // chained rows (sg_sssp.hip "Chained rows"; null: off): the device descriptor that
+  // sssp_device_plan / sssp_plain_rel wrote, its claim words zeroed
+  const SsspChainDesc* chain = nullptr;
 };
 void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l);
 
@@ -393,13 +412,20 @@ struct SsspDevPlan {
   uint32_t* ub_w = nullptr;
   uint32_t* ctl = nullptr;
   uint32_t* ctr = nullptr;
+  const SsspChainDesc* chain = nullptr;  // written when the caller passed claim words
   bool landmarks = false;  // phase 0 = landmark rows; phase 1's bounds come from them (sssp_landmark_bounds)
   unsigned rows_grid = 0;  // sssp_landmark_bounds' grid (one thread per row of the block)
 };
 constexpr int SSSP_PHASES_MAX = 6;
 SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                              uint32_t row_end, int n_phase, int kb, bool exact, int hops, uint32_t n_land,
-                             uint32_t* zero_rows = nullptr, uint32_t* zero_rows2 = nullptr);
+                             uint32_t* zero_rows = nullptr, uint32_t* zero_rows2 = nullptr, bool chain = false,
+                             bool chain_exact = false);
+// Without a plan: rel alone (in the plan's workspace) and the chained rows' descriptor, zeroing the
+// row flags, the claim words and the two claim counters in the same launch.
+const SsspChainDesc* sssp_plain_rel(sg_ctx* ctx, const sg_net* net, const uint32_t* d_used, uint32_t row_begin,
+                                    uint32_t row_end, uint32_t* zero_rows, uint32_t* claim, uint32_t* zero_ctr,
+                                    bool chain_exact);
 // After phase 0 (the landmarks) ran: phase 1's bound rows from the landmark rows' columns.
 void sssp_landmark_bounds(sg_ctx* ctx, const SsspDevPlan& p, uint32_t n_used, uint32_t row_begin,
                           const uint64_t* out_lat, const uint32_t* sat_row, int kb);

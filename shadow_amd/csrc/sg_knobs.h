@@ -28,7 +28,7 @@
 //   SG_APSP_TRACE | 0 | 0, 1 | diag | slab: per-pass times on stderr
 //   SG_SSSP_SEEDS | 1 | 0, 1, 2 | test | LDS search: 0 never plans, 2 always takes the phased plan
 //   SG_SSSP_FLAGGED | -1 | -1, 0, 1 | test | LDS search: the one-launch flagged plan off / on (-1: row blocks of 6+ rows per CU)
-//   SG_SSSP_PHASES | rows per CU >= 16 ? 3 : 2 | 2 .. 6 | tune | plan: phases
+//   SG_SSSP_PHASES | rows per CU >= 16 and no chained rows ? 3 : 2 | 2 .. 6 | tune | plan: phases
 //   SG_SSSP_BOUNDS | 2 | 1 .. 8 | test | plan: bound rows per bounded search
 //   SG_SSSP_EXACT | 1 | 0, 1 | tune | plan: exact seeds through zero-loss arcs
 //   SG_SSSP_HOPS | 3 | 1 .. 3 | tune | plan: hops searched for bound rows
@@ -38,6 +38,7 @@
 //   SG_SSSP_SLEEP | 0 | >= 0 | tune | LDS search: idle back-off, units of ~512 cycles
 //   SG_SSSP_LANE_DEG | 64 | >= 0 | tune | LDS search: out-degree up to which a wave takes the lane path
 //   SG_SSSP_PERSIST | 1 | 0, 1 | test | LDS search: 0 launches a workgroup per row
+//   SG_SSSP_CHAIN | 1 | 0, 1 | tune | LDS search: 0 takes rows in list order, none seeded from the row the workgroup just finished
 //   SG_SSSP_SPIN_MAX | 4194304 | >= 1 | test | LDS and bucketed searches: spin budget per wave; small values make searches give up
 //   SG_PLAN_DIAG | 0 | 0, 1 | diag | plan: phase sizes on stderr
 //   SG_DENSE_LAZY | 1 | 0, 1 | test | dense: 0 takes the T-cut search with seed rows

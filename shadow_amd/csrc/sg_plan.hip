@@ -47,15 +47,18 @@
 
 namespace sg {
 
-// rel[used row] = its relative row; also zeroes jn (and the caller's per-row flags):
-// no fills on the build's path
+// rel[used row] = its relative row; also zeroes jn (and the caller's per-row flags, and the two
+// claim counters of a launch without a plan): no fills on the build's path
 __global__ void k_plan_rel(const uint32_t* __restrict__ used, uint32_t row_begin, uint32_t rows,
                            uint32_t* __restrict__ rel, uint8_t* __restrict__ jn, uint32_t* __restrict__ zero_rows,
-                           uint32_t* __restrict__ zero_rows2) {
+                           uint32_t* __restrict__ zero_rows2, uint32_t* __restrict__ zero_ctr,
+                           SsspChainDesc* __restrict__ desc, SsspChainDesc desc_val) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (zero_ctr && r < 2) zero_ctr[r] = 0;
+  if (desc && r == 0) *desc = desc_val;  // the chained rows' descriptor (sg_sssp.hip)
   if (r >= rows) return;
   rel[used[row_begin + r]] = r;
-  jn[r] = 0;
+  if (jn) jn[r] = 0;
   if (zero_rows) zero_rows[r] = 0;
   if (zero_rows2) zero_rows2[r] = 0;
 }
@@ -252,8 +255,8 @@ constexpr uint32_t PL_CHUNKS = 64;
 template <int NT>
 __global__ void __launch_bounds__(NT)
     k_plan_lists(const uint8_t* __restrict__ jn, uint32_t rows, uint32_t row_begin, int n_phase,
-                 uint8_t* __restrict__ phase_out, uint32_t* __restrict__ list, uint32_t* __restrict__ ctl,
-                 uint32_t* __restrict__ ctr) {
+                 uint8_t* __restrict__ phase_out, uint32_t* __restrict__ list, uint32_t* __restrict__ pos,
+                 uint32_t* __restrict__ ctl, uint32_t* __restrict__ ctr) {
   constexpr int NW = NT / 64;
   __shared__ uint32_t s_cnt[SSSP_PHASES_MAX * PL_CHUNKS * NW];  // (phase, chunk, wave) counts, then offsets
   __shared__ uint32_t s_wsum[NW];
@@ -320,7 +323,11 @@ __global__ void __launch_bounds__(NT)
         if (ph == p) mine = m;
       }
       const uint32_t r = c * NT + tid;
-      if (r < rows) list[s_cnt[((uint32_t)ph * chunks + c) * NW + wv] + (uint32_t)__popcll(mine & lt)] = row_begin + r;
+      if (r < rows) {
+        const uint32_t at = s_cnt[((uint32_t)ph * chunks + c) * NW + wv] + (uint32_t)__popcll(mine & lt);
+        list[at] = row_begin + r;
+        pos[r] = at;  // the row's place in the list (sg_sssp.hip "Chained rows": its bound rows)
+      }
     };
 #pragma unroll
     for (uint32_t c = 0; c < PL_REG; c++) {
@@ -348,7 +355,10 @@ __global__ void __launch_bounds__(NT)
         pre += w < wv ? x : 0u;
         tot += x;
       }
-      if (f) list[base + pre + incl - 1] = row_begin + r;
+      if (f) {
+        list[base + pre + incl - 1] = row_begin + r;
+        pos[r] = base + pre + incl - 1;
+      }
       base += tot;
       __syncthreads();
     }
@@ -486,14 +496,15 @@ __global__ void __launch_bounds__(PB_WAVES * 64)
 
 SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                              uint32_t row_end, int n_phase, int kb, bool exact, int hops, uint32_t n_land,
-                             uint32_t* zero_rows, uint32_t* zero_rows2) {
+                             uint32_t* zero_rows, uint32_t* zero_rows2, bool chain, bool chain_exact) {
   (void)n_used;
   const uint32_t n = net->n_nodes, rows = row_end - row_begin;
   n_phase = std::max(2, std::min(SSSP_PHASES_MAX - (n_land ? 1 : 0), n_phase));
   // one workspace: list, ub_row, ub_w (rows x SSSP_KB_MAX each), ctl, ctr, rel (n), gain (rows),
-  // jn and phase (u8 rows each)
+  // pos (rows), jn and phase (u8 rows each), the chained rows' descriptor
   const size_t nl = rows, nb = (size_t)rows * SSSP_KB_MAX;
-  const size_t words = nl + 2 * nb + 4 * SSSP_PHASES_MAX + n + rows + 2 * ((rows + 3) / 4);
+  const size_t words = nl + 2 * nb + 4 * SSSP_PHASES_MAX + n + 2 * (size_t)rows + 2 * ((rows + 3) / 4) +
+                       (sizeof(SsspChainDesc) + 8) / 4;
   uint32_t* w = ctx->r_plan.get<uint32_t>(words);
   SsspDevPlan p;
   p.n_phase = n_phase;
@@ -504,15 +515,21 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
   p.ctr = p.ctl + 2 * SSSP_PHASES_MAX;
   uint32_t* rel = p.ctr + 2 * SSSP_PHASES_MAX;
   uint32_t* gain = rel + n;
-  uint8_t* jn = (uint8_t*)(gain + rows);
+  uint32_t* pos = gain + rows;
+  uint8_t* jn = (uint8_t*)(pos + rows);
   uint8_t* phase_of = jn + (rows + 3) / 4 * 4;
+  // (the descriptor holds pointers: its address rounded up to 8 bytes, which `words` leaves room for)
+  SsspChainDesc* desc = (SsspChainDesc*)(((uintptr_t)(phase_of + (rows + 3) / 4 * 4) + 7) & ~(uintptr_t)7);
+  const SsspChainDesc desc_val{zero_rows2, rel, phase_of, pos, chain_exact ? 1u : 0u, 0u};
+  if (chain) p.chain = desc;
   hipStream_t st = ctx->stream;
   {
     TimedLaunch tl(ctx, "plan_sets", 0.0);
     // rel of a node outside the block's rows reads ~0; a block of all n rows writes every entry
     if (rows != n) SG_HIP(hipMemsetAsync(rel, 0xff, (size_t)n * 4, st));
     const unsigned g = grid_for(rows, 256);
-    hipLaunchKernelGGL(k_plan_rel, dim3(g), dim3(256), 0, st, d_used, row_begin, rows, rel, jn, zero_rows, zero_rows2);
+    hipLaunchKernelGGL(k_plan_rel, dim3(g), dim3(256), 0, st, d_used, row_begin, rows, rel, jn, zero_rows, zero_rows2,
+                       (uint32_t*)nullptr, chain ? desc : (SsspChainDesc*)nullptr, desc_val);
     // in-neighbours: the CSC when directed; the out-arcs themselves when undirected
     if (net->directed) ensure_csc(ctx, net);
     const uint32_t* in_off = net->directed ? net->in_off : net->out_off;
@@ -532,7 +549,7 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
       p.rows_grid = grid_for(rows, 256);
     }
     hipLaunchKernelGGL(k_plan_lists<1024>, dim3(1), dim3(1024), 0, st, jn, rows, row_begin, n_phase, phase_of, p.list,
-                       p.ctl, p.ctr);
+                       pos, p.ctl, p.ctr);
     SG_CHECK_LAUNCH();
   }
   {
@@ -551,6 +568,24 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
     fprintf(stderr, "\n");
   }
   return p;
+}
+
+// A launch without a plan (sg_sssp.hip "Chained rows"): rel alone and the descriptor, with the row
+// flags, the claim words and the launch's two claim counters zeroed by the same kernel.
+const SsspChainDesc* sssp_plain_rel(sg_ctx* ctx, const sg_net* net, const uint32_t* d_used, uint32_t row_begin,
+                                    uint32_t row_end, uint32_t* zero_rows, uint32_t* claim, uint32_t* zero_ctr,
+                                    bool chain_exact) {
+  const uint32_t n = net->n_nodes, rows = row_end - row_begin;
+  const size_t dw = sizeof(SsspChainDesc) / 4;
+  uint32_t* w = ctx->r_plan.get<uint32_t>(dw + n);
+  SsspChainDesc* desc = (SsspChainDesc*)w;
+  uint32_t* rel = w + dw;
+  // (a row block: no fill, the search checks each entry it reads against used[])
+  const SsspChainDesc desc_val{claim, rel, nullptr, nullptr, chain_exact ? 1u : 0u, rows != n ? rows : 0u};
+  hipLaunchKernelGGL(k_plan_rel, dim3(grid_for(rows, 256)), dim3(256), 0, ctx->stream, d_used, row_begin, rows, rel,
+                     (uint8_t*)nullptr, zero_rows, claim, zero_ctr, desc, desc_val);
+  SG_CHECK_LAUNCH();
+  return desc;
 }
 
 }  // namespace sg

@@ -382,6 +382,10 @@ struct LdsKnobs {
   int n_phase, kb, hops;
   bool exact;
   uint32_t n_land;
+  // SG_SSSP_CHAIN (sg_sssp.hip "Chained rows"): a persistent workgroup's next row is one with an
+  // arc to the row it just finished, seeded from the keys still in its LDS.  Undirected graphs,
+  // the phased launches and the launch without a plan; 0 keeps the list order and the set-up.
+  bool chain;
 };
 static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used, uint32_t rows) {
   LdsKnobs k;
@@ -409,8 +413,12 @@ static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used,
   // phases by rows per CU (one box, tools/sssp_ab.py --rows, C3 graph): 39 rows per CU
   // (10k rows) 4 phases; 19.5 (a half) 3 phases, 2.25 against 2.57 ms unbounded;
   // 9.8 (a quarter) 2 phases, 1.30 against 1.38 ms
+  // With chained rows two phases: a chain bounds most of phase 0's rows, so a smaller phase 0
+  // saves less than the third launch costs (C3, one box, interleaved, tables identical:
+  // 2.60-2.62 ms at 2 phases against 2.67-2.71 at 3 and 2.75-2.77 at 4; unchained 2.82-2.85 at 2 or 3)
+  const bool chain = !knob_off("SG_SSSP_CHAIN") && !net->directed && !k.flagged;
   const uint32_t per_cu = rows / std::max(1, ctx->n_cu);
-  k.n_phase = knob_int("SG_SSSP_PHASES", per_cu >= 16 ? 3 : 2, 2, SSSP_PHASES_MAX);
+  k.n_phase = knob_int("SG_SSSP_PHASES", per_cu >= 16 && !chain ? 3 : 2, 2, SSSP_PHASES_MAX);
   k.kb = knob_int("SG_SSSP_BOUNDS", 2, 1, SSSP_KB_MAX);
   // exact seeds need a column for every node (see sg_sssp.hip "Exact seeds")
   k.exact = knob_int("SG_SSSP_EXACT", 1) != 0 && n_used == net->n_nodes;
@@ -422,6 +430,7 @@ static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used,
   // rows bounded by a neighbour: the build took 3.53 ms against 3.43 (128: 3.54, 512: 3.67).
   const int land_env = knob_int("SG_SSSP_LANDMARKS", 0);
   k.n_land = net->directed || land_env <= 0 ? 0u : (uint32_t)land_env;
+  k.chain = chain;
   return k;
 }
 
@@ -432,11 +441,22 @@ static void print_sssp_diag(sg_ctx* ctx, const sg_net* net, const unsigned long 
   copy_to_host(ctx, h.data(), diag, h.size() * 8);
   double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double setup = 0;
+  // chained against unchained rows (word 3, bit 22): rows, setup cycles, search cycles (set-up included)
+  double cn[2] = {0, 0}, cs[2] = {0, 0}, cq[2] = {0, 0};
   for (uint32_t r = 0; r < n_diag; r++) {
     for (int k = 0; k < 8; k++) a[k] += (double)h[(size_t)r * 8 + k];
-    setup += (double)(h[(size_t)r * 8 + 3] >> 24);
-    a[3] -= (double)(h[(size_t)r * 8 + 3] >> 24 << 24);
+    const unsigned long long w3 = h[(size_t)r * 8 + 3];
+    setup += (double)(w3 >> 24);
+    a[3] -= (double)(w3 >> 22 << 22);
+    if (h[(size_t)r * 8] == 0) continue;  // a row of the list past this launch's phase
+    const int c = (int)((w3 >> 22) & 1);
+    cn[c] += 1;
+    cs[c] += (double)(w3 >> 24);
+    cq[c] += (double)h[(size_t)r * 8];
   }
+  for (int c = 0; c < 2; c++)
+    fprintf(stderr, "[sssp] %s rows: %.0f, mean setup %.0f cyc, mean search %.0f cyc\n", c ? "chained" : "unchained",
+            cn[c], cs[c] / std::max(1.0, cn[c]), cq[c] / std::max(1.0, cn[c]));
   fprintf(stderr, "[sssp] mean setup (init + bound rows) %.0f cyc of the search\n", setup / n_diag);
   fprintf(stderr, "[sssp] per-wave cycles summed over a row's 16 waves: claim+wait %.0f, pop %.0f, steps %.0f "
           "(per pop: %.0f, %.0f)\n", a[5] / n_diag, a[6] / n_diag, a[7] / n_diag, a[6] / std::max(1.0, a[2]),
@@ -452,9 +472,22 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   hipStream_t st = ctx->stream;
   const uint32_t rows = row_end - row_begin;
   const LdsKnobs k = lds_knobs(ctx, net, n_used, rows);
-  uint32_t* sat = ctx->r_flags.get<uint32_t>(rows);  // zeroed by the plan's first kernel, else here
-  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS) : nullptr;
-  if (work) SG_HIP(hipMemsetAsync(work, 0, WORK_SHARDS * 8, st));
+  // the row flags, then the chained rows' claim words: zeroed by the plan's first kernel, else here
+  uint32_t* sat = ctx->r_flags.get<uint32_t>(2 * (size_t)rows);
+  uint32_t* claim = k.chain ? sat + rows : nullptr;
+  // the relaxation counters, then the chained rows' two: rows seeded in place, those with exact seeds
+  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS + 2) : nullptr;
+  if (work) SG_HIP(hipMemsetAsync(work, 0, (WORK_SHARDS + 2) * 8, st));
+  unsigned long long chained_seen[2] = {0, 0};
+  auto diag_chained = [&](const char* what, int ph) {  // SG_SSSP_DIAG: the launch's chained rows
+    if (!work || !k.diag) return;
+    unsigned long long c[2];
+    copy_to_host(ctx, c, work + WORK_SHARDS, 16);
+    fprintf(stderr, "[sssp] %s %d: %llu chained rows, %llu with exact seeds\n", what, ph, c[0] - chained_seen[0],
+            c[1] - chained_seen[1]);
+    chained_seen[0] = c[0];
+    chained_seen[1] = c[1];
+  };
   const uint32_t n_diag = std::min<uint32_t>(rows, 4096);
   unsigned long long* diag = work && k.diag ? ctx->r_misc.get<unsigned long long>((size_t)n_diag * 8) : nullptr;
   if (diag) SG_HIP(hipMemsetAsync(diag, 0, (size_t)n_diag * 64, st));
@@ -484,7 +517,8 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     launch_sssp_lds(ctx, net, l);
   } else if (k.phased) {
     const SsspDevPlan plan =
-        sssp_device_plan(ctx, net, d_used, n_used, row_begin, row_end, k.n_phase, k.kb, k.exact, k.hops, k.n_land, sat);
+        sssp_device_plan(ctx, net, d_used, n_used, row_begin, row_end, k.n_phase, k.kb, k.exact, k.hops, k.n_land, sat,
+                         claim, claim != nullptr, knob_int("SG_SSSP_EXACT", 1) != 0);
     for (int ph = 0; ph < plan.n_phase; ph++) {
       const bool bounded = ph > 0;
       SsspLdsLaunch l = base;
@@ -496,8 +530,12 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
       l.plan_ctl = plan.ctl;
       l.plan_ph = ph;
       l.plan_ctr = plan.ctr + 2 * ph;
-      TimedLaunch tl(ctx, bounded ? "sssp_bounded" : "sssp", 0.0);
-      launch_sssp_lds(ctx, net, l);
+      l.chain = plan.chain;
+      {
+        TimedLaunch tl(ctx, bounded ? "sssp_bounded" : "sssp", 0.0);
+        launch_sssp_lds(ctx, net, l);
+      }
+      diag_chained("phase", ph);
       if (ph == 0 && plan.landmarks) sssp_landmark_bounds(ctx, plan, n_used, row_begin, out_lat, sat, k.kb);
     }
   } else {
@@ -505,15 +543,26 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     // launch (two fills cost two dispatches and ~10 us of host time in a one-shot block build)
     SsspLdsLaunch l = base;
     l.plan_ctr = ctx->r_items.get<uint32_t>(2);
-    launch_zero2(ctx, sat, rows, l.plan_ctr, 2u);
-    TimedLaunch tl(ctx, "sssp", 0.0);
-    launch_sssp_lds(ctx, net, l);
+    // (chained rows need persistent workgroups, as launch_sssp_lds decides them)
+    if (claim && rows > (uint32_t)ctx->n_cu && !knob_off("SG_SSSP_PERSIST")) {
+      l.chain = sssp_plain_rel(ctx, net, d_used, row_begin, row_end, sat, claim, l.plan_ctr,
+                               knob_int("SG_SSSP_EXACT", 1) != 0);
+    } else {
+      launch_zero2(ctx, sat, rows, l.plan_ctr, 2u);
+    }
+    {
+      TimedLaunch tl(ctx, "sssp", 0.0);
+      launch_sssp_lds(ctx, net, l);
+    }
+    diag_chained("launch", 0);
   }
   if (diag) print_sssp_diag(ctx, net, diag, n_diag, k.delta);
   std::vector<uint32_t> wide_rows = finish_rows(ctx, sat, row_begin, rows);
   if (work) {
-    unsigned long long w[WORK_SHARDS];
-    timer_add_work(ctx, "sssp", read_work(ctx, work, w));
+    unsigned long long w[WORK_SHARDS + 2];
+    timer_add_work(ctx, "sssp", read_work(ctx, work, w, 2));
+    // read_timer("sssp_chained"): (0, rows with exact chain seeds, chained rows) of this build
+    timer_set_counter(ctx, "sssp_chained", (double)w[WORK_SHARDS], w[WORK_SHARDS + 1]);
   }
   if (!wide_rows.empty()) run_wide(ctx, net, d_used, n_used, wide_rows, row_begin, out_lat, out_loss);
 }

@@ -81,6 +81,36 @@
 // used node, and a bound row flagged for the wide kernel seeds bounds only.  A
 // node reached optimally through an exactly seeded neighbour row is never
 // popped: its subtree drops out of the search.
+//
+// Chained rows (SG_SSSP_CHAIN; persistent workgroups on an undirected graph, the phased
+// launches and the launch without a plan, never the flagged one).  One bound row needs no
+// publication: the row s the workgroup finished a moment ago, whose final keys are still in its
+// LDS.  After the search's closing barrier, and before the output stores are issued (a load or
+// a returning atomic issued after them would wait behind them), one wave reads s's out-arcs
+// (up to 64), maps each head t through rel to its row, keeps the rows of this block and of this
+// launch's phase whose claim word is 0, and tries them in the order (zero-loss arc, latency,
+// row) with one relaxed device-scope CAS 0 -> 1 each; the undirected upload mirrors every
+// edge (sg_net.hip), so the arc t -> s exists with the same latency w and loss.  The claim
+// words only exclude -- no data passes through them, so no fence or cache policy goes with
+// them -- and every row, listed or chained, belongs to whoever changed its word; a workgroup
+// that finds no neighbour takes the next row of the list whose word it can change.  The loop
+// is bounded by the candidates and waits for nothing another workgroup does.  Only a search
+// that ended normally chains; the sweep of the last workgroup to give up flags only rows
+// whose word is still 0 (a claimed row is its owner's to write or to flag).
+//   The chained row's set-up rewrites key[] in place, for all n nodes: a saturated key, or
+// one whose latency + w reaches LAT32_SAT - 1, becomes FKEY_INF; else (lat + w, loss, clean)
+// when exact, (lat + w + 1, 1.0, clean) when not.  The bound rows the plan lists are then
+// merged with min.  s's own key (0, 0.0) gives (w, 0.0), the arc itself.
+//   Exactness of those seeds: "Bounds" covers the inexact form.  The exact form needs a
+// zero-loss arc, SG_SSSP_EXACT, and an output pass of s that saw no saturated key.  It does
+// NOT need every node to be a used node, as the plan's exact seeds do: the LDS row has a key
+// for every node, which is the seed-for-every-node the induction above asks for.  A
+// saturated key of an UNUSED node, which no output pass sees, does no harm either: latency
+// only grows along a path, so an optimal path to a node whose optimum is below LAT32_SAT
+// passes only through such nodes, and among them s's row is a fixed point (a popped node
+// relaxed every arc, and a candidate is dropped only when it saturates) -- the induction runs
+// over those nodes alone.  A node whose optimum from t reaches LAT32_SAT starts at FKEY_INF
+// or above its optimum and ends saturated, which flags the row like any other.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -96,7 +126,8 @@ constexpr int SSSP_WAVES = SSSP_THREADS / 64;
 constexpr int SSSP_K = 4;            // expansion path: chunks of 64 arc slots a wave handles at once
 constexpr int SSSP_KB = SSSP_KB_MAX;  // bound rows per bounded search (sg_plan.hip sssp_device_plan)
 // static LDS of k_sssp_lds: ctl[8] + red[SSSP_WAVES] (u32), hb (u64), own[SSSP_WAVES][64 * SSSP_K] (u8),
-// sink[64] (u64), s_ub[SSSP_KB][3] + s_nub (u32)
+// sink[64] (u64), s_ub[SSSP_KB][3] + s_nub (u32); the slack holds s_item, s_sat, s_chain, s_cw, s_psat
+// (4,832 B in every instantiation, by the compiler's resource report)
 constexpr size_t SSSP_STATIC_LDS = 4 * (8 + SSSP_WAVES) + 16 + SSSP_WAVES * 64 * SSSP_K + 512 + 4 * (3 * SSSP_KB + 1) + 16;
 // lane path: arcs a lane has in flight (template LA; every launch uses 8);
 // used up to out-degree lane_deg_max (SG_SSSP_LANE_DEG, default 64; the arcs past LA arc-parallel)
@@ -175,9 +206,20 @@ __global__ void __launch_bounds__(NT)
                uint32_t lane_deg_max, const uint32_t* __restrict__ blk_rows,
                const uint32_t* __restrict__ ub_row, const uint32_t* __restrict__ ub_w,
                uint32_t* __restrict__ item_ctr, uint32_t n_items, uint32_t spin_max,
-               const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done) {
+               const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done,
+               const SsspChainDesc* chain_desc) {
   constexpr int NW = NT / 64;
   constexpr int AUX = FLAG ? SSSP_SC1 : 0;  // bound rows and the output: sc1 in the flagged launch
+  // Chained rows: persistent workgroups, never the flagged launch.  The claim words and the maps
+  // are read through the descriptor where they are used, from a copy of its address the compiler
+  // cannot see through: as kernel arguments they stayed in registers across the whole search.
+  if (FLAG || !item_ctr) chain_desc = nullptr;
+  const bool chain_on = chain_desc != nullptr;
+  auto chain_args = [&]() {
+    const SsspChainDesc* d = chain_desc;
+    asm volatile("" : "+s"(d));
+    return d;
+  };
   if (plan_ctl) {  // a device-built plan (sg_plan.hip): this phase's rows and bound rows, its row count
     const uint32_t base = plan_ctl[2 * plan_ph];
     n_items = plan_ctl[2 * plan_ph + 1];
@@ -233,13 +275,38 @@ __global__ void __launch_bounds__(NT)
   // atomic then overlaps the stores instead of starting the next row's setup);
   // give-ups happen only during a search, never with a claim outstanding.
   __shared__ uint32_t s_item;
-  if (item_ctr && tid == 0) s_item = atomicAdd(item_ctr, 1u);
+  // Chained rows: s_chain = 1 (the row was claimed through an arc to the row just finished, whose
+  // keys are still in key[]) | 2 (a zero-loss arc), s_cw the arc's latency; s_psat: the row just
+  // finished had a saturated key in its output (it seeds bounds only)
+  __shared__ uint32_t s_chain, s_cw, s_psat;
+  // the next row of the list (one lane): with claim words, the next one whose word this
+  // workgroup changes from 0 to 1 -- a row another workgroup chained to is skipped
+  auto next_listed = [&]() -> uint32_t {
+    uint32_t* claim_w = chain_on ? chain_args()->claim : nullptr;
+    for (;;) {
+      const uint32_t b = atomicAdd(item_ctr, 1u);
+      if (!claim_w || b >= n_items) return b;
+      const uint32_t r = blk_rows ? blk_rows[b] : row_begin + b;
+      if (atomicCAS(&claim_w[r - row_begin], 0u, 1u) == 0u) return b;
+    }
+  };
+  if (item_ctr && tid == 0) {
+    s_item = next_listed();
+    s_chain = 0u;
+    s_psat = 0u;
+  }
   for (uint32_t it = 0;; it++) {
-    uint32_t bi;
+    uint32_t bi, chain = 0, chain_w = 0;
     if (item_ctr) {
       __syncthreads();  // s_item written (first row: above; later rows: in the previous row's output)
       bi = s_item;
       if (bi >= n_items) break;
+      if (chain_on) {
+        chain = s_chain;
+        chain_w = s_cw;
+        // exact seeds: a zero-loss arc, and the row in key[] a fixed point (no saturated key)
+        if (chain > 1u && !(chain_args()->exact && !s_psat)) chain = 1u;
+      }
     } else {
       if (it) break;
       bi = blockIdx.x;
@@ -253,7 +320,25 @@ __global__ void __launch_bounds__(NT)
     const uint32_t row = blk_rows ? blk_rows[bi] : row_begin + bi;
     const uint32_t src = used[row];
     // Setup: the LDS queue and keys (out_off is staged once, before the row loop)
-    for (uint32_t v = tid; v < n; v += NT) key[v] = FKEY_INF;
+    if (chain) {
+      // Chained rows: key[] holds the finished row of a node this source has an arc to (latency
+      // chain_w); every key becomes this row's start in place -- see the header
+      const bool ex = (chain & 2u) != 0;
+      for (uint32_t v = tid; v < n; v += NT) {
+        const uint64_t kv = key[v];
+        const uint64_t l = (uint64_t)fkey_lat(kv) + chain_w;
+        uint64_t nk = FKEY_INF;
+        if (fkey_lat(kv) != LAT32_SAT && l < LAT32_SAT - 1)
+          nk = ex ? (l << 32) | ((uint32_t)kv & ~1u) : ((l + 1) << 32) | ((uint64_t)0x3F800000u << 1);
+        key[v] = nk;
+      }
+      if (COUNT && tid == 0) {
+        atomicAdd(&work[WORK_SHARDS], 1ull);
+        if (ex) atomicAdd(&work[WORK_SHARDS + 1], 1ull);
+      }
+    } else {
+      for (uint32_t v = tid; v < n; v += NT) key[v] = FKEY_INF;
+    }
     for (uint32_t i = tid; i < cap; i += NT) ring[i] = RING_EMPTY;
     for (int i = tid; i < NW * 64 * SSSP_K; i += NT) (&own[0][0])[i] = 0;
     if (tid < 8) ctl[tid] = 0;
@@ -344,7 +429,9 @@ __global__ void __launch_bounds__(NT)
           for (int g = 0; g < G; g++) {
             uint64_t kv = m[g] < LAT32_SAT - 1 ? ((m[g] + 1) << 32) | ((uint64_t)0x3F800000u << 1) : FKEY_INF;
             kv = min(kv, ex[g]);
-            if (j0 + g * NT < n_used && kv != FKEY_INF) key[vv[g]] = kv;
+            // (a chained row's keys already hold its first bound row: the smaller start wins; one
+            // thread per column, so a plain read and write)
+            if (j0 + g * NT < n_used && kv != FKEY_INF) key[vv[g]] = chain ? min((uint64_t)key[vv[g]], kv) : kv;
           }
         }
       }
@@ -355,6 +442,7 @@ __global__ void __launch_bounds__(NT)
       key[src] = 1ull;  // PathProperties::default(), dirty and queued
       ring[0] = (uint16_t)src;
       ctl[TAIL] = 1;
+      s_psat = 0u;  // (read by every thread before the set-up's barrier; set again in this row's output)
     }
     uint32_t split = delta;  // delta >= 1
     const __amdgpu_buffer_rsrc_t arcs = __builtin_amdgcn_make_buffer_rsrc((void*)out_arc, 0, (int)(n_arcs * 12u),
@@ -386,8 +474,14 @@ __global__ void __launch_bounds__(NT)
           __threadfence();
           if (atomicAdd(&item_ctr[1], 1u) == gridDim.x - 1) {
             const uint32_t c = __hip_atomic_load(&item_ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (uint32_t i = min(c, n_items); i < n_items; i++)
-              sat_row[(blk_rows ? blk_rows[i] : row_begin + i) - row_begin] = 2u;
+            // (with claim words: only the rows no workgroup chained to -- a chained row is its
+            // owner's to write or to flag)
+            uint32_t* claim_w = chain_on ? chain_args()->claim : nullptr;
+            for (uint32_t i = min(c, n_items); i < n_items; i++) {
+              const uint32_t r = (blk_rows ? blk_rows[i] : row_begin + i) - row_begin;
+              if (!claim_w || __hip_atomic_load(&claim_w[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+                sat_row[r] = 2u;
+            }
           }
         }
       }
@@ -619,7 +713,70 @@ __global__ void __launch_bounds__(NT)
 
     // ---- write the row: columns in used order, diagonal = the raw self-loop (graph/mod.rs:210-217)
     __syncthreads();  // every thread has read s_item (at the row's start) before it is written again
-    if (item_ctr && tid == 0) s_item = atomicAdd(item_ctr, 1u);  // the next row (see the row loop)
+    if (item_ctr && !chain_on) {
+      if (tid == 0) s_item = atomicAdd(item_ctr, 1u);  // the next row (see the row loop)
+    } else if (item_ctr && wv == NW - 1) {
+      // Chained rows: one wave looks for the next row among the heads of this source's out-arcs
+      // (up to 64, one per lane): a row of the block, of this launch's phase, not yet claimed;
+      // zero-loss arcs first, then by latency, then by row.  The loop tries one claim per
+      // candidate row at most and waits for nothing another workgroup does.  Four dependent
+      // round trips (arc, rel, {phase, claim word, list place}, the claim) ahead of this wave's
+      // share of the output, so the last wave takes it: its share is the smallest.
+      uint32_t ll = (uint32_t)lane;  // an opaque copy: nothing here is kept across the search
+      asm volatile("" : "+v"(ll));
+      const SsspChainDesc* cd = chain_args();
+      uint32_t* claim_w = cd->claim;
+      const uint32_t* rel = cd->rel;
+      const uint8_t* phase_of = cd->phase_of;
+      const uint32_t* list_pos = cd->pos;
+      const uint32_t a0 = off[src], nd = min(off[src + 1] - a0, 64u);
+      const bool in = ll < nd;
+      const auto r = __builtin_amdgcn_raw_buffer_load_b96(arcs, in ? (a0 + ll) * 12u : OOB, 0, 0);
+      const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)rel, 0, (int)(n * 4u), 0x00020000);
+      const uint32_t q = __builtin_amdgcn_raw_buffer_load_b32(rr, in ? r[0] * 4u : OOB, 0, 0);
+      bool ok = in && q != ~0u;
+      if (const uint32_t vr = cd->check_rows) {  // rel holds anything outside the block's rows: map q back
+        const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)used, 0, (int)(n_used * 4u), 0x00020000);
+        ok = ok && q < vr;
+        const uint32_t back = __builtin_amdgcn_raw_buffer_load_b32(ru, ok ? (row_begin + q) * 4u : OOB, 0, 0);
+        ok = ok && back == r[0];
+      }
+      // (branch-free, in flight together; the claim word past this XCD's L2, which may hold it stale)
+      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)phase_of, 0, phase_of ? 0x7FFFFFFF : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)claim_w, 0, 0x7FFFFFFF, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)list_pos, 0, list_pos ? 0x7FFFFFFF : 0, 0x00020000);
+      const uint32_t q_ph = __builtin_amdgcn_raw_buffer_load_b8(rp, ok ? q : OOB, 0, 0);
+      const uint32_t q_cl = __builtin_amdgcn_raw_buffer_load_b32(rc, ok ? q * 4u : OOB, 0, SSSP_SC1);
+      const uint32_t q_at = __builtin_amdgcn_raw_buffer_load_b32(rl, ok ? q * 4u : OOB, 0, 0);
+      const uint32_t base = list_pos ? plan_ctl[2 * plan_ph] : 0u;
+      ok = ok && q_cl == 0u && (!phase_of || q_ph == (uint32_t)plan_ph);
+      // (zero-loss arcs rank first) | latency | row: the smallest is the best
+      uint64_t sc = ok ? ((uint64_t)(r[2] != 0x3F800000u) << 63) | ((uint64_t)r[1] << 31) | q : ~0ull;
+      uint32_t got = 0, nb = ~0u, cf = 0, cw = 0;
+      for (;;) {
+        uint64_t m = sc;
+        for (int d = 32; d > 0; d >>= 1) m = min(m, (uint64_t)__shfl_xor((unsigned long long)m, d));
+        if (m == ~0ull) break;
+        const uint32_t mq = (uint32_t)m & 0x7FFFFFFFu;
+        const int win = __ffsll((long long)__ballot(sc == m)) - 1;  // parallel arcs can tie
+        uint32_t old = 1u;
+        if ((int)ll == win) old = atomicCAS(&claim_w[mq], 0u, 1u);
+        old = __shfl(old, win);
+        if (old == 0u) {
+          got = 1u;
+          cf = 1u | ((m >> 63) ? 0u : 2u);
+          cw = (uint32_t)(m >> 31);
+          nb = list_pos ? __shfl(q_at, win) - base : mq;  // (a plan's list: its place in this phase)
+          break;
+        }
+        if (ok && q == mq) sc = ~0ull;  // claimed by another workgroup: every arc to it drops out
+      }
+      if (lane == 0) {
+        s_item = got ? nb : next_listed();
+        s_chain = cf;
+        s_cw = cw;
+      }
+    }
     const size_t orow = (size_t)(row - out_row0) * n_used;
     bool sat = false;
     // the row's output: nontemporal 16-B stores; in the flagged launch sc1 (write-through) stores,
@@ -732,11 +889,13 @@ __global__ void __launch_bounds__(NT)
     if (__any(sat) && lane == 0) {
       sat_row[row - row_begin] = 1u;
       if (FLAG) s_sat = 1u;
+      if (chain_on) s_psat = 1u;
     }
     if (dg) {
       diag[bi * 8 + 0] = c_search - c_start;
       diag[bi * 8 + 1] = clock64() - c_search;
-      diag[bi * 8 + 3] = n_adv | ((c_setup - c_start) << 24);  // bucket advances | setup cycles
+      // bucket advances (< 2^22) | chained, exact (bits 22, 23) | setup cycles
+      diag[bi * 8 + 3] = n_adv | ((unsigned long long)chain << 22) | ((c_setup - c_start) << 24);
     }
     if constexpr (FLAG) {
       // Flagged rows: every wave waits for its sc1 stores, then one lane publishes the row
@@ -807,6 +966,9 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
     SG_HIP(hipMemsetAsync(item_ctr, 0, 8, ctx->stream));
   }
   const uint32_t grid = persist ? (uint32_t)ctx->n_cu : rows;
+  // Chained rows: persistent workgroups on an undirected graph (the arc t -> s mirrors s -> t),
+  // never the flagged launch (the caller passes claim words only with SG_SSSP_CHAIN on)
+  const SsspChainDesc* chain = persist && !l.done && !net->directed ? l.chain : nullptr;
   auto go = [&](auto kern) {
     SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)(LDS_PER_CU - SSSP_STATIC_LDS)));
@@ -814,7 +976,7 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
                        l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
                        l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
                        k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
-                       l.done);
+                       l.done, chain);
   };
   // <counting, threads, lane arcs, fill symbol, flagged>
   if (l.done) {  // the flagged one-launch plan

@@ -479,14 +479,30 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS + 2) : nullptr;
   if (work) SG_HIP(hipMemsetAsync(work, 0, (WORK_SHARDS + 2) * 8, st));
   unsigned long long chained_seen[2] = {0, 0};
-  auto diag_chained = [&](const char* what, int ph) {  // SG_SSSP_DIAG: the launch's chained rows
-    if (!work || !k.diag) return;
+  unsigned long long phase_chained[SSSP_PHASES_MAX] = {};
+  // counting mode: the rows this launch chained (kept per phase; SG_SSSP_DIAG prints them)
+  auto diag_chained = [&](const char* what, int ph) {
+    if (!work) return;
     unsigned long long c[2];
     copy_to_host(ctx, c, work + WORK_SHARDS, 16);
-    fprintf(stderr, "[sssp] %s %d: %llu chained rows, %llu with exact seeds\n", what, ph, c[0] - chained_seen[0],
-            c[1] - chained_seen[1]);
+    phase_chained[ph] = c[0] - chained_seen[0];
+    if (k.diag)
+      fprintf(stderr, "[sssp] %s %d: %llu chained rows, %llu with exact seeds\n", what, ph, c[0] - chained_seen[0],
+              c[1] - chained_seen[1]);
     chained_seen[0] = c[0];
     chained_seen[1] = c[1];
+  };
+  // counting mode: read_timer("sssp_phase<p>") = (0, rows of the plan's phase p, rows chained in its launch)
+  auto publish_phases = [&](const SsspDevPlan& plan) {
+    if (!work) return;
+    uint32_t h[2 * SSSP_PHASES_MAX];
+    copy_to_host(ctx, h, plan.ctl, sizeof(h));
+    for (int p = 0; p < SSSP_PHASES_MAX; p++) {
+      char name[24];
+      snprintf(name, sizeof(name), "sssp_phase%d", p);
+      const bool on = p < plan.n_phase;  // (ctl past the plan's phases is not written)
+      timer_set_counter(ctx, name, on ? (double)phase_chained[p] : 0.0, on ? h[2 * p + 1] : 0u);
+    }
   };
   const uint32_t n_diag = std::min<uint32_t>(rows, 4096);
   unsigned long long* diag = work && k.diag ? ctx->r_misc.get<unsigned long long>((size_t)n_diag * 8) : nullptr;
@@ -513,8 +529,11 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     l.ub_w = plan.ub_w;
     l.plan_ctr = plan.ctr;
     l.done = done;
-    TimedLaunch tl(ctx, "sssp", 0.0);
-    launch_sssp_lds(ctx, net, l);
+    {
+      TimedLaunch tl(ctx, "sssp", 0.0);
+      launch_sssp_lds(ctx, net, l);
+    }
+    publish_phases(plan);  // (the one launch chains no rows)
   } else if (k.phased) {
     const SsspDevPlan plan =
         sssp_device_plan(ctx, net, d_used, n_used, row_begin, row_end, k.n_phase, k.kb, k.exact, k.hops, k.n_land, sat,
@@ -538,6 +557,7 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
       diag_chained("phase", ph);
       if (ph == 0 && plan.landmarks) sssp_landmark_bounds(ctx, plan, n_used, row_begin, out_lat, sat, k.kb);
     }
+    publish_phases(plan);
   } else {
     // without a plan: the row flags and the persistent workgroups' claim counters zeroed by one
     // launch (two fills cost two dispatches and ~10 us of host time in a one-shot block build)

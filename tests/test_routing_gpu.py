@@ -420,8 +420,8 @@ def test_c3_full_table(c3_oracle, ctx):
 
 def test_c3_row_blocks(c3_oracle, ctx, apsp_kernel):
     """The row blocks one rank builds in a sharded C3 build (bench.py at N = 2, 4, 8): their
-    own phase plans (3, 2 and no phases by rows per CU, bounds only from rows in the block),
-    every cell against the oracle's rows."""
+    own plans (by rows per CU: the flagged one-launch plan of 3 phases, of 2, and no plan below 6
+    rows per CU; bounds only from rows in the block), every cell against the oracle's rows."""
     import torch
 
     if apsp_kernel == "slab":

@@ -296,6 +296,20 @@ pub struct sg_wire_state {
     pub event_id: *mut u64,
 }
 
+/// An `sg_record` after `sg_wire_stamp_records[_padded]`: same size, same offsets; the low half
+/// of `order_key` carries `len`, `packet` the caller's packet id.  It travels through the
+/// exchanges as an `sg_record`; never hand one to `sg_deliver_bucket[_padded]`.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct sg_wire_record {
+    pub deliver_time_ns: u64,
+    pub len: u32,
+    pub src_host: u32,
+    pub event_id: u64,
+    pub packet_id: u32,
+    pub dst_host: u32,
+}
+
 // ---------------------------------------------------------------------------
 // Constants
 // ---------------------------------------------------------------------------
@@ -518,4 +532,20 @@ unsafe extern "C" {
                        n_out: *mut u32, next_time_ns: *mut u64) -> i32;
     pub fn sg_wire_get_state(w: *mut sg_wire, cap: u64, out: *mut sg_wire_state, n: *mut u64) -> i32;
     pub fn sg_wire_set_state(w: *mut sg_wire, n: u64, input: *const sg_wire_state) -> i32;
+
+    // ---- the wire on the sharded path: stamp on the source rank, push on the owner ----
+    /// After sg_deliver_source: len and the caller's packet id into the records, in place.
+    pub fn sg_wire_stamp_records(ctx: *mut sg_ctx, send: *mut sg_record, n_records: u32, packet_id: *const u32,
+                                 id_base: u32, len: *const u32, n_packets: u32) -> i32;
+    /// After sg_deliver_source_padded: the valid slots of every block and the spilled records.
+    pub fn sg_wire_stamp_records_padded(ctx: *mut sg_ctx, send_padded: *mut sg_record, send: *mut sg_record,
+                                        n_ranks: u32, cap: u32, xrow: *const u64, packet_id: *const u32,
+                                        id_base: u32, len: *const u32, n_packets: u32) -> i32;
+    /// One event per stamped record received; does not synchronise.
+    pub fn sg_wire_push_records(ctx: *mut sg_ctx, w: *mut sg_wire, recv: *const sg_record, n_records: u32,
+                                host_map: *const u32, n_hosts: u32) -> i32;
+    /// The valid records of every block of a fixed-split exchange; nothing when the round overflowed.
+    pub fn sg_wire_push_records_padded(ctx: *mut sg_ctx, w: *mut sg_wire, recv_padded: *const sg_record,
+                                       n_ranks: u32, cap: u32, xall: *const u64, rank: u32, host_map: *const u32,
+                                       n_hosts: u32) -> i32;
 }

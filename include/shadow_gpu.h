@@ -669,8 +669,8 @@ uint64_t* sg_hosts_event_ctr(sg_hosts* hosts);
  * the bus while it waits (a 50 ms latency under a 1 ms runahead: ~50 rounds).
  * The key (host, time, src_host, event_id) is unique, so what a pop returns
  * depends only on the set of events held, never on the order they were pushed
- * in.  Single-GPU: the sharded path's sg_record carries neither len nor a
- * caller packet id.  Additive to ABI 7. */
+ * in.  On the sharded path (one rank per GPU) the owner rank pushes the records
+ * it received: see "the wire on the sharded path" below.  Additive to ABI 7. */
 typedef struct sg_wire sg_wire; /* every host's in-flight Packet events, on the device */
 
 /* capacity: events the store may hold (at most 2^31).  bin_ns >= 1 and n_bins
@@ -725,7 +725,14 @@ typedef struct sg_wire_arrivals { /* device arrays of capacity cap */
  * over all hosts: an input of the manager's min_next_event_time).  With more
  * due events than out->cap: SG_ERR_CAPACITY, *n_out = the number needed, the
  * store unchanged.  SG_ERR_CAPACITY with a message in sg_ctx_last_error also
- * when the store's arena has no room left.  Synchronises. */
+ * when the store's arena has no room left.  Synchronises.
+ * On the sharded path this is the round's synchronising call, so it also
+ * reports what sg_deliver_source_padded could not: if that call's batch was
+ * rejected (SG_ERR_UNSORTED, SG_ERR_INVALID_ARG for a source host or route row
+ * out of range: nothing was delivered, no record sent) or overflowed
+ * (SG_ERR_TIME_OVERFLOW), and no sg_deliver_bucket_padded has reported it, the
+ * first pop on the context afterwards returns that error, once.  The pop itself
+ * is then complete: *n_out, *next_time_ns and out are as on SG_OK. */
 int32_t sg_wire_pop(sg_ctx* ctx, sg_wire* w, uint64_t window_end_ns, sg_wire_arrivals* out, uint32_t* n_out,
                     uint64_t* next_time_ns);
 
@@ -739,6 +746,80 @@ typedef struct sg_wire_state {
 } sg_wire_state;
 int32_t sg_wire_get_state(sg_wire* w, uint64_t cap, sg_wire_state* out, uint64_t* n);
 int32_t sg_wire_set_state(sg_wire* w, uint64_t n, const sg_wire_state* in);
+
+/* ---- the wire on the sharded path (additive to ABI 7) ----------------------
+ * With hosts partitioned over ranks, WorkerShared::push_packet_to_host
+ * (worker.rs:597-607) runs on the destination's owner, which holds only the
+ * sg_records it received.  The wire needs, per event, (time, src_host, event
+ * id, destination, len, packet id).  Of an sg_record's 32 bytes the owner has
+ * no use for two words: k, the low half of order_key (it restarts every round;
+ * the wire orders by the real, unique (time, src_host, event_id)), and
+ * `packet` (an index into the SOURCE rank's batch).  The source rank writes
+ * len and the caller's packet id there -- "stamps" the record -- and the record
+ * then reads as an sg_wire_record.  Size and every other field are unchanged, so
+ * sg_comm_exchange_padded, sg_comm_alltoallv_records and
+ * sg_deliver_pad_to_compact move stamped records exactly as they move records.
+ * A stamped record MUST NOT be given to sg_deliver_bucket[_padded]: its
+ * order_key is no longer an order key.  A round is
+ *   source rank: sg_deliver_source[_padded], sg_wire_stamp_records[_padded]
+ *   exchange:    as before
+ *   owner rank:  sg_wire_push_records[_padded], sg_wire_pop,
+ *                sg_inbound_run_ordered
+ * sg_deliver_source_padded's batch errors, which sg_deliver_bucket_padded
+ * reports on the path without a wire, are returned by sg_wire_pop here.       */
+typedef struct sg_wire_record {
+  uint64_t deliver_time_ns;
+  uint32_t len;       /* PacketRc::len() (packet.rs:388-390); was the low half of order_key */
+  uint32_t src_host;  /* the high half of order_key, unchanged */
+  uint64_t event_id;  /* src_host_event_id */
+  uint32_t packet_id; /* the caller's packet id; was `packet` */
+  uint32_t dst_host;  /* HostId of the destination */
+} sg_wire_record;
+
+/* Stamp, in place, the n_records records sg_deliver_source wrote to `send`: for
+ * record k with p = send[k].packet, the low 32 bits of order_key become len[p]
+ * and packet becomes packet_id ? packet_id[p] : id_base + p.  packet_id (may be
+ * NULL) and len: device arrays of n_packets, as sg_wire_push's.  A record with
+ * p >= n_packets is left alone.  Stamp once: a second call would read packet
+ * ids as indices.  On the context's stream; does not synchronise. */
+int32_t sg_wire_stamp_records(sg_ctx* ctx, sg_record* send, uint32_t n_records, const uint32_t* packet_id,
+                              uint32_t id_base, const uint32_t* len, uint32_t n_packets);
+/* The same after sg_deliver_source_padded, with its send_padded, send, n_ranks,
+ * cap and xrow: stamps the valid slots of every block, [r cap, r cap +
+ * min(xrow[3 + r], cap)), and the records past cap at their compact positions
+ * in `send` (n_packets records), so that a later sg_deliver_pad_to_compact
+ * yields a compact array stamped throughout.  No slot is stamped twice and none
+ * outside those is touched.  The counts are read on the device: does not
+ * synchronise. */
+int32_t sg_wire_stamp_records_padded(sg_ctx* ctx, sg_record* send_padded, sg_record* send, uint32_t n_ranks,
+                                     uint32_t cap, const uint64_t* xrow, const uint32_t* packet_id, uint32_t id_base,
+                                     const uint32_t* len, uint32_t n_packets);
+
+/* WorkerShared::push_packet_to_host (worker.rs:597-607) on the owner rank: one
+ * event per stamped record of recv (device, n_records).  The event's host is
+ * host_map ? host_map[dst_host] : dst_host; host_map (device, n_hosts entries,
+ * may be NULL) is e.g. the partition's host_local for a wire over the rank's own
+ * hosts.  Errors as sg_wire_push: SG_ERR_CAPACITY when sg_wire_count + n_records
+ * exceeds the capacity, the store unchanged.  A bad destination (dst_host >=
+ * n_hosts, or a host that is UINT32_MAX or not below the wire's n_hosts) cannot
+ * be reported without a synchronisation: the call returns SG_OK, the store is
+ * incomplete from then on, and the next sg_wire_pop (or get_state) returns
+ * SG_ERR_INVALID_ARG with a message naming this call; sg_wire_set_state starts
+ * the store afresh.  Does not synchronise. */
+int32_t sg_wire_push_records(sg_ctx* ctx, sg_wire* w, const sg_record* recv, uint32_t n_records,
+                             const uint32_t* host_map, uint32_t n_hosts);
+/* The same for the blocks of a fixed-split exchange: the valid records of every
+ * block of recv_padded (block b holds min(xall[b][3 + rank], cap)), xall read on
+ * the device.  If the largest count in xall exceeds cap the call appends
+ * NOTHING: every rank sees the same xall and runs the exact exchange, whose
+ * sg_wire_push_records carries all the round's records.  The caller learns that
+ * from its own copy of xall; the round's one synchronisation remains the pop's.
+ * sg_wire_count rises by n_ranks * cap whatever the blocks hold (conservative,
+ * as sg_wire_push's count of dropped packets; the next pop makes it exact), and
+ * SG_ERR_CAPACITY is returned when that would pass the capacity. */
+int32_t sg_wire_push_records_padded(sg_ctx* ctx, sg_wire* w, const sg_record* recv_padded, uint32_t n_ranks,
+                                    uint32_t cap, const uint64_t* xall, uint32_t rank, const uint32_t* host_map,
+                                    uint32_t n_hosts);
 
 #ifdef __cplusplus
 }

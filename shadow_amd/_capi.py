@@ -53,7 +53,8 @@ EXPORTED = [
     "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_comm_allgather_rows", "sg_comm_exchange_padded",
     "sg_comm_alltoallv_records", "sg_comm_allgather_u64",
     "sg_wire_create", "sg_wire_destroy", "sg_wire_count", "sg_wire_push", "sg_wire_pop", "sg_wire_get_state",
-    "sg_wire_set_state",
+    "sg_wire_set_state", "sg_wire_stamp_records", "sg_wire_stamp_records_padded", "sg_wire_push_records",
+    "sg_wire_push_records_padded",
 ]
 
 
@@ -277,6 +278,10 @@ def load(path: str | None = None):
         "sg_wire_pop": (i32, [vp, vp, u64, C.POINTER(sg_wire_arrivals), u32p, u64p]),
         "sg_wire_get_state": (i32, [vp, u64, C.POINTER(sg_wire_state), u64p]),
         "sg_wire_set_state": (i32, [vp, u64, C.POINTER(sg_wire_state)]),
+        "sg_wire_stamp_records": (i32, [vp, vp, u32, vp, u32, vp, u32]),
+        "sg_wire_stamp_records_padded": (i32, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32]),
+        "sg_wire_push_records": (i32, [vp, vp, vp, u32, vp, u32]),
+        "sg_wire_push_records_padded": (i32, [vp, vp, vp, u32, u32, vp, u32, vp, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

@@ -1761,8 +1761,15 @@ static RoundWork source_phase(sg_ctx* ctx, sg_hosts* hs, const sg_table* tab, co
   return w;
 }
 
+void report_round_flags(sg_ctx* ctx) {
+  if (!ctx->round_flags_pending) return;
+  ctx->round_flags_pending = false;
+  fail_flags(((const volatile sg_round_ret*)ctx->round_ret)->err);
+}
+
 static void finish(sg_ctx* ctx, const RoundWork& w, sg_round_stats* stats) {
   SG_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->round_flags_pending = false;  // (this round's flags replace them, and are reported here)
   unsigned long long s[3] = {0, ~0ull, ~0ull};
   uint32_t err = 0;
   if (w.walked) {  // written by k_reduce_stats into mapped host memory; the sync made it visible
@@ -1830,6 +1837,7 @@ static void deliver_source_padded(sg_ctx* ctx, sg_hosts* hs, const sg_table* tab
   hipStream_t st = ctx->stream;
   const uint32_t P = pk->n_packets;
   RoundWork w = source_phase(ctx, hs, tab, rd, pk, status, deliver, eid, true, false, xrow);
+  ctx->round_flags_pending = true;  // reported by the round's synchronising call: the bucketing, or sg_wire_pop
   const uint32_t nb = std::max<uint32_t>(1, std::min<uint32_t>(grid_for(P, PACK_BLOCK * 8), 2048));
   uint32_t* bc = ctx->d_cnt.get<uint32_t>((size_t)n_ranks * nb + 1);
   uint32_t* bo = ctx->d_scan.get<uint32_t>((size_t)n_ranks * nb + 1);
@@ -1868,6 +1876,7 @@ static void deliver_bucket_padded(sg_ctx* ctx, const sg_record* recv, uint32_t n
   SG_CHECK_LAUNCH();
   SG_HIP(hipStreamSynchronize(st));
   const volatile sg_round_ret* r = ctx->round_ret;
+  ctx->round_flags_pending = false;
   fail_flags(r->err);
   if (region && r->overflow) {  // a hot destination overfilled its region
     SG_HIP(hipMemsetAsync(ws, 0, 8 * 4, st));

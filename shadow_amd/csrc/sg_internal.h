@@ -120,6 +120,9 @@ struct sg_ctx {
   // the round's stats and error flags straight from that kernel: no copies.
   uint32_t* round_err = nullptr;
   sg_round_ret* round_ret = nullptr;
+  // sg_deliver_source_padded does not synchronise: its flags sit in round_ret until a call that
+  // does reads them (sg_deliver_bucket_padded, or sg_wire_pop on the wire's path); set until then.
+  bool round_flags_pending = false;
   // Region bucketing counters, two parities of [SB_SUB x SB_MAX counts + overflow
   // flag] (zeroed at creation; each call's sort kernel clears the other parity),
   // then two parities for the coarse level of two-level scatters (cleared by the
@@ -289,6 +292,10 @@ void copy_to_host(sg_ctx* ctx, void* dst, const void* src, size_t bytes);
 // and returns it (grown to `bytes`); stage_release after the hipMemcpyAsync out of it.
 char* stage_acquire(sg_ctx* ctx, int slot, size_t bytes);
 void stage_release(sg_ctx* ctx, int slot);
+
+// After a synchronisation of the context's stream: throws the error of a padded source phase
+// whose flags no call has reported yet (sg_deliver.hip); otherwise nothing.
+void report_round_flags(sg_ctx* ctx);
 
 // Add algorithmic work to a timer after the fact (e.g. a device-side count).
 void timer_add_work(sg_ctx* ctx, const char* name, double work);

@@ -42,6 +42,12 @@
 // again under the new (base, hz), to ring rows or to the other far row.
 //
 //   push: k_wire_count, k_wire_alloc, k_wire_scatter
+//         from a delivery round's buckets (sg_wire_push), or on an owner rank of the sharded
+//         path from the records it received (sg_wire_push_records[_padded]): the source rank
+//         has written len and the caller's packet id into the two words of the 32-byte
+//         sg_record the owner does not need (k_wire_stamp, sg_wire_stamp_records[_padded]), so
+//         the exchange moves what it always moved and the append reads one record per event
+//         k_wire_stamp (source rank), k_wire_padded_valid (the blocks' record counts, from xall)
 //   pop:  k_wire_plan      the rows to scan, the new base / horizon
 //         k_wire_popcount  due records per destination host (and the far records' new rows)
 //         (scan)           host offsets
@@ -53,6 +59,7 @@
 //         k_wire_sort_small / k_wire_sort_lds / k_wire_merge   the three sort tiers
 //         k_wire_compact_list / _move / _finish   after the pop, when the straddling row needs it
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -72,8 +79,21 @@ constexpr int WR_ITEMS = 8;             // records per thread and step of the ap
 constexpr uint64_t WR_TOMB = ~0ull;      // time of a record that has left its row
 constexpr uint32_t WR_DEAD_SHARE = 8;    // a row is compacted when its tombstones reach live / 8 (and a chunk)
 constexpr uint64_t WR_CAP_MAX = 1ull << 31;
+constexpr uint32_t WR_MAX_RANKS = 64;    // ranks of a fixed-split exchange at most (sg_deliver.hip's MAX_RANKS)
 
-enum : uint32_t { WE_ARENA = 1, WE_CORRUPT = 2 };                                  // WireCtl::err (sticky)
+// A stamped record travels as an sg_record: through every sg_comm_* exchange and
+// sg_deliver_pad_to_compact unchanged.
+static_assert(sizeof(sg_wire_record) == sizeof(sg_record) && sizeof(sg_record) == 32, "sg_wire_record");
+static_assert(offsetof(sg_wire_record, deliver_time_ns) == offsetof(sg_record, deliver_time_ns) &&
+                  offsetof(sg_wire_record, len) == offsetof(sg_record, order_key) &&
+                  offsetof(sg_wire_record, src_host) == offsetof(sg_record, order_key) + 4 &&
+                  offsetof(sg_wire_record, event_id) == offsetof(sg_record, event_id) &&
+                  offsetof(sg_wire_record, packet_id) == offsetof(sg_record, packet) &&
+                  offsetof(sg_wire_record, dst_host) == offsetof(sg_record, dst_host),
+              "sg_wire_record is a second reading of sg_record");
+
+// WireCtl::err (sticky).  WE_BADDST: a pushed record named a destination outside the hosts
+enum : uint32_t { WE_ARENA = 1, WE_CORRUPT = 2, WE_BADDST = 4 };
 enum : uint32_t { WV_OK = 0, WV_CAP = 1, WV_ERR = 2, WV_ARENA = 3 };  // WirePlan::verdict
 
 struct WireCtl {
@@ -83,7 +103,9 @@ struct WireCtl {
   uint32_t far;                 // the live far row (n_bins or n_bins + 1)
   uint32_t nfree;               // chunks on the free list
   uint32_t err;                 // WE_*: a push found no room; the store is no longer whole
-  uint32_t pad_;
+  // Set while a push's count pass runs, by records with no host here; k_wire_alloc, alone on the
+  // device, moves it into err: err itself never changes under a kernel that branches on it.
+  uint32_t bad;
 };
 
 struct WirePlan {
@@ -102,7 +124,8 @@ struct WireRet {  // pinned, written by k_wire_final
   unsigned long long next, held, pushed;
   // the straddling row, when its tombstones have reached an eighth of its live records (and a
   // chunk): compact it (row = ~0u: nothing to do); its slots in use and its live records
-  uint32_t compact_row, compact_cnt, compact_keep, pad_;
+  uint32_t compact_row, compact_cnt, compact_keep;
+  uint32_t err;  // WireCtl::err
 };
 
 struct WireDev {
@@ -235,6 +258,127 @@ struct SrcArray {
   }
 };
 
+// Received records of the sharded path, stamped on their source rank (sg_wire_record: time |
+// len, src_host | event id | packet id, dst_host).  The destination stands in the record: no
+// search, and no gather but host_map's.  A destination outside host_map, or mapped to no host of
+// this wire, is left out by both passes and flagged (WireCtl::bad, then WE_BADDST: the next pop
+// reports it).
+struct SrcRecords {
+  const uint4* recs;
+  const uint32_t* host_map;  // may be null: the destination is the wire's host
+  uint32_t* bad;             // &WireCtl::bad
+  uint32_t count, n_map, n_hosts;
+  __device__ uint32_t n() const { return count; }
+  __device__ bool host(uint32_t d, uint32_t* h) const {
+    if (d >= n_map) return false;
+    *h = host_map ? host_map[d] : d;
+    return *h < n_hosts;  // (UINT32_MAX, a host of another rank, included)
+  }
+  __device__ bool time(uint32_t i, unsigned long long* t) const {
+    const uint4 a = recs[2 * (size_t)i];
+    *t = ((unsigned long long)a.y << 32) | a.x;
+    if (*t == WR_TOMB) return false;
+    uint32_t h;
+    if (host(recs[2 * (size_t)i + 1].w, &h)) return true;
+    atomicOr(bad, 1u);
+    return false;
+  }
+  __device__ bool load(uint32_t i, Rec* r) const {
+    const uint4 a = recs[2 * (size_t)i], b = recs[2 * (size_t)i + 1];
+    r->time = ((unsigned long long)a.y << 32) | a.x;
+    if (r->time == WR_TOMB || !host(b.w, &r->dst)) return false;
+    r->len = a.z;
+    r->src = a.w;
+    r->eid = ((unsigned long long)b.y << 32) | b.x;
+    r->packet = b.z;
+    return true;
+  }
+};
+
+// The blocks of a fixed-split exchange: slot i is record i % cap of block i / cap, a record when
+// that is below valid[block] (k_wire_padded_valid: all zero when the round overflowed its blocks).
+struct SrcPaddedRecords {
+  SrcRecords recs;
+  const uint32_t* valid;
+  uint32_t cap;
+  __device__ uint32_t n() const { return recs.count; }
+  __device__ bool time(uint32_t i, unsigned long long* t) const {
+    return i % cap < valid[i / cap] && recs.time(i, t);
+  }
+  __device__ bool load(uint32_t i, Rec* r) const { return i % cap < valid[i / cap] && recs.load(i, r); }
+};
+
+// One wave: valid[b] = the records block b of recv_padded holds for `rank`, min(xall[b][3 + rank],
+// cap); or 0 for every block when any pair's count exceeds cap: the round is then exchanged again
+// exactly (every rank sees the same xall), and that exchange's push carries all its records.
+__global__ void __launch_bounds__(64) k_wire_padded_valid(const unsigned long long* xall, uint32_t n_ranks,
+                                                          uint32_t rank, uint32_t cap, uint32_t* valid) {
+  const uint32_t b = threadIdx.x, wd = 3 + n_ranks;
+  unsigned long long pm = 0;
+  if (b < n_ranks)
+    for (uint32_t r = 0; r < n_ranks; r++) pm = max(pm, xall[(size_t)b * wd + 3 + r]);
+  for (int d = 32; d > 0; d >>= 1) pm = max(pm, (unsigned long long)__shfl_xor(pm, d, 64));
+  if (b < n_ranks) valid[b] = pm > cap ? 0u : (uint32_t)min(xall[(size_t)b * wd + 3 + rank], (unsigned long long)cap);
+}
+
+// ---- stamp (on the source rank) -----------------------------------------------
+// len and the caller's packet id into the two words of a record its owner does not read: the low
+// half of order_key and `packet` (until now the index p into this rank's batch).  Not idempotent
+// (the second word is its own input), so every slot is visited once.
+struct WireStamp {
+  const uint32_t *packet_id, *len;
+  uint32_t id_base, n_packets;
+};
+
+__device__ __forceinline__ void wire_stamp(uint32_t* recs, size_t i, const WireStamp& s) {
+  const uint32_t p = recs[8 * i + 6];
+  if (p >= s.n_packets) return;
+  recs[8 * i + 2] = s.len[p];
+  recs[8 * i + 6] = s.packet_id ? s.packet_id[p] : s.id_base + p;
+}
+
+// PADDED 0: records [0, n) of `recs`.  PADDED 1: the layout k_owner_scatter writes and
+// k_pad_to_compact reads (sg_deliver.hip): the first min(count_r, cap) records for rank r in block
+// r of `recs`, the others at their compact positions start_r + k (k >= cap) of `spill`, an array
+// of s.n_packets records; the counts are xrow[3 + r], read here, on the device.
+template <int PADDED>
+__global__ void __launch_bounds__(WR_THREADS) k_wire_stamp(uint32_t* recs, uint32_t* spill, uint32_t n,
+                                                          uint32_t n_ranks, uint32_t cap,
+                                                          const unsigned long long* xrow, WireStamp s) {
+  const size_t t0 = (size_t)blockIdx.x * WR_THREADS + threadIdx.x, step = (size_t)gridDim.x * WR_THREADS;
+  if (!PADDED) {
+    for (size_t i = t0; i < n; i += step) wire_stamp(recs, i, s);
+    return;
+  }
+  __shared__ unsigned long long s_cnt[WR_MAX_RANKS], s_start[WR_MAX_RANKS], s_spill[WR_MAX_RANKS + 1];
+  if (threadIdx.x == 0) {
+    unsigned long long a = 0, sp = 0;
+    for (uint32_t r = 0; r < n_ranks; r++) {
+      const unsigned long long c = min(xrow[3 + r], (unsigned long long)s.n_packets);
+      s_cnt[r] = c;
+      s_start[r] = a;
+      s_spill[r] = sp;
+      a += c;
+      sp += c > cap ? c - cap : 0;
+    }
+    s_spill[n_ranks] = sp;
+  }
+  __syncthreads();
+  const size_t blocks = (size_t)n_ranks * cap, total = blocks + (size_t)s_spill[n_ranks];
+  for (size_t e = t0; e < total; e += step) {
+    if (e < blocks) {
+      const uint32_t r = (uint32_t)(e / cap);
+      if (e - (size_t)r * cap < s_cnt[r]) wire_stamp(recs, e, s);
+    } else {
+      const unsigned long long j = e - blocks;
+      uint32_t r = 0;  // the rank whose spilled records [s_spill[r], s_spill[r + 1]) hold j
+      while (s_spill[r + 1] <= j) r++;
+      const unsigned long long pos = s_start[r] + cap + (j - s_spill[r]);
+      if (pos < s.n_packets) wire_stamp(spill, (size_t)pos, s);
+    }
+  }
+}
+
 // ---- append ------------------------------------------------------------------
 // Pass 1: records per row, in LDS first, one global add per (block, row).
 template <class S>
@@ -318,6 +462,11 @@ __device__ bool wire_alloc(const WireDev& w, uint32_t* s_nfree, uint32_t* s_off,
 
 __global__ void __launch_bounds__(1024) k_wire_alloc(WireDev w) {
   __shared__ uint32_t s_off[WR_ROWS + 1], s_first[WR_ROWS], s_w[17], s_nfree;
+  // With `bad` set the batch is left out whole, and its counts stay in add[]: harmless only because
+  // err is sticky and every append kernel returns on it until k_wire_reset (sg_wire_set_state)
+  // clears add[] too.  A way to clear err without a reset would have to clear add[] as well.
+  if (threadIdx.x == 0 && w.ctl->bad) w.ctl->err |= WE_BADDST;
+  __syncthreads();
   if (w.ctl->err) return;
   if (threadIdx.x == 0) s_nfree = w.ctl->nfree;
   __syncthreads();
@@ -683,6 +832,7 @@ __global__ void __launch_bounds__(1024) k_wire_final(WireDev w, WirePlan* pl, Wi
     ret->held = w.ctl->held;
     ret->pushed = w.ctl->pushed;
     w.ctl->pushed = 0;
+    ret->err = w.ctl->err;
     ret->compact_row = ~0u;
     const uint32_t e = pl->n_ring - 1;
     if (v == WV_OK && !w.ctl->err && pl->ent_kind[e] == 1) {
@@ -909,7 +1059,7 @@ struct sg_wire {
   uint64_t capacity = 0, count = 0;
   sg::WireDev d = {};
   sg::WirePlan* plan = nullptr;
-  uint32_t* hbuf = nullptr;  // hcnt [n_hosts + 1], hcur [n_hosts], hoff [n_hosts + 1]
+  uint32_t* hbuf = nullptr;  // hcnt [n_hosts + 1], hcur [n_hosts], hoff [n_hosts + 1], valid [WR_MAX_RANKS]
   sg::WireRet* ret = nullptr;
   ~sg_wire() {
     void* ps[] = {d.ctl, d.cnt, d.rmin, d.tbl, d.freel, d.arena, plan, hbuf};
@@ -983,7 +1133,7 @@ int32_t sg_wire_create(sg_ctx* ctx, uint32_t n_hosts, uint64_t capacity, uint64_
     SG_HIP(hipMalloc(&d.freel, M * 4));
     SG_HIP(hipMalloc(&d.arena, M * WR_CHUNK * 32));
     SG_HIP(hipMalloc(&w->plan, sizeof(WirePlan)));
-    SG_HIP(hipMalloc(&w->hbuf, (3 * (size_t)n_hosts + 2) * 4));
+    SG_HIP(hipMalloc(&w->hbuf, (3 * (size_t)n_hosts + 2 + WR_MAX_RANKS) * 4));
     SG_HIP(hipHostMalloc(&w->ret, sizeof(WireRet), hipHostMallocMapped | hipHostMallocCoherent));
     wire_reset(ctx, w);
     SG_HIP(hipStreamSynchronize(ctx->stream));
@@ -1032,6 +1182,83 @@ int32_t sg_wire_push(sg_ctx* ctx, sg_wire* w, const sg_packets* packets, const s
   });
 }
 
+int32_t sg_wire_stamp_records(sg_ctx* ctx, sg_record* send, uint32_t n_records, const uint32_t* packet_id,
+                              uint32_t id_base, const uint32_t* len, uint32_t n_packets) {
+  if (!len || (n_records && !send)) return SG_ERR_INVALID_ARG;
+  return sg::guarded(ctx, [&] {
+    using namespace sg;
+    if (!n_records) return;
+    TimedLaunch tl(ctx, "wire_stamp", 32.0 * n_records);
+    hipLaunchKernelGGL(k_wire_stamp<0>, dim3(grid_for(n_records, WR_THREADS, (unsigned)ctx->n_cu * 8)),
+                       dim3(WR_THREADS), 0, ctx->stream, (uint32_t*)send, (uint32_t*)nullptr, n_records, 0u, 0u,
+                       (const unsigned long long*)nullptr, WireStamp{packet_id, len, id_base, n_packets});
+    SG_CHECK_LAUNCH();
+  });
+}
+
+int32_t sg_wire_stamp_records_padded(sg_ctx* ctx, sg_record* send_padded, sg_record* send, uint32_t n_ranks,
+                                     uint32_t cap, const uint64_t* xrow, const uint32_t* packet_id, uint32_t id_base,
+                                     const uint32_t* len, uint32_t n_packets) {
+  if (!send_padded || !send || !xrow || !len) return SG_ERR_INVALID_ARG;
+  return sg::guarded(ctx, [&] {
+    using namespace sg;
+    if (n_ranks == 0 || n_ranks > WR_MAX_RANKS || cap == 0 || (uint64_t)n_ranks * cap > 0xFFFFFFFFull)
+      throw Error(SG_ERR_INVALID_ARG, "bad n_ranks / cap");
+    // the counts are on the device: the grid covers the blocks and, at most, a spilled record per packet
+    const size_t most = (size_t)n_ranks * cap + n_packets;
+    TimedLaunch tl(ctx, "wire_stamp", 32.0 * n_ranks * cap);  // (the slots scanned)
+    hipLaunchKernelGGL(k_wire_stamp<1>, dim3(grid_for(most, WR_THREADS, (unsigned)ctx->n_cu * 8)), dim3(WR_THREADS), 0,
+                       ctx->stream, (uint32_t*)send_padded, (uint32_t*)send, 0u, n_ranks, cap,
+                       (const unsigned long long*)xrow, WireStamp{packet_id, len, id_base, n_packets});
+    SG_CHECK_LAUNCH();
+  });
+}
+
+int32_t sg_wire_push_records(sg_ctx* ctx, sg_wire* w, const sg_record* recv, uint32_t n_records,
+                             const uint32_t* host_map, uint32_t n_hosts) {
+  if (!w || (n_records && !recv)) return SG_ERR_INVALID_ARG;
+  return sg::guarded(ctx, [&] {
+    using namespace sg;
+    if (w->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "the wire belongs to another context");
+    if (!n_records) return;
+    if (w->count + n_records > w->capacity)
+      throw Error(SG_ERR_CAPACITY, "sg_wire_push_records: count + n_records exceeds the wire's capacity");
+    SrcRecords s{(const uint4*)recv, host_map, &w->d.ctl->bad, n_records, n_hosts, w->n_hosts};
+    {
+      TimedLaunch tl(ctx, "wire_push", 0.0);  // the work (events x 32 B) is known at the next pop
+      wire_append_launch(ctx, w, s, n_records);
+    }
+    w->count += n_records;
+  });
+}
+
+int32_t sg_wire_push_records_padded(sg_ctx* ctx, sg_wire* w, const sg_record* recv_padded, uint32_t n_ranks,
+                                    uint32_t cap, const uint64_t* xall, uint32_t rank, const uint32_t* host_map,
+                                    uint32_t n_hosts) {
+  if (!w || !recv_padded || !xall) return SG_ERR_INVALID_ARG;
+  return sg::guarded(ctx, [&] {
+    using namespace sg;
+    if (w->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "the wire belongs to another context");
+    if (n_ranks == 0 || n_ranks > WR_MAX_RANKS || rank >= n_ranks || cap == 0 ||
+        (uint64_t)n_ranks * cap > 0xFFFFFFFFull)
+      throw Error(SG_ERR_INVALID_ARG, "bad n_ranks / rank / cap");
+    const uint32_t n = n_ranks * cap;
+    // the counts stay on the device: every slot counts (conservative, as sg_wire_push's dropped packets)
+    if (w->count + n > w->capacity)
+      throw Error(SG_ERR_CAPACITY, "sg_wire_push_records_padded: count + n_ranks x cap exceeds the wire's capacity");
+    uint32_t* valid = w->hbuf + 3 * (size_t)w->n_hosts + 2;
+    SrcPaddedRecords s{SrcRecords{(const uint4*)recv_padded, host_map, &w->d.ctl->bad, n, n_hosts, w->n_hosts}, valid,
+                       cap};
+    {
+      TimedLaunch tl(ctx, "wire_push", 0.0);
+      hipLaunchKernelGGL(k_wire_padded_valid, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)xall,
+                         n_ranks, rank, cap, valid);
+      wire_append_launch(ctx, w, s, n);
+    }
+    w->count += n;
+  });
+}
+
 int32_t sg_wire_pop(sg_ctx* ctx, sg_wire* w, uint64_t window_end_ns, sg_wire_arrivals* out, uint32_t* n_out,
                     uint64_t* next_time_ns) {
   if (!w || !out || !n_out) return SG_ERR_INVALID_ARG;
@@ -1074,8 +1301,11 @@ int32_t sg_wire_pop(sg_ctx* ctx, sg_wire* w, uint64_t window_end_ns, sg_wire_arr
     }
     SG_HIP(hipStreamSynchronize(st));
     const volatile WireRet* r = w->ret;
-    const uint32_t v = r->verdict, due = r->due;
+    const uint32_t v = r->verdict, due = r->due, err = r->err;
     timer_add_work(ctx, "wire_push", 32.0 * (double)r->pushed);
+    if (v == WV_ERR && (err & WE_BADDST))
+      throw Error(SG_ERR_INVALID_ARG, "sg_wire_push_records: a record's dst_host is outside host_map (n_hosts), or "
+                                      "maps to no host of this wire; the store is incomplete");
     if (v == WV_ERR) throw Error(SG_ERR_CAPACITY, "sg_wire: an earlier push found the arena without room; "
                                                   "the store is incomplete (raise capacity or n_bins)");
     w->count = r->held;
@@ -1105,6 +1335,10 @@ int32_t sg_wire_pop(sg_ctx* ctx, sg_wire* w, uint64_t window_end_ns, sg_wire_arr
       hipLaunchKernelGGL(k_wire_compact_finish, dim3(1), dim3(1024), 0, st, w->d, row, c, keep, ws, h_max);
       SG_CHECK_LAUNCH();
     }
+    // The sharded round's synchronisation is this one: a padded source phase's batch errors
+    // (sg_deliver_source_padded reads nothing back) are reported here, as sg_deliver_bucket_padded
+    // reports them on the path without a wire.  The pop itself is complete: *n_out and out hold.
+    report_round_flags(ctx);
   });
 }
 
@@ -1120,6 +1354,9 @@ int32_t sg_wire_get_state(sg_wire* w, uint64_t cap, sg_wire_state* out, uint64_t
     SG_HIP(hipMemcpyAsync(&ctl, d.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
     SG_HIP(hipMemcpyAsync(cnt.data(), d.cnt, (size_t)d.R * 4, hipMemcpyDeviceToHost, st));
     SG_HIP(hipStreamSynchronize(st));
+    if (ctl.err & WE_BADDST)
+      throw Error(SG_ERR_INVALID_ARG, "sg_wire_push_records: a record's dst_host is outside host_map (n_hosts), or "
+                                      "maps to no host of this wire; the store is incomplete");
     if (ctl.err) throw Error(SG_ERR_CAPACITY, "sg_wire: an earlier push found the arena without room");
     w->count = ctl.held;
     *n = ctl.held;

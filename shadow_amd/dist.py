@@ -24,6 +24,11 @@ all-to-all move them, and the bucketing reads the valid records of each block
 (sg_deliver_bucket_padded), which synchronises once.  cap follows the largest
 pair count of the round before (all ranks see the same gathered rows, so they
 agree on it); a round whose counts outgrow it is exchanged again exactly.
+With a wire.PacketWire given to ShardedDelivery.round the destination phase is the
+wire's: the source rank stamps len and the packet id into its records
+(sg_wire_stamp_records[_padded]), the exchange moves them as it moves records, and
+the owner pushes them (sg_wire_push_records[_padded]) instead of bucketing; no
+record is copied to the host.
 The phases are injectable so the exchange logic is testable on CPU (gloo).
 """
 from __future__ import annotations
@@ -42,6 +47,11 @@ NONE = 0xFFFFFFFF
 RECORD_DTYPE = np.dtype([("deliver_time_ns", "<u8"), ("order_key", "<u8"), ("event_id", "<u8"),
                          ("packet", "<u4"), ("dst_host", "<u4")])
 assert RECORD_DTYPE.itemsize == 32
+# The same 32 bytes after wire.stamp_records[_padded] (sg_wire_record): len in place of the low
+# half of order_key, the caller's packet id in place of `packet`.  What PacketWire.push_records reads.
+WIRE_RECORD_DTYPE = np.dtype([("deliver_time_ns", "<u8"), ("len", "<u4"), ("src_host", "<u4"), ("event_id", "<u8"),
+                              ("packet_id", "<u4"), ("dst_host", "<u4")])
+assert WIRE_RECORD_DTYPE.itemsize == 32
 
 
 def row_range(n_used: int, world: int, rank: int):
@@ -419,6 +429,9 @@ def _records_all_to_all(send, send_counts: List[int], recv_counts: List[int], di
     n_recv = sum(recv_counts)
     recv = (ws or Workspace()).get("x_recv", max(n_recv, 1), torch.int64, dev, cols=4)
     n_send = sum(send_counts)
+    if dist is None:  # one rank, no process group: what it sends itself (as exchange_padded)
+        recv[:n_recv].copy_(send[:n_send])
+        return recv[:n_recv]
     if is_comm(dist):
         _comm_in(dist, send)
         dist.alltoallv_records(send, send_counts, recv, recv_counts)
@@ -510,11 +523,37 @@ class ShardedDelivery:
         self.last = None
         self.last_send_counts = None
 
-    def round(self, packets, round_end_ns: int, sim_end_ns: int, bootstrap_end_ns: int = 0):
+    def round(self, packets, round_end_ns: int, sim_end_ns: int, bootstrap_end_ns: int = 0, wire=None, length=None,
+              packet_id=None, id_base: int = 0):
         """One round.  The returned tensors are views of buffers the next round
         overwrites (copy what must outlive it).  In a padded round `recv` holds
         n_ranks blocks of `cap` records and `order` indexes it, and the returned
-        SourceResult's `send` is None (its records are `send_padded`; see SourceResult)."""
+        SourceResult's `send` is None (its records are `send_padded`; see SourceResult).
+
+        With `wire` (a wire.PacketWire over all hosts, or over this rank's n_local hosts) the
+        received records go into the wire instead of being bucketed: `length` (int32 device
+        tensor, PacketRc::len() per packet of `packets`) and `packet_id` (int32 device tensor, or
+        None: id_base + the packet's index) are stamped into the records after the source phase.
+        Returns (source result, recv_counts, last_stats); the records in the source result are
+        stamped (WIRE_RECORD_DTYPE).  The arrivals come out of wire.pop.
+
+        Synchronisation: an exact round synchronises in its source phase and counts exchange, as
+        without a wire.  A padded round copies the gathered [stats, counts] rows (W x (3 + W)
+        words, never a record) to the host to return the counts and stats and to decide on the
+        exact re-exchange: that copy synchronises, besides the pop (the C loop of INTEGRATION
+        section 2.7 reads the rows after the pop instead and synchronises once).  The padded source
+        phase's batch errors (SG_ERR_UNSORTED, ...) are raised by the next wire.pop, not here."""
+        if wire is not None:
+            if length is None:
+                raise ValueError("round(wire=...) needs length")
+            if self.padded and self.cap is not None:
+                return self._round_padded_wire(packets, round_end_ns, sim_end_ns, bootstrap_end_ns, wire, length,
+                                               packet_id, id_base)
+            out = self._round_exact_wire(packets, round_end_ns, sim_end_ns, bootstrap_end_ns, wire, length, packet_id,
+                                         id_base)
+            if self.padded:
+                self.cap = next_cap(self._pair_max)
+            return out
         if self.padded and self.cap is not None:
             return self._round_padded(packets, round_end_ns, sim_end_ns, bootstrap_end_ns)
         out = self._round_exact(packets, round_end_ns, sim_end_ns, bootstrap_end_ns)
@@ -582,3 +621,87 @@ class ShardedDelivery:
         self.last = (recv, order, offsets)  # this rank's destination buckets of the round
         self.last_recv_counts = list(recv_counts)
         return src, recv, recv_counts, order, offsets
+
+    # ---- rounds into a wire (the owner's sg_wire_push_records in place of the bucketing) ----
+    def _wire_map(self, wire):
+        """host_map of the pushes: None for a wire over all hosts, `local` for one over this rank's."""
+        if wire.n == len(self.part.local):
+            return None
+        if wire.n == self.part.n_local(self.rank):
+            return self.local_dev
+        raise ValueError(f"the wire holds {wire.n} hosts: neither all {len(self.part.local)} nor this rank's "
+                         f"{self.part.n_local(self.rank)}")
+
+    def _round_exact_wire(self, packets, round_end_ns, sim_end_ns, bootstrap_end_ns, wire, length, packet_id, id_base):
+        from . import wire as _wire
+
+        host_map = self._wire_map(wire)
+        self.last_mode = "exact"
+        src = self.source_fn(self.ctx, self.hosts, self.table, packets, round_end_ns, sim_end_ns, bootstrap_end_ns,
+                             self.owner_dev, self.world)
+        stats = (int(src.n_delivered), int(src.min_deliver_time_ns), int(src.min_used_latency_ns))
+        self.last_send_counts = list(src.send_counts)
+        _wire.stamp_records(src.send, int(sum(src.send_counts)), length, len(packets), packet_id, id_base, ctx=self.ctx)
+        streams = _streams(self.ctx, src.send)  # the stamp is enqueued on the library's stream only
+        if streams:
+            _stream_wait(streams[1], streams[0])
+        if self.exchange_fn is None:
+            recv, recv_counts, self.last_stats, self._pair_max = exchange_round(
+                src.send, src.send_counts, stats, self.rank, self.dist, self.group, ws=self.ws, want_pair_max=True)
+        else:
+            recv, recv_counts = self.exchange_fn(src.send, src.send_counts)
+            self.last_stats = gather_round_stats(*stats, self.dist, self.group, self.device)
+            self._pair_max = _global_max(max(list(src.send_counts) + list(recv_counts) + [0]), self.dist,
+                                         self.group, self.device)
+        if streams:
+            _stream_wait(streams[0], streams[1])
+        wire.push_records(recv, int(sum(recv_counts)), host_map)
+        self.last = None
+        self.last_recv_counts = list(recv_counts)
+        return src, list(recv_counts), self.last_stats
+
+    def _round_padded_wire(self, packets, round_end_ns, sim_end_ns, bootstrap_end_ns, wire, length, packet_id,
+                           id_base):
+        from . import wire as _wire
+
+        host_map = self._wire_map(wire)
+        cap, W = self.cap, self.world
+        src = self.source_padded_fn(self.ctx, self.hosts, self.table, packets, round_end_ns, sim_end_ns,
+                                    bootstrap_end_ns, self.owner_dev, W, cap)
+        _wire.stamp_records_padded(src.send_padded, src.send, W, cap, src.xrow, length, len(packets), packet_id,
+                                   id_base, ctx=self.ctx)
+        streams = _streams(self.ctx, src.send_padded)
+        if streams:
+            _stream_wait(streams[1], streams[0])
+        recv, xall = exchange_padded(src.send_padded, src.xrow, self.dist, self.group, ws=self.ws)
+        if streams:
+            _stream_wait(streams[0], streams[1])
+        wire.push_records_padded(recv, W, cap, xall, self.rank, host_map)  # nothing if the round overflowed
+        if streams:
+            _stream_wait(streams[1], streams[0])
+        # The gathered [stats, counts] rows, W x (3 + W) words: the only thing this round copies to the
+        # host.  Every rank reads the same rows, so all agree on whether the blocks overflowed.
+        xa = xall.cpu().numpy().view(np.uint64).reshape(W, 3 + W)
+        send_counts = [int(x) for x in xa[self.rank, 3:]]
+        recv_counts = [int(xa[b, 3 + self.rank]) for b in range(W)]
+        pair_max = int(xa[:, 3:].max())
+        self.last_send_counts = send_counts
+        self.last_stats = (int(xa[:, 0].sum()), int(xa[:, 1].min()), int(xa[:, 2].min()))
+        self.cap = next_cap(pair_max)
+        if pair_max > cap:  # the padded push appended nothing: exchange again, exactly, and push that
+            self.last_mode = "padded+exact"
+            send = self.pad_to_compact_fn(self.ctx, src, W)  # stamped throughout: blocks and spill both were
+            if streams:
+                _stream_wait(streams[1], streams[0])
+            recv = _records_all_to_all(send, send_counts, recv_counts, self.dist, self.group, self.ws)
+            if streams:
+                _stream_wait(streams[0], streams[1])
+            wire.push_records(recv, int(sum(recv_counts)), host_map)
+        else:
+            self.last_mode = "padded"
+        res = SourceResult(src.status, src.deliver_time_ns, src.event_id,
+                           src.send if self.last_mode == "padded+exact" else None, send_counts, *self.last_stats,
+                           send_padded=src.send_padded)
+        self.last = None
+        self.last_recv_counts = recv_counts
+        return res, recv_counts, self.last_stats

@@ -6,6 +6,8 @@ Host::execute's pops (src/main/host/host.rs:753-757), restricted to Packet event
 the arrivals of a window grouped by host in EventQueue order (time, src_host,
 event_id; core/work/event.rs:84-155) as device tensors, ready for
 `InboundPipeline.run_ordered`.  Nothing crosses the bus while a packet waits.
+On the sharded path (shadow_amd.dist) the source rank stamps its records (`stamp_records`)
+and the owner rank pushes what it received (`PacketWire.push_records`).
 Every computation is a HIP kernel in libshadow_gpu.so (csrc/sg_wire.hip).
 """
 from __future__ import annotations
@@ -29,6 +31,30 @@ NEVER = 2**64 - 1  # next_time_ns of an empty wire (UINT64_MAX)
 
 _STATE_KEYS = ("host", "src_host", "packet", "len", "time_ns", "event_id")
 _STATE_TYPES = (np.uint32, np.uint32, np.uint32, np.uint32, np.uint64, np.uint64)
+
+
+def stamp_records(send, n_records: int, length, n_packets: int, packet_id=None, id_base: int = 0,
+                  ctx: Optional[Context] = None) -> None:
+    """On the source rank, after the source phase: write len and the packet id into the first
+    n_records records of `send` (int64 device tensor [n, 4]), in place: they become
+    dist.WIRE_RECORD_DTYPE records.  length / packet_id: int32 device tensors over the rank's
+    n_packets packets (packet_id None: id_base + the packet's index).  Once per round: stamped
+    records must not be bucketed (sg_deliver_bucket) or stamped again.  Asynchronous."""
+    ctx = ctx or default_context()
+    n = int(n_records)
+    check(ctx.handle, load().sg_wire_stamp_records(
+        ctx.handle, send.data_ptr() if n else None, n, packet_id.data_ptr() if packet_id is not None else None,
+        int(id_base), length.data_ptr(), int(n_packets)))
+
+
+def stamp_records_padded(send_padded, send, n_ranks: int, cap: int, xrow, length, n_packets: int, packet_id=None,
+                         id_base: int = 0, ctx: Optional[Context] = None) -> None:
+    """The same after a padded source phase (dist.SourcePadded's send_padded, send, cap, xrow): the
+    valid slots of every block and the records past cap in `send`, counts read on the device."""
+    ctx = ctx or default_context()
+    check(ctx.handle, load().sg_wire_stamp_records_padded(
+        ctx.handle, send_padded.data_ptr(), send.data_ptr(), int(n_ranks), int(cap), xrow.data_ptr(),
+        packet_id.data_ptr() if packet_id is not None else None, int(id_base), length.data_ptr(), int(n_packets)))
 
 
 class PacketWire:
@@ -59,6 +85,29 @@ class PacketWire:
             self.ctx.handle, self.handle, C.byref(packets.c_struct()), C.byref(out.c_struct()),
             packet_id.data_ptr() if packet_id is not None else None, int(id_base), length.data_ptr()))
 
+    def push_records(self, recv, n_records: int, host_map=None) -> None:
+        """The owner rank's push on the sharded path: one event per stamped record (see
+        stamp_records) of `recv`, an int64 device tensor [n, 4] as the exchange delivers it.
+        host_map: int32 device tensor over all hosts or None; the event's host is
+        host_map[dst_host] (e.g. the partition's `local` for a wire over the rank's own hosts),
+        else dst_host.  A destination outside the map or the wire is reported by the next pop
+        (SG_ERR_INVALID_ARG).  Asynchronous."""
+        n = int(n_records)
+        check(self.ctx.handle, load().sg_wire_push_records(
+            self.ctx.handle, self.handle, recv.data_ptr() if n else None, n,
+            host_map.data_ptr() if host_map is not None else None,
+            int(host_map.numel()) if host_map is not None else self.n))
+
+    def push_records_padded(self, recv_padded, n_ranks: int, cap: int, xall, rank: int, host_map=None) -> None:
+        """The same for the blocks of a fixed-split exchange ([n_ranks * cap, 4]; xall: the gathered
+        [stats, counts] rows, on the device).  Appends nothing when a count in xall exceeds cap:
+        the round is then exchanged again exactly and pushed with push_records.  `count` rises by
+        n_ranks * cap until the next pop.  Asynchronous."""
+        check(self.ctx.handle, load().sg_wire_push_records_padded(
+            self.ctx.handle, self.handle, recv_padded.data_ptr(), int(n_ranks), int(cap), xall.data_ptr(), int(rank),
+            host_map.data_ptr() if host_map is not None else None,
+            int(host_map.numel()) if host_map is not None else self.n))
+
     def _buffers(self, cap: int):
         import torch
 
@@ -75,7 +124,11 @@ class PacketWire:
         packet, len, src_host, event_id), device tensors sliced to n (views of buffers the next
         pop reuses), grouped by ascending host, each host's in EventQueue order.  cap: the output
         capacity (default: the events held); with more due, ShadowGpuError(SG_ERR_CAPACITY)
-        whose `needed` is their number, and the wire is unchanged."""
+        whose `needed` is their number, and the wire is unchanged.  After a padded sharded round
+        (ShardedDelivery.round(wire=...)) the pop is the round's synchronisation and also raises
+        that round's source-phase error (e.g. SG_ERR_UNSORTED for a batch not grouped by source
+        host: nothing of it was delivered), once; the pop is then complete all the same, and the
+        exception's `arrivals` holds what it returned."""
         cap = max(int(self.count if cap is None else cap), 0)
         b = self._buffers(max(cap, 1))
         o = _capi.sg_wire_arrivals(cap, *(b[k].data_ptr() for k in ("host", "time_ns", "packet", "len", "src_host",
@@ -83,14 +136,17 @@ class PacketWire:
         n, nxt = C.c_uint32(), C.c_uint64(NEVER)
         rc = load().sg_wire_pop(self.ctx.handle, self.handle, int(window_end_ns), C.byref(o), C.byref(n),
                                 C.byref(nxt))
-        try:
-            check(self.ctx.handle, rc)
-        except _capi.ShadowGpuError as e:
-            e.needed = int(n.value)
-            raise
         k = int(n.value)
         res = dict(n=k, next_time_ns=int(nxt.value))
         res.update({key: b[key][:k] for key in ("host", "time_ns", "packet", "len", "src_host", "event_id")})
+        try:
+            check(self.ctx.handle, rc)
+        except _capi.ShadowGpuError as e:
+            e.needed = k
+            # a source-phase error of the sharded round reported by this pop: the pop itself is
+            # complete, and these are its arrivals (they have left the wire)
+            e.arrivals = res if rc != _capi.SG_ERR_CAPACITY else None
+            raise
         return res
 
     @staticmethod

@@ -13,6 +13,15 @@ condition under test: a round's wire time depends on what it pushes and pops, no
 store holds, so P40M / P10M should be 1 within the spread.
 
     python tools/wire_bench.py --out profiles/wire_bench.json
+
+A fourth leg, not in the default list, compares the two ways into the wire on P10M's volume and
+geometry with W = 1 (every record is local), both in every timed round of one run:
+  P10M_records  old: sg_deliver_round + sg_wire_push
+                new: sg_deliver_source + sg_wire_stamp_records + sg_wire_push_records
+Each path has its own hosts table and wire, fed the same batches (so both hold the same events);
+the wire_push timer is read around each path's push, wire_stamp around the stamp.
+
+    python tools/wire_bench.py --legs P10M_records --out profiles/wire_bench_records.json
 """
 import argparse
 import json
@@ -102,6 +111,87 @@ def leg(name, a, torch, ctx, lat_max_ms, n_bins, capacity):
     return res
 
 
+def leg_records(name, a, torch, ctx, lat_max_ms, n_bins, capacity):
+    """The same rounds through both ways into the wire (see the module docstring)."""
+    from shadow_amd import synth
+    from shadow_amd.dist import HostPartition, ShardedDelivery
+    from shadow_amd.wire import PacketWire, stamp_records
+    from shadow_amd.worker import DeviceTable, Deliveries, HostTable, PacketBatch, deliver_round
+
+    rng = np.random.default_rng(11)
+    hosts = synth.make_hosts(a.hosts, a.nodes, exact_seeds=False)
+    lat = rng.integers(MS, lat_max_ms * MS + 1, (a.nodes, a.nodes)).astype(np.uint64)
+    loss = (rng.random((a.nodes, a.nodes)) * 0.02).astype(np.float32)
+    table = DeviceTable(torch.from_numpy(lat.view(np.int64).ravel()).cuda(), torch.from_numpy(loss.ravel()).cuda(),
+                        a.nodes)
+    table.pack(ctx)
+    ht_old = HostTable(hosts["ip"], hosts["route"], hosts["seed"], ctx=ctx)
+    ht_new = HostTable(hosts["ip"], hosts["route"], hosts["seed"], ctx=ctx)
+    sd = ShardedDelivery(ctx, ht_new, table, HostPartition(hosts["route"], a.nodes, 1), 0, 1)
+    batches = []
+    for s in range(4):
+        pk = synth.make_packets(a.packets, hosts, 0, MS, seed=50 + s)
+        batches.append((PacketBatch.from_numpy(pk["src"], pk["dst_ip"], pk["payload"], pk["send_time"]),
+                        torch.from_numpy(pk["send_time"].view(np.int64)).cuda(),
+                        torch.from_numpy((pk["payload"] + 28).astype(np.uint32).view(np.int32)).cuda()))
+    out = Deliveries.allocate(a.packets, a.hosts)
+    w_old = PacketWire(a.hosts, capacity, MS, n_bins, ctx=ctx)
+    w_new = PacketWire(a.hosts, capacity, MS, n_bins, ctx=ctx)
+    warm = lat_max_ms + 8
+    cap = 2 * a.packets
+    names = ("wire_push", "wire_stamp", "wire_pop")
+    rows = []
+
+    def read():
+        return {n: ctx.read_timer(n)[0] for n in names}
+
+    for k in range(warm + a.rounds):
+        batch, rel, length = batches[k % len(batches)]
+        batch.send_time_ns.copy_(rel + (T0 + k * MS))
+        end = T0 + (k + 1) * MS
+        if k == warm:
+            ctx.enable_timers(True)
+        timed = k >= warm
+        # old: the single-GPU round and its push
+        deliver_round(ht_old, table, batch, end, 2**63, 0, out=out, ctx=ctx)
+        t0 = read() if timed else None
+        w_old.push(batch, out, length, id_base=0)
+        g_old = w_old.pop(end, cap=cap)
+        t1 = read() if timed else None
+        # new: the sharded round's source half, the stamp, the push from records
+        src = sd.source_fn(ctx, ht_new, table, batch, end, 2**63, 0, sd.owner_dev, 1)
+        n_rec = int(sum(src.send_counts))
+        t2 = read() if timed else None
+        stamp_records(src.send, n_rec, length, len(batch), id_base=0, ctx=ctx)
+        w_new.push_records(src.send, n_rec)
+        g_new = w_new.pop(end, cap=cap)
+        t3 = read() if timed else None
+        if g_old["n"] != g_new["n"] or w_old.count != w_new.count or int(out.n_delivered) != n_rec:
+            sys.exit(f"{name}: the two paths disagree in round {k}")
+        if timed:
+            rows.append(dict(round=k, delivered=n_rec, popped=g_new["n"], held=w_new.count,
+                             push_old_ms=t1["wire_push"] - t0["wire_push"], pop_old_ms=t1["wire_pop"] - t0["wire_pop"],
+                             push_new_ms=t3["wire_push"] - t2["wire_push"], stamp_ms=t3["wire_stamp"] - t2["wire_stamp"],
+                             pop_new_ms=t3["wire_pop"] - t2["wire_pop"]))
+    ctx.enable_timers(False)
+    # the last timed pops of both wires hold the same events in the same order
+    same = all(bool(torch.equal(g_old[key], g_new[key])) for key in ("host", "time_ns", "packet", "len", "src_host",
+                                                                      "event_id"))
+    res = dict(name=name, lat_max_ms=lat_max_ms, n_bins=n_bins, bin_ns=MS, capacity=capacity, warmup_rounds=warm,
+               ranks=1, last_pops_equal=same, held=stats([r["held"] for r in rows]),
+               delivered=stats([r["delivered"] for r in rows]),
+               push_old_ms=stats([r["push_old_ms"] for r in rows]), push_new_ms=stats([r["push_new_ms"] for r in rows]),
+               stamp_ms=stats([r["stamp_ms"] for r in rows]), pop_old_ms=stats([r["pop_old_ms"] for r in rows]),
+               pop_new_ms=stats([r["pop_new_ms"] for r in rows]), rounds=rows)
+    res["ratio_push_new_over_old"] = res["push_new_ms"]["mean"] / res["push_old_ms"]["mean"]
+    res["ratio_push_plus_stamp_over_old"] = (res["push_new_ms"]["mean"] + res["stamp_ms"]["mean"]) / \
+        res["push_old_ms"]["mean"]
+    res["regression_bound"] = 1.10  # the push's round-to-round spread is 4 % (DESIGN.md 4e)
+    del w_old, w_new, ht_old, ht_new, table, out, batches, sd
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--hosts", type=int, default=100_000)
@@ -127,7 +217,16 @@ def main():
     res = {"config": dict(hosts=a.hosts, nodes=a.nodes, packets_per_round=a.packets, round_ns=MS,
                           timed_rounds=a.rounds, record_bytes=RECORD_BYTES,
                           device=torch.cuda.get_device_name(0)), "legs": {}}
+    res["config"]["command"] = "python tools/wire_bench.py " + " ".join(sys.argv[1:])
     for name in a.legs.split(","):
+        if name == "P10M_records":
+            r = res["legs"][name] = leg_records(name, a, torch, ctx, *legs["P10M"])
+            print(f"{name}: held {r['held']['mean'] / 1e6:.1f}M  push from deliveries {r['push_old_ms']['mean']:.3f} ms "
+                  f"(sd {r['push_old_ms']['std']:.3f})  push from records {r['push_new_ms']['mean']:.3f} ms (sd "
+                  f"{r['push_new_ms']['std']:.3f})  stamp {r['stamp_ms']['mean']:.3f} ms  ratio "
+                  f"{r['ratio_push_new_over_old']:.3f} (with the stamp {r['ratio_push_plus_stamp_over_old']:.3f})  "
+                  f"pops equal: {r['last_pops_equal']}", flush=True)
+            continue
         res["legs"][name] = leg(name, a, torch, ctx, *legs[name])
         r = res["legs"][name]
         print(f"{name}: held {r['held']['mean'] / 1e6:.1f}M  push {r['push_ms']['mean']:.3f} ms (sd "

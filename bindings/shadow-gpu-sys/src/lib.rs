@@ -54,6 +54,11 @@ pub struct sg_routing_info {
 pub struct sg_comm {
     _private: [u8; 0],
 }
+/// N `sg_ctx` of this one process (the `Manager` owns them all) behind one object.
+#[repr(C)]
+pub struct sg_group {
+    _private: [u8; 0],
+}
 /// Every host's in-flight Packet events (the per-host `EventQueue`, on the device).
 #[repr(C)]
 pub struct sg_wire {
@@ -335,7 +340,7 @@ pub const SG_ERR_DUPLICATE_IP: i32 = 9;
 pub const SG_ERR_CAPACITY: i32 = 10;
 /// EmulatedTime + SimulationTime past EMUTIME_MAX (a panic in the reference, emulated_time.rs:121-126)
 pub const SG_ERR_TIME_OVERFLOW: i32 = 11;
-/// sg_comm_*: RCCL could not be opened
+/// sg_comm_*: RCCL could not be opened; sg_group_create: a pair of devices without peer access
 pub const SG_ERR_UNSUPPORTED: i32 = 12;
 
 pub const SG_TIMERS_ON: u32 = 1;
@@ -548,4 +553,23 @@ unsafe extern "C" {
     pub fn sg_wire_push_records_padded(ctx: *mut sg_ctx, w: *mut sg_wire, recv_padded: *const sg_record,
                                        n_ranks: u32, cap: u32, xall: *const u64, rank: u32, host_map: *const u32,
                                        n_hosts: u32) -> i32;
+
+    // ---- device group: the one Shadow process owns N contexts (manager.rs:254-261) ----
+    /// 1 <= n <= 64 distinct contexts; peer access is enabled between distinct devices.
+    /// The pointer arrays of these calls are only read.
+    pub fn sg_group_create(ctxs: *mut *mut sg_ctx, n: u32, out: *mut *mut sg_group) -> i32;
+    pub fn sg_group_destroy(g: *mut sg_group);
+    pub fn sg_group_size(g: *const sg_group) -> u32;
+    pub fn sg_group_last_error(g: *const sg_group) -> *const c_char;
+    pub fn sg_group_last_error_pair(g: *const sg_group, row: *mut u32, col: *mut u32);
+    /// One host RoutingInfo from all members: member m builds and copies its block of rows.
+    pub fn sg_group_routing_info_fill(g: *mut sg_group, nets: *mut *mut sg_net, nodes: *const u32, flags: u32,
+                                      ri: *mut sg_routing_info) -> i32;
+    /// The fixed-split round's exchange for all members: one pull kernel per owner, no RCCL.
+    pub fn sg_group_exchange_padded(g: *mut sg_group, send_padded: *mut *const sg_record,
+                                    recv_padded: *mut *mut sg_record, cap: u32, xrow: *mut *const u64,
+                                    xall: *mut *mut u64) -> i32;
+    /// The exact exchange: counts is the host n x n matrix (member b's records for member r).
+    pub fn sg_group_alltoallv_records(g: *mut sg_group, send: *mut *const sg_record, counts: *const u32,
+                                      recv: *mut *mut sg_record) -> i32;
 }

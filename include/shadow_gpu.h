@@ -50,7 +50,8 @@ typedef enum sg_status {
   SG_ERR_UNSORTED = 8,      /* sg_deliver_round: packets not grouped by ascending source host */
   SG_ERR_DUPLICATE_IP = 9,  /* two hosts with one address (IpAssignment::assign_ip, graph/mod.rs:383-394) */
   SG_ERR_CAPACITY = 10,     /* a CoDel queue outgrew its ring (sg_codel_create ring_cap) */
-  SG_ERR_UNSUPPORTED = 12,  /* sg_comm_*: RCCL (librccl.so.1) could not be opened (ABI 7) */
+  SG_ERR_UNSUPPORTED = 12,  /* sg_comm_*: RCCL (librccl.so.1) could not be opened (ABI 7);
+                               sg_group_create: a pair of devices without peer access */
   SG_ERR_TIME_OVERFLOW = 11 /* send time + latency past EMUTIME_MAX: EmulatedTime + SimulationTime
                                panics in the reference (emulated_time.rs:121-126, worker.rs:381) */
 } sg_status;
@@ -820,6 +821,61 @@ int32_t sg_wire_push_records(sg_ctx* ctx, sg_wire* w, const sg_record* recv, uin
 int32_t sg_wire_push_records_padded(sg_ctx* ctx, sg_wire* w, const sg_record* recv_padded, uint32_t n_ranks,
                                     uint32_t cap, const uint64_t* xall, uint32_t rank, const uint32_t* host_map,
                                     uint32_t n_hosts);
+
+/* ---- device group: one process, N contexts (additive to ABI 7) --------------
+ * Shadow is one process: Manager::run spawns worker threads (manager.rs:254-261) and
+ * a packet crosses hosts through an in-process push (worker.rs:597-607).  A group
+ * binds N contexts of that one process, usually one per GPU, so the sharded paths
+ * above need neither one process per GPU nor RCCL: "member m" (the m-th context
+ * given) plays the part "rank m" plays there.  Calls on one group are not
+ * thread-safe, and no other call may run on a member's context meanwhile.
+ *
+ * create: 1 <= n <= 64 distinct contexts (64: the per-rank receive counts of a padded
+ * round); devices may repeat (all members on device 0 is legal).  For every pair of
+ * distinct devices peer access is checked and enabled: SG_ERR_UNSUPPORTED, naming the
+ * pair, if the platform refuses.  SG_ERR_INVALID_ARG for NULL, n == 0, n > 64, a NULL
+ * or repeated context.  The contexts must outlive the group.  The arrays of pointers
+ * these calls take are only read.
+ * last_error[_pair]: message and (row, col) of the group's last failing call, as the
+ * context's; with NULL, the reason the last create on this thread failed. */
+typedef struct sg_group sg_group;
+int32_t sg_group_create(sg_ctx** ctxs, uint32_t n, sg_group** out);
+void sg_group_destroy(sg_group* g);
+uint32_t sg_group_size(const sg_group* g);
+const char* sg_group_last_error(const sg_group* g);
+void sg_group_last_error_pair(const sg_group* g, uint32_t* row, uint32_t* col);
+
+/* One host RoutingInfo from all members at once: nets[m] is the same graph created
+ * on member m.  With per = ceil(ri->n / n), member m builds rows [min(m per, ri->n),
+ * min((m + 1) per, ri->n)) and copies them into ri's pinned cells, each member on a
+ * host thread of its own, in blocks of half its rows (whole 64-row batches); a
+ * member whose range is empty does nothing.  ri ends exactly as after the single
+ * fill of one context, and so do the errors: the self-loop check runs first (on member 0), and of
+ * the members' search errors the one at the smallest (row, col) is reported.  After
+ * a failure ri is not filled, and no copy still writes into it.
+ * SG_ERR_INVALID_ARG when nets[m] was not created on member m or the graphs differ in
+ * node count, edge count or directedness. */
+int32_t sg_group_routing_info_fill(sg_group* g, sg_net** nets, const uint32_t* nodes, uint32_t flags,
+                                   sg_routing_info* ri);
+
+/* Step 2 of the fixed-split round ("sharded delivery with a fixed-split exchange"
+ * above) for all members in one call.  Arrays of n device pointers, entry m on member
+ * m's device.  Afterwards, for every owner r and source b:
+ *   xall[r] = xrow[0] | xrow[1] | ... | xrow[n-1]            (n x (3 + n) u64)
+ *   recv_padded[r][b*cap + k] = send_padded[b][r*cap + k]    for k < min(xrow[b][3 + r], cap)
+ * Slots past that count in recv_padded are left as they were.  Each owner pulls its
+ * blocks with one kernel on its own stream; no count leaves the device.  Ordering is
+ * by events: every owner's pull waits for what every member had enqueued on its stream
+ * before the call, and what the caller enqueues on any member's stream after the call
+ * waits for every pull (so the next round may overwrite send_padded at once).
+ * Stamped records move as plain ones.  Does not synchronise. */
+int32_t sg_group_exchange_padded(sg_group* g, const sg_record** send_padded, sg_record** recv_padded, uint32_t cap,
+                                 const uint64_t** xrow, uint64_t** xall);
+/* The exact exchange (the contract of sg_comm_alltoallv_records): counts is a host
+ * n x n array, counts[b*n + r] = records member b holds for member r, grouped by r in
+ * send[b]; recv[r] receives them source after source.  Device copies behind the same
+ * event ordering.  Does not synchronise. */
+int32_t sg_group_alltoallv_records(sg_group* g, const sg_record** send, const uint32_t* counts, sg_record** recv);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,8 @@ from ._capi import LIB_PATH, ShadowGpuError, ShadowGpuUnavailable, load  # noqa:
 from .graph import (Context, IpAssignment, NetworkGraph, PathProperties, PathTable,  # noqa: F401
                     RoutingInfo, default_context, generate_routing_info, ipv4_to_u32, u32_to_ipv4)
 from .wire import PacketWire  # noqa: F401
+from .group import Group, GroupDelivery  # noqa: F401
 
 __all__ = ["Context", "NetworkGraph", "PathProperties", "PathTable", "RoutingInfo", "IpAssignment",
            "generate_routing_info", "default_context", "load", "ShadowGpuError", "ShadowGpuUnavailable",
-           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire"]
+           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire", "Group", "GroupDelivery"]

@@ -55,6 +55,8 @@ EXPORTED = [
     "sg_wire_create", "sg_wire_destroy", "sg_wire_count", "sg_wire_push", "sg_wire_pop", "sg_wire_get_state",
     "sg_wire_set_state", "sg_wire_stamp_records", "sg_wire_stamp_records_padded", "sg_wire_push_records",
     "sg_wire_push_records_padded",
+    "sg_group_create", "sg_group_destroy", "sg_group_size", "sg_group_last_error", "sg_group_last_error_pair",
+    "sg_group_routing_info_fill", "sg_group_exchange_padded", "sg_group_alltoallv_records",
 ]
 
 
@@ -282,6 +284,14 @@ def load(path: str | None = None):
         "sg_wire_stamp_records_padded": (i32, [vp, vp, vp, u32, u32, vp, vp, u32, vp, u32]),
         "sg_wire_push_records": (i32, [vp, vp, vp, u32, vp, u32]),
         "sg_wire_push_records_padded": (i32, [vp, vp, vp, u32, u32, vp, u32, vp, u32]),
+        "sg_group_create": (i32, [vp, u32, C.POINTER(vp)]),
+        "sg_group_destroy": (None, [vp]),
+        "sg_group_size": (u32, [vp]),
+        "sg_group_last_error": (C.c_char_p, [vp]),
+        "sg_group_last_error_pair": (None, [vp, u32p, u32p]),
+        "sg_group_routing_info_fill": (i32, [vp, vp, vp, u32, vp]),
+        "sg_group_exchange_padded": (i32, [vp, vp, vp, u32, vp, vp]),
+        "sg_group_alltoallv_records": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

@@ -263,6 +263,19 @@ int32_t guarded(sg_ctx* ctx, F&& fn) {
   }
 }
 
+// sg_routing.hip: the host RoutingInfo fill over a row range of one context (what
+// sg_routing_info_fill runs over every row and sg_group_routing_info_fill, sg_group.hip, over
+// one range per member), the used-node list's check, and the object's state around a fill.
+struct FillRows {
+  uint64_t min_lat = UINT64_MAX;
+  std::vector<sg_routing_info::Wide> wide;  // unsorted
+};
+void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used);
+void fill_rows(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t flags, sg_routing_info* ri, uint32_t r0,
+               uint32_t r1, uint32_t block_rows, bool self_check, FillRows* out);
+void fill_reset(sg_routing_info* ri);
+void fill_finish(sg_routing_info* ri, uint64_t min_lat, std::vector<sg_routing_info::Wide>&& wide);
+
 // Region bucketing counters per parity: 8 sub-counters (one per XCD) x SB_MAX
 // (4096) super-buckets + an overflow flag.
 constexpr uint32_t SB_SUB = 8;

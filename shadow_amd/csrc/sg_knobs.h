@@ -69,7 +69,7 @@
 //   SG_NET_THREADS | 4 | 1 .. 4 | test | graph upload: host threads staging a large edge list
 //   SG_NET_LDS | 1 | 0, 1 | tune | graph upload: 0 counts and places arcs with global atomics at any size
 //   SG_NET_TRACE | 0 | 0, 1 | diag | graph upload: host phases on stderr
-//   SG_RI_BLOCK_ROWS | n_used / 8 | >= 64, whole 64-row batches | test | RoutingInfo fill: rows per block
+//   SG_RI_BLOCK_ROWS | n_used / 8; a group member: half its rows | >= 64, whole 64-row batches | test | RoutingInfo fill: rows per block
 //   SG_GML_THREADS | min(hardware threads, 16) | >= 1 | tune | GML parser: threads
 #pragma once
 

@@ -655,12 +655,10 @@ static void direct_paths(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, const
 
 }  // namespace sg
 
-extern "C" {
-
 namespace sg {
 // The used-node list: every index in range, none twice.  One branch-free pass; only a bad
 // list is walked again, entry by entry, for the first bad entry's error.
-static void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used) {
+void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used) {
   const uint32_t n = net->n_nodes;
   std::vector<uint8_t> seen((size_t)n + 1, 0);  // the spare last byte takes out-of-range ids
   uint32_t bad = 0;
@@ -679,6 +677,8 @@ static void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n
   }
 }
 }  // namespace sg
+
+extern "C" {
 
 int32_t sg_routing_build(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_used,
                          uint32_t row_begin, uint32_t row_end, uint32_t flags,
@@ -744,10 +744,131 @@ int32_t sg_routing_build(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32
   });
 }
 
-// The whole table into a host RoutingInfo (sg_route_info.hip): row blocks are
-// built into one of two device staging buffers, packed into 8-byte cells and
-// copied to the object's pinned host array on a second stream while the next
-// block builds.  The copy (8 bytes per cell over PCIe) is what binds.
+}  // extern "C"
+
+namespace sg {
+// Rows [r0, r1) of the table into a host RoutingInfo's cells (sg_route_info.hip), on one
+// context: row blocks are built into one of two device staging buffers, packed into 8-byte
+// cells and copied to the object's pinned host array on a second stream while the next block
+// builds.  The copy (8 bytes per cell over PCIe) is what binds.  The rows' smallest latency
+// and their wide cells (unsorted) go to `out`, not into the object: sg_routing_info_fill runs
+// this over [0, n), sg_group_routing_info_fill (sg_group.hip) over one row range per member,
+// each on a thread of its own, and merges.  block_rows: the block size where
+// SG_RI_BLOCK_ROWS is unset.  self_check: the self-loop check of every used node
+// (graph/mod.rs:210-217) ahead of the first block.  copy_stream is synchronised on every
+// path: no copy still writes into the object once this returns or throws.
+void fill_rows(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t flags, sg_routing_info* ri, uint32_t r0,
+               uint32_t r1, uint32_t block_rows, bool self_check, FillRows* out) {
+  const uint32_t n_used = ri->n;
+  out->min_lat = UINT64_MAX;
+  out->wide.clear();
+  hipStream_t st = ctx->stream;
+  if (!ctx->copy_stream) {
+    SG_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; b++) {
+      SG_HIP(hipEventCreateWithFlags(&ctx->stage_done[b], hipEventDisableTiming));
+      SG_HIP(hipEventCreateWithFlags(&ctx->stage_copied[b], hipEventDisableTiming));
+    }
+  }
+  // an earlier fill that failed may have left copies in flight into its staging buffers
+  SG_HIP(hipStreamSynchronize(ctx->copy_stream));
+  uint32_t* d_used = ctx->r_used.get<uint32_t>(n_used);
+  {
+    char* hu = stage_acquire(ctx, 1, (size_t)n_used * 4);
+    memcpy(hu, nodes, (size_t)n_used * 4);
+    SG_HIP(hipMemcpyAsync(d_used, hu, (size_t)n_used * 4, hipMemcpyHostToDevice, st));
+    stage_release(ctx, 1);
+  }
+  const bool shortest = flags & SG_ROUTE_SHORTEST_PATH;
+  if (shortest && self_check) raise_self_loops(ctx, net, launch_self_loops(ctx, net, d_used, n_used), nodes);
+  if (r1 <= r0) return;
+  // at least 64 rows, whole 64-row batches
+  uint32_t rows = (uint32_t)std::max(64, knob_int("SG_RI_BLOCK_ROWS", (int)block_rows));
+  rows = std::min(r1 - r0, (rows + 63) / 64 * 64);
+  uint64_t* slat[2];
+  float* sloss[2];
+  uint64_t* spack[2];
+  for (int b = 0; b < 2; b++) {
+    slat[b] = ctx->r_stage_lat[b].get<uint64_t>((size_t)rows * n_used);
+    sloss[b] = ctx->r_stage_loss[b].get<float>((size_t)rows * n_used);
+    spack[b] = ctx->r_stage_pack[b].get<uint64_t>((size_t)rows * n_used);
+  }
+  const unsigned nbp = grid_for((size_t)rows * n_used / 2, 256, 4096);
+  uint64_t m = UINT64_MAX;
+  int k = 0;
+  try {
+    for (uint32_t b0 = r0; b0 < r1; b0 += rows, k++) {
+      const uint32_t b1 = std::min(r1, b0 + rows), b = k & 1;
+      ctx->in_fill = true;
+      try {
+        if (shortest)
+          shortest_paths(ctx, net, d_used, nodes, n_used, b0, b1, slat[b], sloss[b]);
+        else
+          direct_paths(ctx, net, d_used, nodes, n_used, b0, b1, slat[b], sloss[b]);
+      } catch (...) {
+        ctx->in_fill = false;
+        throw;
+      }
+      ctx->in_fill = false;
+      const size_t cells = (size_t)(b1 - b0) * n_used;
+      // (workspace fetched after the build, which may grow these buffers)
+      unsigned long long* ctl = ctx->r_err.get<unsigned long long>(4);
+      SG_HIP(hipMemsetAsync(ctl, 0xff, 8, st));
+      SG_HIP(hipMemsetAsync(ctl + 1, 0, 8, st));
+      if (k >= 2) SG_HIP(hipStreamWaitEvent(st, ctx->stage_copied[b], 0));  // block k - 2 left spack[b]
+      hipLaunchKernelGGL(k_pack_cells, dim3(nbp), dim3(256), 0, st, slat[b], sloss[b], cells, spack[b], ctl);
+      SG_CHECK_LAUNCH();
+      SG_HIP(hipEventRecord(ctx->stage_done[b], st));
+      SG_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_done[b], 0));
+      SG_HIP(hipMemcpyAsync(ri->cell + (size_t)b0 * n_used, spack[b], cells * 8, hipMemcpyDeviceToHost,
+                            ctx->copy_stream));
+      SG_HIP(hipEventRecord(ctx->stage_copied[b], ctx->copy_stream));
+      unsigned long long h[2] = {0, 0};
+      copy_to_host(ctx, h, ctl, 16);  // (the next block's build starts after this sync; the copy runs on)
+      m = std::min<uint64_t>(m, h[0]);
+      if (h[1]) {  // paths of 4.29 s or more: their u64 latencies to the side table
+        uint64_t* list = ctx->r_misc.get<uint64_t>(2 * h[1]);
+        SG_HIP(hipMemsetAsync(ctl + 1, 0, 8, st));
+        hipLaunchKernelGGL(k_wide_list, dim3(grid_for(cells, 256, 4096)), dim3(256), 0, st, slat[b], cells,
+                           (uint64_t)b0 * n_used, ctl + 1, list);
+        SG_CHECK_LAUNCH();
+        std::vector<uint64_t> hl(2 * h[1]);
+        copy_to_host(ctx, hl.data(), list, hl.size() * 8);
+        for (size_t i = 0; i < h[1]; i++) out->wide.push_back({hl[2 * i], hl[2 * i + 1]});
+      }
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx->copy_stream);  // no copy may still run into the object
+    throw;
+  }
+  SG_HIP(hipStreamSynchronize(ctx->copy_stream));
+  out->min_lat = m;
+}
+
+// A fill's start: the object as after sg_routing_info_create (not filled, no row set).
+void fill_reset(sg_routing_info* ri) {
+  ri->filled = false;
+  ri->min_lat = UINT64_MAX;
+  ri->wide.clear();
+  std::fill(ri->row_set.begin(), ri->row_set.end(), 0);
+  ri->rows_set = 0;
+}
+
+// A fill's end: every row written, the wide cells sorted by cell.
+void fill_finish(sg_routing_info* ri, uint64_t min_lat, std::vector<sg_routing_info::Wide>&& wide) {
+  ri->wide = std::move(wide);
+  std::sort(ri->wide.begin(), ri->wide.end(),
+            [](const sg_routing_info::Wide& x, const sg_routing_info::Wide& y) { return x.cell < y.cell; });
+  std::fill(ri->row_set.begin(), ri->row_set.end(), 2);  // written; per-row minima not kept
+  ri->rows_set = ri->n;
+  ri->min_lat = min_lat;
+  ri->filled = true;
+}
+}  // namespace sg
+
+extern "C" {
+
+// The whole table into a host RoutingInfo: fill_rows over every row.
 int32_t sg_routing_info_fill(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t flags, sg_routing_info* ri) {
   return sg::guarded(ctx, [&] {
     using namespace sg;
@@ -756,100 +877,14 @@ int32_t sg_routing_info_fill(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, ui
     const uint32_t n_used = ri->n;
     if (n_used && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
     check_node_list(net, nodes, n_used);
-    ri->filled = false;
-    ri->min_lat = UINT64_MAX;
-    ri->wide.clear();
-    std::fill(ri->row_set.begin(), ri->row_set.end(), 0);
-    ri->rows_set = 0;
+    fill_reset(ri);
     if (n_used == 0) {
       ri->filled = true;
       return;
     }
-    hipStream_t st = ctx->stream;
-    if (!ctx->copy_stream) {
-      SG_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-      for (int b = 0; b < 2; b++) {
-        SG_HIP(hipEventCreateWithFlags(&ctx->stage_done[b], hipEventDisableTiming));
-        SG_HIP(hipEventCreateWithFlags(&ctx->stage_copied[b], hipEventDisableTiming));
-      }
-    }
-    // an earlier fill that failed may have left copies in flight into its staging buffers
-    SG_HIP(hipStreamSynchronize(ctx->copy_stream));
-    uint32_t* d_used = ctx->r_used.get<uint32_t>(n_used);
-    {
-      char* hu = stage_acquire(ctx, 1, (size_t)n_used * 4);
-      memcpy(hu, nodes, (size_t)n_used * 4);
-      SG_HIP(hipMemcpyAsync(d_used, hu, (size_t)n_used * 4, hipMemcpyHostToDevice, st));
-      stage_release(ctx, 1);
-    }
-    const bool shortest = flags & SG_ROUTE_SHORTEST_PATH;
-    if (shortest) raise_self_loops(ctx, net, launch_self_loops(ctx, net, d_used, n_used), nodes);
-    // blocks of about 1/8 of the table (at least 64 rows, whole 64-row batches)
-    uint32_t rows = (uint32_t)std::max(64, knob_int("SG_RI_BLOCK_ROWS", (int)((n_used + 7) / 8)));
-    rows = std::min(n_used, (rows + 63) / 64 * 64);
-    uint64_t* slat[2];
-    float* sloss[2];
-    uint64_t* spack[2];
-    for (int b = 0; b < 2; b++) {
-      slat[b] = ctx->r_stage_lat[b].get<uint64_t>((size_t)rows * n_used);
-      sloss[b] = ctx->r_stage_loss[b].get<float>((size_t)rows * n_used);
-      spack[b] = ctx->r_stage_pack[b].get<uint64_t>((size_t)rows * n_used);
-    }
-    const unsigned nbp = grid_for((size_t)rows * n_used / 2, 256, 4096);
-    uint64_t m = UINT64_MAX;
-    int k = 0;
-    try {
-      for (uint32_t r0 = 0; r0 < n_used; r0 += rows, k++) {
-        const uint32_t r1 = std::min(n_used, r0 + rows), b = k & 1;
-        ctx->in_fill = true;
-        try {
-          if (shortest)
-            shortest_paths(ctx, net, d_used, nodes, n_used, r0, r1, slat[b], sloss[b]);
-          else
-            direct_paths(ctx, net, d_used, nodes, n_used, r0, r1, slat[b], sloss[b]);
-        } catch (...) {
-          ctx->in_fill = false;
-          throw;
-        }
-        ctx->in_fill = false;
-        const size_t cells = (size_t)(r1 - r0) * n_used;
-        // (workspace fetched after the build, which may grow these buffers)
-        unsigned long long* ctl = ctx->r_err.get<unsigned long long>(4);
-        SG_HIP(hipMemsetAsync(ctl, 0xff, 8, st));
-        SG_HIP(hipMemsetAsync(ctl + 1, 0, 8, st));
-        if (k >= 2) SG_HIP(hipStreamWaitEvent(st, ctx->stage_copied[b], 0));  // block k - 2 left spack[b]
-        hipLaunchKernelGGL(k_pack_cells, dim3(nbp), dim3(256), 0, st, slat[b], sloss[b], cells, spack[b], ctl);
-        SG_CHECK_LAUNCH();
-        SG_HIP(hipEventRecord(ctx->stage_done[b], st));
-        SG_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_done[b], 0));
-        SG_HIP(hipMemcpyAsync(ri->cell + (size_t)r0 * n_used, spack[b], cells * 8, hipMemcpyDeviceToHost,
-                              ctx->copy_stream));
-        SG_HIP(hipEventRecord(ctx->stage_copied[b], ctx->copy_stream));
-        unsigned long long h[2] = {0, 0};
-        copy_to_host(ctx, h, ctl, 16);  // (the next block's build starts after this sync; the copy runs on)
-        m = std::min<uint64_t>(m, h[0]);
-        if (h[1]) {  // paths of 4.29 s or more: their u64 latencies to the side table
-          uint64_t* list = ctx->r_misc.get<uint64_t>(2 * h[1]);
-          SG_HIP(hipMemsetAsync(ctl + 1, 0, 8, st));
-          hipLaunchKernelGGL(k_wide_list, dim3(grid_for(cells, 256, 4096)), dim3(256), 0, st, slat[b], cells,
-                             (uint64_t)r0 * n_used, ctl + 1, list);
-          SG_CHECK_LAUNCH();
-          std::vector<uint64_t> hl(2 * h[1]);
-          copy_to_host(ctx, hl.data(), list, hl.size() * 8);
-          for (size_t i = 0; i < h[1]; i++) ri->wide.push_back({hl[2 * i], hl[2 * i + 1]});
-        }
-      }
-    } catch (...) {
-      (void)hipStreamSynchronize(ctx->copy_stream);  // no copy may still run into the object
-      throw;
-    }
-    SG_HIP(hipStreamSynchronize(ctx->copy_stream));
-    std::sort(ri->wide.begin(), ri->wide.end(),
-              [](const sg_routing_info::Wide& x, const sg_routing_info::Wide& y) { return x.cell < y.cell; });
-    std::fill(ri->row_set.begin(), ri->row_set.end(), 2);  // written; per-row minima not kept
-    ri->rows_set = n_used;
-    ri->min_lat = m;
-    ri->filled = true;
+    FillRows out;
+    fill_rows(ctx, net, nodes, flags, ri, 0, n_used, (n_used + 7) / 8, true, &out);  // blocks of about 1/8 of the table
+    fill_finish(ri, out.min_lat, std::move(out.wide));
   });
 }
 

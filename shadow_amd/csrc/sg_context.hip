@@ -251,6 +251,12 @@ void sg_ctx_destroy(sg_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->side_stream) {
+    (void)hipStreamSynchronize(ctx->side_stream);
+    (void)hipStreamDestroy(ctx->side_stream);
+  }
+  if (ctx->plan_lists) (void)hipEventDestroy(ctx->plan_lists);
+  if (ctx->plan_bounds) (void)hipEventDestroy(ctx->plan_bounds);
   for (auto& kv : ctx->timers)
     for (auto& pr : kv.second.pending) {
       (void)hipEventDestroy(pr.first);

@@ -114,6 +114,20 @@ struct sg_ctx {
   hipStream_t copy_stream = nullptr;
   bool in_fill = false;  // inside sg_routing_info_fill (selects the row-block kernel symbols)
   hipEvent_t stage_done[2] = {nullptr, nullptr}, stage_copied[2] = {nullptr, nullptr};
+  // The phased plan's bound rows (sg_plan.hip k_plan_bounds) run beside phase 0 on a stream
+  // of their own (created by the first build that needs it): plan_lists orders them after the
+  // lists kernel, plan_bounds orders the first bounded launch after them.  side_busy: work was
+  // queued there that the context stream's last synchronisation may not cover (an error exit
+  // synchronises the side stream itself).
+  hipStream_t side_stream = nullptr;
+  hipEvent_t plan_lists = nullptr, plan_bounds = nullptr;
+  bool side_busy = false;
+  // sg_routing_build with the identity used list ("every node used", in order): no copy of the
+  // list; the build's first kernel that reads it writes used_fill[j] = j, j < used_fill_n, first
+  // (the plan's k_plan_rel, else a fill of its own: sg_routing.hip flush_used).  Null: nothing
+  // is pending.
+  uint32_t* used_fill = nullptr;
+  uint32_t used_fill_n = 0;
   // Round control: round_err (device, zeroed at creation) collects the source
   // phase's error flags; the stats kernel hands them to the host and clears
   // them for the next round.  round_ret (pinned, mapped host memory) receives
@@ -131,8 +145,9 @@ struct sg_ctx {
   uint32_t sb_parity = 0, sb_parity_c = 0;
   sg::DevBuf d_cd, d_ct, d_ck, d_ci;  // coarse-level runs of a two-level scatter
   // APSP (pinned host-mapped, 32 B): [0] the slab's active-batch count of the next
-  // pass (k_active_list, each pass-chunk end); [4] the LDS search's flagged rows and
-  // [2..3] the self-loop check's first failure (k_build_finish, the build's end)
+  // pass (k_active_list, each pass-chunk end); [4] the flagged rows' count (k_build_finish, the
+  // build's end) or, where no such kernel runs, nonzero once an LDS search flagged a row;
+  // [2..3] the self-loop check's first failure (k_build_finish)
   uint32_t* apsp_ret = nullptr;
   // sg_routing_build's self-loop check (graph/mod.rs:210-217), folded into the LDS
   // search's final kernel when it runs: the inputs, and the result once read
@@ -270,7 +285,11 @@ struct FillRows {
   uint64_t min_lat = UINT64_MAX;
   std::vector<sg_routing_info::Wide> wide;  // unsorted
 };
-void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used);
+// (returns whether the list is the identity: nodes[j] == j for every j)
+bool check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used);
+// The pending fill of an identity used list (sg_ctx::used_fill), launched now if still pending:
+// ahead of the first kernel that reads the list, wherever the plan's first kernel does not run.
+void flush_used(sg_ctx* ctx);
 void fill_rows(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t flags, sg_routing_info* ri, uint32_t r0,
                uint32_t r1, uint32_t block_rows, bool self_check, FillRows* out);
 void fill_reset(sg_routing_info* ri);
@@ -435,12 +454,22 @@ struct SsspDevPlan {
   const SsspChainDesc* chain = nullptr;  // written when the caller passed claim words
   bool landmarks = false;  // phase 0 = landmark rows; phase 1's bounds come from them (sssp_landmark_bounds)
   unsigned rows_grid = 0;  // sssp_landmark_bounds' grid (one thread per row of the block)
+  // the bound rows were left to sssp_plan_bounds_side (its inputs in the plan's workspace)
+  bool bounds_deferred = false;
+  const uint32_t* rel = nullptr;
+  const uint8_t* phase_of = nullptr;
 };
 constexpr int SSSP_PHASES_MAX = 6;
+// defer_bounds: the plan ends at its lists (an event marks them on the context stream); the
+// caller launches phase 0, which reads no bound row, and then sssp_plan_bounds_side.
 SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                              uint32_t row_end, int n_phase, int kb, bool exact, int hops, uint32_t n_land,
                              uint32_t* zero_rows = nullptr, uint32_t* zero_rows2 = nullptr, bool chain = false,
-                             bool chain_exact = false);
+                             bool chain_exact = false, bool defer_bounds = false);
+// The deferred bound rows on the context's side stream, after the plan's lists.  Sets
+// ctx->side_busy; the caller orders the context stream's next launch after the side stream.
+void sssp_plan_bounds_side(sg_ctx* ctx, const sg_net* net, const SsspDevPlan& p, const uint32_t* d_used,
+                           uint32_t row_begin, uint32_t row_end, int kb, bool exact, int hops);
 // Without a plan: rel alone (in the plan's workspace) and the chained rows' descriptor, zeroing the
 // row flags, the claim words and the two claim counters in the same launch.
 const SsspChainDesc* sssp_plain_rel(sg_ctx* ctx, const sg_net* net, const uint32_t* d_used, uint32_t row_begin,

@@ -69,6 +69,7 @@
 //   SG_NET_THREADS | 4 | 1 .. 4 | test | graph upload: host threads staging a large edge list
 //   SG_NET_LDS | 1 | 0, 1 | tune | graph upload: 0 counts and places arcs with global atomics at any size
 //   SG_NET_TRACE | 0 | 0, 1 | diag | graph upload: host phases on stderr
+//   SG_BUILD_FUSED | 1 | 0, 1 | tune | one-shot build: 0 copies an identity used list and keeps the plan's bound rows ahead of phase 0
 //   SG_RI_BLOCK_ROWS | n_used / 8; a group member: half its rows | >= 64, whole 64-row batches | test | RoutingInfo fill: rows per block
 //   SG_GML_THREADS | min(hardware threads, 16) | >= 1 | tune | GML parser: threads
 #pragma once
@@ -103,6 +104,9 @@ inline bool knob_off(const char* name) {
   const char* s = getenv(name);
   return s && s[0] == '0';
 }
+
+// SG_BUILD_FUSED (sg_routing.hip: the used list's upload, the LDS search's dispatch)
+inline bool build_fused() { return knob_int("SG_BUILD_FUSED", 1) != 0; }
 
 // SG_SSSP_SPIN_MAX, which the LDS and the bucketed search share
 inline unsigned sssp_spin_max() { return (unsigned)knob_int("SG_SSSP_SPIN_MAX", 1 << 22, 1, INT_MAX); }

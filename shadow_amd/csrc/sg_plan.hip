@@ -48,16 +48,20 @@
 namespace sg {
 
 // rel[used row] = its relative row; also zeroes jn (and the caller's per-row flags, and the two
-// claim counters of a launch without a plan): no fills on the build's path
+// claim counters of a launch without a plan): no fills on the build's path.  fill_used: the used
+// list is the identity and was not copied (sg_ctx::used_fill): its n_fill entries are written
+// here, by a grid that covers them, and a row's node is its own index.
 __global__ void k_plan_rel(const uint32_t* __restrict__ used, uint32_t row_begin, uint32_t rows,
                            uint32_t* __restrict__ rel, uint8_t* __restrict__ jn, uint32_t* __restrict__ zero_rows,
                            uint32_t* __restrict__ zero_rows2, uint32_t* __restrict__ zero_ctr,
-                           SsspChainDesc* __restrict__ desc, SsspChainDesc desc_val) {
+                           SsspChainDesc* __restrict__ desc, SsspChainDesc desc_val, uint32_t* fill_used,
+                           uint32_t n_fill) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (zero_ctr && r < 2) zero_ctr[r] = 0;
   if (desc && r == 0) *desc = desc_val;  // the chained rows' descriptor (sg_sssp.hip)
+  if (fill_used && r < n_fill) fill_used[r] = r;
   if (r >= rows) return;
-  rel[used[row_begin + r]] = r;
+  rel[fill_used ? row_begin + r : used[row_begin + r]] = r;
   if (jn) jn[r] = 0;
   if (zero_rows) zero_rows[r] = 0;
   if (zero_rows2) zero_rows2[r] = 0;
@@ -372,20 +376,24 @@ __global__ void __launch_bounds__(NT)
 
 // Bound rows.  Candidate key: (not exact) << 63 | latency << 31 | relative row, so
 // the u64 order is the plan's rank (exact seeds, then latency, then row).
+// PBW waves per block: PB_WAVES on the build's stream; one (5 KB of LDS, 64 threads) when the
+// launch runs beside phase 0 (sssp_plan_bounds_side), whose workgroup leaves a CU 8 KB of LDS
+// and 1,024 thread slots at C3: such a block fits beside it, a block of four (20 KB) does not.
 constexpr int PB_WAVES = 4;
 constexpr int PB_FMAX = 256;  // zero-loss frontier entries per wave and level (more are dropped: fewer seeds)
 constexpr int PB_LIST = 4;    // candidates a lane keeps
 
-__global__ void __launch_bounds__(PB_WAVES * 64)
+template <int PBW>
+__global__ void __launch_bounds__(PBW * 64)
     k_plan_bounds(const uint32_t* __restrict__ out_off, const uint32_t* __restrict__ out_arc,
                   const uint32_t* __restrict__ used, const uint32_t* __restrict__ rel,
                   const uint8_t* __restrict__ phase_of, const uint32_t* __restrict__ list, uint32_t rows,
                   uint32_t row_begin, int kb, int exact, int hops, uint32_t* __restrict__ ub_row,
                   uint32_t* __restrict__ ub_w) {
-  __shared__ uint32_t fx[PB_WAVES][2][PB_FMAX], fw[PB_WAVES][2][PB_FMAX], fpre[PB_WAVES][PB_FMAX + 1];
-  __shared__ uint32_t fcnt[PB_WAVES][2];
+  __shared__ uint32_t fx[PBW][2][PB_FMAX], fw[PBW][2][PB_FMAX], fpre[PBW][PB_FMAX + 1];
+  __shared__ uint32_t fcnt[PBW][2];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t i = blockIdx.x * PB_WAVES + wv;
+  const uint32_t i = blockIdx.x * PBW + wv;
   if (i >= rows) return;
   const uint32_t row = list[i];
   const int ph = phase_of[row - row_begin];
@@ -494,9 +502,18 @@ __global__ void __launch_bounds__(PB_WAVES * 64)
   }
 }
 
+// A pending identity used list (sg_ctx::used_fill) is written by the k_plan_rel launch that takes it.
+static uint32_t* take_used_fill(sg_ctx* ctx, const uint32_t* d_used, uint32_t* n_fill) {
+  uint32_t* fill = ctx->used_fill == d_used ? ctx->used_fill : nullptr;
+  *n_fill = fill ? ctx->used_fill_n : 0u;
+  if (fill) ctx->used_fill = nullptr;
+  return fill;
+}
+
 SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                              uint32_t row_end, int n_phase, int kb, bool exact, int hops, uint32_t n_land,
-                             uint32_t* zero_rows, uint32_t* zero_rows2, bool chain, bool chain_exact) {
+                             uint32_t* zero_rows, uint32_t* zero_rows2, bool chain, bool chain_exact,
+                             bool defer_bounds) {
   (void)n_used;
   const uint32_t n = net->n_nodes, rows = row_end - row_begin;
   n_phase = std::max(2, std::min(SSSP_PHASES_MAX - (n_land ? 1 : 0), n_phase));
@@ -528,8 +545,11 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
     // rel of a node outside the block's rows reads ~0; a block of all n rows writes every entry
     if (rows != n) SG_HIP(hipMemsetAsync(rel, 0xff, (size_t)n * 4, st));
     const unsigned g = grid_for(rows, 256);
-    hipLaunchKernelGGL(k_plan_rel, dim3(g), dim3(256), 0, st, d_used, row_begin, rows, rel, jn, zero_rows, zero_rows2,
-                       (uint32_t*)nullptr, chain ? desc : (SsspChainDesc*)nullptr, desc_val);
+    uint32_t n_fill = 0;
+    uint32_t* fill = take_used_fill(ctx, d_used, &n_fill);
+    hipLaunchKernelGGL(k_plan_rel, dim3(grid_for(std::max(rows, n_fill), 256)), dim3(256), 0, st, d_used, row_begin, rows,
+                       rel, jn, zero_rows, zero_rows2, (uint32_t*)nullptr, chain ? desc : (SsspChainDesc*)nullptr,
+                       desc_val, fill, n_fill);
     // in-neighbours: the CSC when directed; the out-arcs themselves when undirected
     if (net->directed) ensure_csc(ctx, net);
     const uint32_t* in_off = net->directed ? net->in_off : net->out_off;
@@ -552,10 +572,21 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
                        pos, p.ctl, p.ctr);
     SG_CHECK_LAUNCH();
   }
-  {
+  p.rel = rel;
+  p.phase_of = phase_of;
+  if (defer_bounds && !n_land) {
+    // the bound rows wait for the lists only: the caller launches phase 0 ahead of them
+    if (!ctx->side_stream) SG_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+    // (both sides of either event are kernels of this device: no system-scope fence at the record)
+    const unsigned ev_flags = hipEventDisableTiming | hipEventDisableSystemFence;
+    if (!ctx->plan_lists) SG_HIP(hipEventCreateWithFlags(&ctx->plan_lists, ev_flags));
+    if (!ctx->plan_bounds) SG_HIP(hipEventCreateWithFlags(&ctx->plan_bounds, ev_flags));
+    SG_HIP(hipEventRecord(ctx->plan_lists, st));
+    p.bounds_deferred = true;
+  } else {
     TimedLaunch tl(ctx, "plan_bounds", 0.0);
-    hipLaunchKernelGGL(k_plan_bounds, dim3((rows + PB_WAVES - 1) / PB_WAVES), dim3(PB_WAVES * 64), 0, ctx->stream,
-                       net->out_off, net->out_arc, d_used, rel, phase_of, p.list, rows, row_begin,
+    hipLaunchKernelGGL(k_plan_bounds<PB_WAVES>, dim3((rows + PB_WAVES - 1) / PB_WAVES), dim3(PB_WAVES * 64), 0,
+                       ctx->stream, net->out_off, net->out_arc, d_used, rel, phase_of, p.list, rows, row_begin,
                        std::max(1, std::min(SSSP_KB_MAX, kb)), exact ? 1 : 0, std::max(1, std::min(3, hops)),
                        p.ub_row, p.ub_w);
     SG_CHECK_LAUNCH();
@@ -570,6 +601,24 @@ SsspDevPlan sssp_device_plan(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, u
   return p;
 }
 
+// The bound rows of a plan built with defer_bounds, on the side stream: phase 0 (launched by the
+// caller just before) starts from infinity and reads none of them, so the 32 us they take at C3
+// run under it instead of ahead of it.  One wave per block, which fits beside a search workgroup
+// (PBW above); where it does not, the blocks run in phase 0's tail and nothing is lost.  The
+// caller then makes the context stream wait for the side stream (plan_bounds) before the first
+// bounded phase -- and with it everything later on that stream: the next build's use of r_plan,
+// a destroyed net's reuse.
+void sssp_plan_bounds_side(sg_ctx* ctx, const sg_net* net, const SsspDevPlan& p, const uint32_t* d_used,
+                           uint32_t row_begin, uint32_t row_end, int kb, bool exact, int hops) {
+  const uint32_t rows = row_end - row_begin;
+  SG_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->plan_lists, 0));
+  ctx->side_busy = true;
+  hipLaunchKernelGGL(k_plan_bounds<1>, dim3(rows), dim3(64), 0, ctx->side_stream, net->out_off, net->out_arc, d_used,
+                     p.rel, p.phase_of, p.list, rows, row_begin, std::max(1, std::min(SSSP_KB_MAX, kb)), exact ? 1 : 0,
+                     std::max(1, std::min(3, hops)), p.ub_row, p.ub_w);
+  SG_CHECK_LAUNCH();
+}
+
 // A launch without a plan (sg_sssp.hip "Chained rows"): rel alone and the descriptor, with the row
 // flags, the claim words and the launch's two claim counters zeroed by the same kernel.
 const SsspChainDesc* sssp_plain_rel(sg_ctx* ctx, const sg_net* net, const uint32_t* d_used, uint32_t row_begin,
@@ -582,8 +631,10 @@ const SsspChainDesc* sssp_plain_rel(sg_ctx* ctx, const sg_net* net, const uint32
   uint32_t* rel = w + dw;
   // (a row block: no fill, the search checks each entry it reads against used[])
   const SsspChainDesc desc_val{claim, rel, nullptr, nullptr, chain_exact ? 1u : 0u, rows != n ? rows : 0u};
-  hipLaunchKernelGGL(k_plan_rel, dim3(grid_for(rows, 256)), dim3(256), 0, ctx->stream, d_used, row_begin, rows, rel,
-                     (uint8_t*)nullptr, zero_rows, claim, zero_ctr, desc, desc_val);
+  uint32_t n_fill = 0;
+  uint32_t* fill = take_used_fill(ctx, d_used, &n_fill);
+  hipLaunchKernelGGL(k_plan_rel, dim3(grid_for(std::max(rows, n_fill), 256)), dim3(256), 0, ctx->stream, d_used,
+                     row_begin, rows, rel, (uint8_t*)nullptr, zero_rows, claim, zero_ctr, desc, desc_val, fill, n_fill);
   SG_CHECK_LAUNCH();
   return desc;
 }

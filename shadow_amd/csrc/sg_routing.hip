@@ -55,9 +55,12 @@ __global__ void k_self_check(const uint32_t* __restrict__ used, uint32_t n_used,
 // kernel, and (when sg_routing_build asked for it) the self-loop check's first
 // failure as k_self_check encodes it, both into the mapped return block -- the
 // build's end is one synchronisation and no copies.  One workgroup, branch-free loads.
+// count_flags 0: the self-loop check alone (on the side stream, beside phase 0: the LDS search
+// kernels then tell the host themselves that a row was flagged, and no kernel ends the build).
 __global__ void __launch_bounds__(1024) k_build_finish(const uint32_t* __restrict__ sat, uint32_t rows,
                                                        const uint32_t* __restrict__ used, uint32_t n_used,
-                                                       const uint32_t* __restrict__ self_cnt, uint32_t* __restrict__ ret) {
+                                                       const uint32_t* __restrict__ self_cnt, uint32_t* __restrict__ ret,
+                                                       int count_flags) {
   constexpr int G = 8;
   __shared__ uint32_t s_cnt[16];
   __shared__ unsigned long long s_min[16];
@@ -104,7 +107,7 @@ __global__ void __launch_bounds__(1024) k_build_finish(const uint32_t* __restric
       t += s_cnt[w];
       m = min(m, s_min[w]);
     }
-    ret[4] = t;
+    if (count_flags) ret[4] = t;
     ((unsigned long long*)ret)[1] = m;
   }
 }
@@ -234,6 +237,7 @@ __global__ void k_wide_list(const uint64_t* __restrict__ lat, size_t cells, uint
 // n^2 assertion (:219).  The search reads self_edge only at count 1 (and it is
 // zeroed elsewhere), so it stays in bounds on a graph the check rejects.
 static unsigned long long* launch_self_loops(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used) {
+  flush_used(ctx);
   unsigned long long* first = ctx->r_self.get<unsigned long long>(4);  // (its own word: the build uses r_err)
   SG_HIP(hipMemsetAsync(first, 0xff, 8, ctx->stream));
   hipLaunchKernelGGL(k_self_check, dim3(grid_for(n_used, 256, 4096)), dim3(256), 0, ctx->stream,
@@ -280,12 +284,16 @@ static double read_work(sg_ctx* ctx, const unsigned long long* work, unsigned lo
 
 // The build's end: the flagged rows' count and the self-loop check in one kernel,
 // one synchronisation; the flags themselves are copied only when some row was
-// flagged.  Returns the rows (absolute) that need the wide kernel.
-static std::vector<uint32_t> finish_rows(sg_ctx* ctx, const uint32_t* sat, uint32_t row_begin, uint32_t rows) {
+// flagged.  Returns the rows (absolute) that need the wide kernel.  told: no kernel -- the
+// searches set the flagged word themselves and the self-loop check ran on the side stream.
+static std::vector<uint32_t> finish_rows(sg_ctx* ctx, const uint32_t* sat, uint32_t row_begin, uint32_t rows,
+                                         bool told = false) {
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_build_finish, dim3(1), dim3(1024), 0, st, sat, rows, ctx->self_used, ctx->self_n,
-                     ctx->self_cnt, ctx->apsp_ret);
-  SG_CHECK_LAUNCH();
+  if (!told) {
+    hipLaunchKernelGGL(k_build_finish, dim3(1), dim3(1024), 0, st, sat, rows, ctx->self_used, ctx->self_n,
+                       ctx->self_cnt, ctx->apsp_ret, 1);
+    SG_CHECK_LAUNCH();
+  }
   SG_HIP(hipStreamSynchronize(st));
   const volatile uint32_t* ret = ctx->apsp_ret;
   const uint32_t n_flag = ret[4];
@@ -386,6 +394,7 @@ struct LdsKnobs {
   // arc to the row it just finished, seeded from the keys still in its LDS.  Undirected graphs,
   // the phased launches and the launch without a plan; 0 keeps the list order and the set-up.
   bool chain;
+  bool overlap;  // SG_BUILD_FUSED: the phased plan's bound rows run beside phase 0
 };
 static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used, uint32_t rows) {
   LdsKnobs k;
@@ -431,6 +440,7 @@ static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used,
   const int land_env = knob_int("SG_SSSP_LANDMARKS", 0);
   k.n_land = net->directed || land_env <= 0 ? 0u : (uint32_t)land_env;
   k.chain = chain;
+  k.overlap = build_fused();
   return k;
 }
 
@@ -472,6 +482,19 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   hipStream_t st = ctx->stream;
   const uint32_t rows = row_end - row_begin;
   const LdsKnobs k = lds_knobs(ctx, net, n_used, rows);
+  // (the searches set it to 1 when they flag a row; no launch of an earlier build is in flight)
+  *(volatile uint32_t*)(ctx->apsp_ret + 4) = 0u;
+  bool told = false;  // the build needs no final kernel (the phased plan with its side stream)
+  // However the build ends, nothing stays pending on the side stream: the build's last
+  // synchronisation covers it once the context stream waits for the bound rows (side_busy is
+  // cleared there); an error thrown before that leaves through this.
+  struct SideDrain {
+    sg_ctx* c;
+    ~SideDrain() {
+      if (c->side_busy) (void)hipStreamSynchronize(c->side_stream);
+      c->side_busy = false;
+    }
+  } side_drain{ctx};
   // the row flags, then the chained rows' claim words: zeroed by the plan's first kernel, else here
   uint32_t* sat = ctx->r_flags.get<uint32_t>(2 * (size_t)rows);
   uint32_t* claim = k.chain ? sat + rows : nullptr;
@@ -535,9 +558,12 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     }
     publish_phases(plan);  // (the one launch chains no rows)
   } else if (k.phased) {
+    // the plan's bound rows beside phase 0 (sssp_plan_bounds_side) -- not with timers on, where
+    // read_timer("plan_bounds") times them on this stream, and not with landmarks
+    const bool overlap = k.overlap && !ctx->timing && !k.n_land;
     const SsspDevPlan plan =
         sssp_device_plan(ctx, net, d_used, n_used, row_begin, row_end, k.n_phase, k.kb, k.exact, k.hops, k.n_land, sat,
-                         claim, claim != nullptr, knob_int("SG_SSSP_EXACT", 1) != 0);
+                         claim, claim != nullptr, knob_int("SG_SSSP_EXACT", 1) != 0, overlap);
     for (int ph = 0; ph < plan.n_phase; ph++) {
       const bool bounded = ph > 0;
       SsspLdsLaunch l = base;
@@ -555,6 +581,18 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
         launch_sssp_lds(ctx, net, l);
       }
       diag_chained("phase", ph);
+      if (ph == 0 && plan.bounds_deferred) {
+        sssp_plan_bounds_side(ctx, net, plan, d_used, row_begin, row_end, k.kb, k.exact, k.hops);
+        // the build's self-loop check rides along; the bounded phases wait for both
+        if (ctx->self_used) {
+          hipLaunchKernelGGL(k_build_finish, dim3(1), dim3(1024), 0, ctx->side_stream, sat, 0u, ctx->self_used,
+                             ctx->self_n, ctx->self_cnt, ctx->apsp_ret, 0);
+          SG_CHECK_LAUNCH();
+        }
+        told = true;
+        SG_HIP(hipEventRecord(ctx->plan_bounds, ctx->side_stream));
+        SG_HIP(hipStreamWaitEvent(st, ctx->plan_bounds, 0));
+      }
       if (ph == 0 && plan.landmarks) sssp_landmark_bounds(ctx, plan, n_used, row_begin, out_lat, sat, k.kb);
     }
     publish_phases(plan);
@@ -568,6 +606,7 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
       l.chain = sssp_plain_rel(ctx, net, d_used, row_begin, row_end, sat, claim, l.plan_ctr,
                                knob_int("SG_SSSP_EXACT", 1) != 0);
     } else {
+      flush_used(ctx);  // (k_plan_rel writes a pending identity list, here as in a plan; nothing else does)
       launch_zero2(ctx, sat, rows, l.plan_ctr, 2u);
     }
     {
@@ -577,7 +616,8 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     diag_chained("launch", 0);
   }
   if (diag) print_sssp_diag(ctx, net, diag, n_diag, k.delta);
-  std::vector<uint32_t> wide_rows = finish_rows(ctx, sat, row_begin, rows);
+  std::vector<uint32_t> wide_rows = finish_rows(ctx, sat, row_begin, rows, told);
+  ctx->side_busy = false;  // (the context stream waited for the side stream and was synchronised)
   if (work) {
     unsigned long long w[WORK_SHARDS + 2];
     timer_add_work(ctx, "sssp", read_work(ctx, work, w, 2));
@@ -608,12 +648,16 @@ static void shortest_paths(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, con
   const bool arcs_ok = (uint64_t)net->n_arcs * 12 < (1ull << 31);
   // Dense graphs up to DENSE_MAX nodes (C2): the register-resident search of sg_dense.hip,
   // Dijkstra's n^2 relaxations per row
-  if (per_source && dense_on && !sparse && sssp_dense_fits(net->n_nodes))
+  const bool dense = per_source && dense_on && !sparse && sssp_dense_fits(net->n_nodes);
+  const bool bucket = !dense && per_source && sparse && arcs_ok && bucket_env != 0 && sssp_bucket_fits(net->n_nodes) &&
+                      (bucket_env == 1 || !sssp_lds_fits(net->n_nodes));
+  const bool lds = !dense && !bucket && per_source && sparse && sssp_lds_fits(net->n_nodes) && arcs_ok;
+  if (!lds) flush_used(ctx);  // (the LDS search's plan writes a pending identity list itself)
+  if (dense)
     shortest_paths_dense(ctx, net, d_used, n_used, row_begin, row_end, out_lat, out_loss);
-  else if (per_source && sparse && arcs_ok && bucket_env != 0 && sssp_bucket_fits(net->n_nodes) &&
-           (bucket_env == 1 || !sssp_lds_fits(net->n_nodes)))
+  else if (bucket)
     shortest_paths_bucket(ctx, net, d_used, n_used, row_begin, row_end, out_lat, out_loss);
-  else if (per_source && sparse && sssp_lds_fits(net->n_nodes) && arcs_ok)
+  else if (lds)
     shortest_paths_lds(ctx, net, d_used, n_used, row_begin, row_end, out_lat, out_loss);
   else
     shortest_paths_slab(ctx, net, d_used, n_used, row_begin, row_end, out_lat, out_loss);
@@ -624,6 +668,7 @@ static void direct_paths(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, const
                          uint32_t n_used, uint32_t row_begin, uint32_t row_end, uint64_t* out_lat,
                          float* out_loss) {
   hipStream_t st = ctx->stream;
+  flush_used(ctx);
   const uint32_t n = net->n_nodes;
   std::vector<uint32_t> map(n, ~0u);
   for (uint32_t j = 0; j < n_used; j++) map[h_used[j]] = j;
@@ -658,23 +703,40 @@ static void direct_paths(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, const
 namespace sg {
 // The used-node list: every index in range, none twice.  One branch-free pass; only a bad
 // list is walked again, entry by entry, for the first bad entry's error.
-void check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used) {
+bool check_node_list(const sg_net* net, const uint32_t* nodes, uint32_t n_used) {
   const uint32_t n = net->n_nodes;
   std::vector<uint8_t> seen((size_t)n + 1, 0);  // the spare last byte takes out-of-range ids
-  uint32_t bad = 0;
+  uint32_t bad = 0, moved = 0;
   for (uint32_t j = 0; j < n_used; j++) {
     const uint32_t v = nodes[j];
     const uint32_t out = v >= n;
     const uint32_t x = out ? n : v;
     bad |= out | (uint32_t)seen[x];
+    moved |= v ^ j;
     seen[x] = 1;
   }
-  if (!bad) return;
+  if (!bad) return !moved;
   std::fill(seen.begin(), seen.end(), (uint8_t)0);
   for (uint32_t j = 0; j < n_used; j++) {
     if (nodes[j] >= n) throw Error(SG_ERR_INVALID_ARG, "node index out of range");
     if (seen[nodes[j]]++) throw Error(SG_ERR_INVALID_ARG, "duplicate node in node list");
   }
+  return false;
+}
+
+// used[j] = j: the identity used list written on the device (sg_ctx::used_fill) where no plan
+// kernel does it; one launch in place of a 40-KB copy at C3 and of the wait that follows a copy.
+__global__ void k_used_identity(uint32_t* __restrict__ used, uint32_t n_used) {
+  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n_used; j += gridDim.x * blockDim.x) used[j] = j;
+}
+
+void flush_used(sg_ctx* ctx) {
+  uint32_t* used = ctx->used_fill;
+  if (!used) return;
+  ctx->used_fill = nullptr;
+  hipLaunchKernelGGL(k_used_identity, dim3(grid_for(ctx->used_fill_n, 256, 1024)), dim3(256), 0, ctx->stream, used,
+                     ctx->used_fill_n);
+  SG_CHECK_LAUNCH();
 }
 }  // namespace sg
 
@@ -690,11 +752,20 @@ int32_t sg_routing_build(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32
     if (n_used && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
     if (row_end > row_begin && (!out_latency_ns || !out_packet_loss))
       throw Error(SG_ERR_INVALID_ARG, "null output");
-    check_node_list(net, nodes, n_used);
+    const bool identity = check_node_list(net, nodes, n_used);
     if (n_used == 0) return;
     hipStream_t st = ctx->stream;
     uint32_t* d_used = ctx->r_used.get<uint32_t>(n_used);
-    {
+    struct NoFill {  // however the build ends, no later call finds this list's fill pending
+      sg_ctx* c;
+      ~NoFill() { c->used_fill = nullptr; }
+    } no_fill{ctx};
+    if (identity && build_fused()) {
+      // every node used, in order (C3, C5, C2; Shadow whenever every graph node has a host): the
+      // list is written by the first kernel that reads it (the plan's k_plan_rel, else flush_used)
+      ctx->used_fill = d_used;
+      ctx->used_fill_n = n_used;
+    } else {
       char* hu = stage_acquire(ctx, 1, (size_t)n_used * 4);
       memcpy(hu, nodes, (size_t)n_used * 4);
       SG_HIP(hipMemcpyAsync(d_used, hu, (size_t)n_used * 4, hipMemcpyHostToDevice, st));

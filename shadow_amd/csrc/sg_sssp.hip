@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(NT)
                const uint32_t* __restrict__ ub_row, const uint32_t* __restrict__ ub_w,
                uint32_t* __restrict__ item_ctr, uint32_t n_items, uint32_t spin_max,
                const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done,
-               const SsspChainDesc* chain_desc) {
+               const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag) {
   constexpr int NW = NT / 64;
   constexpr int AUX = FLAG ? SSSP_SC1 : 0;  // bound rows and the output: sc1 in the flagged launch
   // Chained rows: persistent workgroups, never the flagged launch.  The claim words and the maps
@@ -467,6 +467,7 @@ __global__ void __launch_bounds__(NT)
     auto give_up = [&]() {
       if (lane == 0) {
         sat_row[row - row_begin] = 2u;  // never written: the wide kernel redoes it, and no search bounds by it
+        *any_flag = 1u;                 // (host-visible: some row of the build was flagged)
         // the workgroup's first wave to give up counts it out; when every persistent
         // workgroup has given up (none left to claim the rest), the last one flags the
         // rows none claimed.  (A workgroup that ends normally has seen every row claimed.)
@@ -888,6 +889,7 @@ __global__ void __launch_bounds__(NT)
     }
     if (__any(sat) && lane == 0) {
       sat_row[row - row_begin] = 1u;
+      *any_flag = 1u;
       if (FLAG) s_sat = 1u;
       if (chain_on) s_psat = 1u;
     }
@@ -976,7 +978,7 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
                        l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
                        l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
                        k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
-                       l.done, chain);
+                       l.done, chain, ctx->apsp_ret + 4);
   };
   // <counting, threads, lane arcs, fill symbol, flagged>
   if (l.done) {  // the flagged one-launch plan

@@ -23,16 +23,40 @@ def analyze(d):
         for r in csv.DictReader(open(f)):
             ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "COPY " + r.get("Direction", "")))
     ks.sort()
-    # builds: split at the first k_net_count of each build
-    starts = [i for i, k in enumerate(ks) if "k_net_count" in k[2]]
-    for bi, s in enumerate(starts[-2:]):
-        e = starts[starts.index(s) + 1] if starts.index(s) + 1 < len(starts) else len(ks)
-        t0 = ks[s][0]
-        print(f"build {bi}: {(ks[e - 1][1] - t0) / 1e3:.1f} us from the first kernel to the last end")
+    # builds: each starts at the edge list's copy, the last copy ahead of its counting kernel
+    # (k_net_count, k_net_count_lds or the fused k_net_count_scan)
+    starts = []
+    for i, k in enumerate(ks):
+        if "k_net_count" in k[2]:
+            s = i
+            while s > 0 and not ks[s][2].startswith("COPY"):
+                s -= 1
+            starts.append(s)
+    spans = {"ops before phase 0": [], "first copy to phase 0 (us)": [], "phase 0 end to bounded start (us)": [],
+             "last search end to last end (us)": []}
+    for bi, s in enumerate(starts):
+        e = starts[bi + 1] if bi + 1 < len(starts) else len(ks)
+        b = ks[s:e]
+        srch = [k for k in b if "k_sssp_lds" in k[2]]
+        if srch:
+            spans["ops before phase 0"].append(sum(1 for k in b if k[0] < srch[0][0]))
+            spans["first copy to phase 0 (us)"].append((srch[0][0] - b[0][0]) / 1e3)
+            if len(srch) > 1:
+                spans["phase 0 end to bounded start (us)"].append((srch[1][0] - srch[0][1]) / 1e3)
+            spans["last search end to last end (us)"].append((max(k[1] for k in b) - srch[-1][1]) / 1e3)
+        if bi < len(starts) - 2:
+            continue
+        t0 = b[0][0]
+        print(f"build {bi}: {(max(k[1] for k in b) - t0) / 1e3:.1f} us from the first copy to the last end")
         prev_end = t0
-        for k in ks[s:e]:
+        for k in b:
             print(f"  +{(k[0] - t0) / 1e3:8.1f} gap {(k[0] - prev_end) / 1e3:7.1f}  dur {(k[1] - k[0]) / 1e3:8.1f}  {k[2]}")
             prev_end = max(prev_end, k[1])
+    # per build, the first (cold) one left out: median and range
+    for name, v in spans.items():
+        v = sorted(v[1:])
+        if v:
+            print(f"{name}: median {v[len(v) // 2]:.1f}, {v[0]:.1f} .. {v[-1]:.1f} over {len(v)} builds")
 
 
 def main():

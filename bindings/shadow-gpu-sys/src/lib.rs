@@ -275,6 +275,26 @@ pub struct sg_outbound_queue_state {
     pub ring_dst: *mut u32,
 }
 
+/// A round-robin object's interfaces in canonical form (host arrays, any may be null): per host
+/// the deque front to back with each socket's packet count, the queued packets socket by socket
+/// in deque order, and the relay's cached packet.
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct sg_outbound_qdisc_state {
+    pub n_active: *mut u32,
+    pub active: *mut u32,
+    pub active_count: *mut u32,
+    pub n_queued: *mut u32,
+    pub q_packet: *mut u32,
+    pub q_len: *mut u32,
+    pub q_payload_len: *mut u32,
+    pub q_dst: *mut u32,
+    pub cached_packet: *mut u32,
+    pub cached_len: *mut u32,
+    pub cached_payload_len: *mut u32,
+    pub cached_dst: *mut u32,
+}
+
 /// A window's arrivals out of the wire (device arrays of capacity `cap`): the first four
 /// arrays are an `sg_inbound_arrivals`; `src_host` / `event_id` both, or both null.
 #[repr(C)]
@@ -369,6 +389,11 @@ pub const SG_OUT_QUEUED: u8 = 0;
 pub const SG_OUT_SENT: u8 = 1;
 /// dst == own address: back to the interface
 pub const SG_OUT_LOCAL: u8 = 2;
+/// experimental.interface_qdisc (QDiscMode, configuration.rs:971-973)
+pub const SG_QDISC_FIFO: u32 = 0;
+pub const SG_QDISC_ROUND_ROBIN: u32 = 1;
+/// the most socket slots per host of a round-robin object
+pub const SG_QDISC_MAX_SOCKETS: u32 = 256;
 
 // ---------------------------------------------------------------------------
 // Entry points (in the header's order)
@@ -520,6 +545,18 @@ unsafe extern "C" {
                            n_sent: *mut u32) -> i32;
     pub fn sg_outbound_get_state(ob: *mut sg_outbound, queue: *mut sg_outbound_queue_state,
                                  relay: *mut sg_inbound_relay_state) -> i32;
+
+    // ---- the interface's qdisc (interface.rs:97-108, :168-181, :227-259; queuing.rs) ----
+    pub fn sg_outbound_create_qdisc(ctx: *mut sg_ctx, n_hosts: u32, host_ipv4: *const u32, bw_up_bits: *const u64,
+                                    ring_cap: u32, qdisc: u32, max_sockets: u32, out: *mut *mut sg_outbound) -> i32;
+    pub fn sg_outbound_qdisc(ob: *const sg_outbound) -> u32;
+    pub fn sg_outbound_max_sockets(ob: *const sg_outbound) -> u32;
+    pub fn sg_outbound_run_qdisc(ctx: *mut sg_ctx, ob: *mut sg_outbound, sends: *const sg_outbound_sends,
+                                 socket: *const u32, window_end_ns: u64, bootstrap_end_ns: u64, sim_end_ns: u64,
+                                 event_ctr: *mut u64, fwd_time: *mut u64, pkt_status: *mut u8, n_packets: u32,
+                                 sent: *mut sg_outbound_sent, n_sent: *mut u32) -> i32;
+    pub fn sg_outbound_get_qdisc_state(ob: *mut sg_outbound, q: *mut sg_outbound_qdisc_state,
+                                       relay: *mut sg_inbound_relay_state) -> i32;
 
     /// The device array of the hosts' event-id counters (Host::event_id_counter).
     pub fn sg_hosts_event_ctr(hosts: *mut sg_hosts) -> *mut u64;

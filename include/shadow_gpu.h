@@ -656,6 +656,73 @@ typedef struct sg_outbound_queue_state {
 } sg_outbound_queue_state;
 int32_t sg_outbound_get_state(sg_outbound* ob, sg_outbound_queue_state* queue, sg_inbound_relay_state* relay);
 
+/* ---- the interface's queueing discipline (additive to ABI 7) ----------------
+ * experimental.interface_qdisc (QDiscMode, configuration.rs:971-973) selects how
+ * the interface picks the next sending socket (host/network/interface.rs:97-108):
+ * fifo, above, or round-robin, a NetworkQueueKind::FirstInFirstOut over sockets
+ * (host/network/queuing.rs).  Per host, round-robin keeps a deque of socket ids
+ * without duplicates (send_sockets and its membership set) and a FIFO of packets
+ * per socket:
+ *   a send of packet p on socket s   appends p to s's FIFO; pushes s to the deque's
+ *                                    back unless s is already in it (add_data_source,
+ *                                    interface.rs:168-181); notifies the relay as
+ *                                    under fifo;
+ *   pop() (interface.rs:227-259)     takes s from the deque's front and s's oldest
+ *                                    packet; pushes s to the back if it still holds a
+ *                                    packet (counting the sends processed before this
+ *                                    pop in the host's execution order); an empty
+ *                                    deque is an idle interface.
+ * The relay's forward loop, its cached packet (already popped: its socket has
+ * already rotated), the token bucket and the bootstrap exemption, local packets,
+ * the sim_end rule, the event-counter advances and the keyed same-time order are
+ * those of sg_outbound_run (relay/mod.rs:111-273).  With one socket per host, or a
+ * socket per packet, round-robin is the fifo order.
+ *
+ * max_sockets: the socket slots per host, rounded up to a power of two
+ * (sg_outbound_max_sockets returns that); 0 or more than SG_QDISC_MAX_SOCKETS is
+ * SG_ERR_INVALID_ARG, as is an unknown qdisc.  ring_cap keeps sg_outbound_create's
+ * contract.  sg_outbound_create(...) is sg_outbound_create_qdisc(..., SG_QDISC_FIFO, 1). */
+enum { SG_QDISC_FIFO = 0, SG_QDISC_ROUND_ROBIN = 1 };
+enum { SG_QDISC_MAX_SOCKETS = 256 };
+int32_t sg_outbound_create_qdisc(sg_ctx* ctx, uint32_t n_hosts, const uint32_t* host_ipv4,
+                                 const uint64_t* bw_up_bits, uint32_t ring_cap, uint32_t qdisc, uint32_t max_sockets,
+                                 sg_outbound** out);
+uint32_t sg_outbound_qdisc(const sg_outbound* ob);
+uint32_t sg_outbound_max_sockets(const sg_outbound* ob);
+
+/* sg_outbound_run with each send's socket: socket (device, sends->n) is the
+ * caller's per-host slot index of the sending socket, below
+ * sg_outbound_max_sockets(ob) (SG_ERR_INVALID_ARG with a message of its own
+ * otherwise).  A slot is only a queue index: it may be given to another socket
+ * once it has drained.  On a fifo object `socket` is ignored (it may be NULL) and
+ * the call is sg_outbound_run; on a round-robin object sg_outbound_run itself is
+ * SG_ERR_INVALID_ARG.  Every other argument and error is sg_outbound_run's, in
+ * the same precedence (the socket check comes after the host checks).  The sent
+ * batch has sg_outbound_run's layout: grouped by ascending host, each host's
+ * packets in forward order, send_time_ns the forward time. */
+int32_t sg_outbound_run_qdisc(sg_ctx* ctx, sg_outbound* ob, const sg_outbound_sends* sends, const uint32_t* socket,
+                              uint64_t window_end_ns, uint64_t bootstrap_end_ns, uint64_t sim_end_ns,
+                              uint64_t* event_ctr, uint64_t* fwd_time, uint8_t* pkt_status, uint32_t n_packets,
+                              sg_outbound_sent* sent, uint32_t* n_sent);
+
+/* A round-robin object's interfaces in a canonical form that does not depend on
+ * how the library stores them (host arrays, any may be NULL).  Per host h: the
+ * deque front to back is active[h * max_sockets + j], j < n_active[h], and
+ * active_count[...] the packets each of those sockets holds; the n_queued[h]
+ * queued packets are q_*[h * ring_cap + i], listed socket by socket in deque
+ * order, each socket's in FIFO order; cached_*[h] is the relay's cached packet
+ * (zeros unless relay flags bit 2).  Entries past n_active / n_queued are not
+ * written.  On a round-robin object sg_outbound_get_state's queue half is
+ * SG_ERR_INVALID_ARG (its relay half works as before); on a fifo object this
+ * call's queue half is. */
+typedef struct sg_outbound_qdisc_state {
+  uint32_t *n_active, *active, *active_count;
+  uint32_t* n_queued;
+  uint32_t *q_packet, *q_len, *q_payload_len, *q_dst;
+  uint32_t *cached_packet, *cached_len, *cached_payload_len, *cached_dst;
+} sg_outbound_qdisc_state;
+int32_t sg_outbound_get_qdisc_state(sg_outbound* ob, sg_outbound_qdisc_state* q, sg_inbound_relay_state* relay);
+
 /* The device array of the hosts' event-id counters (Host::event_id_counter). */
 uint64_t* sg_hosts_event_ctr(sg_hosts* hosts);
 

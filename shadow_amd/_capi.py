@@ -25,6 +25,7 @@ SG_ERR_PARSE = 7
 SG_ERR_UNSORTED = 8
 SG_ERR_DUPLICATE_IP = 9
 SG_ERR_CAPACITY = 10
+SG_QDISC_FIFO, SG_QDISC_ROUND_ROBIN, SG_QDISC_MAX_SOCKETS = 0, 1, 256
 SG_ERR_TIME_OVERFLOW = 11
 SG_ERR_UNSUPPORTED = 12
 SG_COMM_ID_BYTES = 128
@@ -46,6 +47,8 @@ EXPORTED = [
     "sg_codel_get_state", "sg_codel_set_state", "sg_inbound_create", "sg_inbound_destroy", "sg_inbound_ring_cap",
     "sg_inbound_run", "sg_inbound_run_ordered", "sg_ctx_set_packet_counters", "sg_inbound_get_state", "sg_hosts_event_ctr", "sg_outbound_create", "sg_outbound_destroy",
     "sg_outbound_ring_cap", "sg_outbound_run", "sg_outbound_get_state",
+    "sg_outbound_create_qdisc", "sg_outbound_qdisc", "sg_outbound_max_sockets", "sg_outbound_run_qdisc",
+    "sg_outbound_get_qdisc_state",
     "sg_routing_info_create", "sg_routing_info_destroy", "sg_routing_info_fill", "sg_routing_info_set_rows",
     "sg_routing_info_view", "sg_routing_info_rows", "sg_routing_info_index", "sg_routing_info_path", "sg_routing_info_smallest_latency",
     "sg_routing_info_increment_packet_count", "sg_routing_info_packet_count", "sg_routing_info_set_addresses",
@@ -118,6 +121,12 @@ class sg_outbound_sent(C.Structure):
 
 class sg_outbound_queue_state(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("head", "tail", "ring_packet", "ring_len", "ring_payload_len", "ring_dst")]
+
+
+class sg_outbound_qdisc_state(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("n_active", "active", "active_count", "n_queued", "q_packet", "q_len",
+                                          "q_payload_len", "q_dst", "cached_packet", "cached_len",
+                                          "cached_payload_len", "cached_dst")]
 
 
 class sg_routing_view(C.Structure):
@@ -266,6 +275,13 @@ def load(path: str | None = None):
         "sg_outbound_run": (i32, [vp, vp, C.POINTER(sg_outbound_sends), u64, u64, u64, vp, vp, vp, u32,
                                   C.POINTER(sg_outbound_sent), C.POINTER(C.c_uint32)]),
         "sg_outbound_get_state": (i32, [vp, C.POINTER(sg_outbound_queue_state), C.POINTER(sg_inbound_relay_state)]),
+        "sg_outbound_create_qdisc": (i32, [vp, u32, vp, vp, u32, u32, u32, C.POINTER(vp)]),
+        "sg_outbound_qdisc": (u32, [vp]),
+        "sg_outbound_max_sockets": (u32, [vp]),
+        "sg_outbound_run_qdisc": (i32, [vp, vp, C.POINTER(sg_outbound_sends), vp, u64, u64, u64, vp, vp, vp, u32,
+                                        C.POINTER(sg_outbound_sent), C.POINTER(C.c_uint32)]),
+        "sg_outbound_get_qdisc_state": (i32, [vp, C.POINTER(sg_outbound_qdisc_state),
+                                              C.POINTER(sg_inbound_relay_state)]),
         "sg_comm_unique_id": (i32, [vp]),
         "sg_comm_create": (i32, [vp, vp, u32, u32, C.POINTER(vp)]),
         "sg_comm_destroy": (None, [vp]),

@@ -198,23 +198,40 @@ class InboundPipeline:
 
 
 class OutboundPipeline:
-    """Every host's network interface (fifo qdisc) + outbound relay (sg_outbound_*):
-    sends enter the interface in creation order; the relay forwards them as the
-    host's token bucket (bw up) allows, packets to the host's own address back to
-    the interface, the rest to the router, i.e. to Worker::send_packet.  The
-    packets sent form the next delivery round's PacketBatch (`run` returns it)."""
+    """Every host's network interface + outbound relay (sg_outbound_*): sends enter
+    the interface; the relay forwards them as the host's token bucket (bw up)
+    allows, packets to the host's own address back to the interface, the rest to
+    the router, i.e. to Worker::send_packet.  The packets sent form the next
+    delivery round's PacketBatch (`run` returns it).
 
-    def __init__(self, host_ipv4, bw_up_bits, ring_cap: int = 4096, ctx: Optional[Context] = None):
+    qdisc (experimental.interface_qdisc): "fifo", the default -- a host's sends
+    leave in creation order -- or "round-robin" -- the relay takes one packet from
+    each sending socket in turn; `run` then takes each send's socket, a slot index
+    below max_sockets (rounded up to a power of two, at most 256)."""
+
+    QDISCS = {"fifo": _capi.SG_QDISC_FIFO, "round-robin": _capi.SG_QDISC_ROUND_ROBIN}
+
+    def __init__(self, host_ipv4, bw_up_bits, ring_cap: int = 4096, ctx: Optional[Context] = None,
+                 qdisc: str = "fifo", max_sockets: int = 1):
         self.ctx = ctx or default_context()
         ip = np.ascontiguousarray(host_ipv4, dtype=np.uint32)
         bw = np.ascontiguousarray(bw_up_bits, dtype=np.uint64)
         assert len(ip) == len(bw)
+        if qdisc not in self.QDISCS:
+            raise ValueError(f"qdisc must be one of {sorted(self.QDISCS)}, not {qdisc!r}")
         self.n = len(bw)
+        self.qdisc = qdisc
         h = C.c_void_p()
-        check(self.ctx.handle, load().sg_outbound_create(self.ctx.handle, self.n, ip.ctypes.data, bw.ctypes.data,
-                                                         int(ring_cap), C.byref(h)))
+        if qdisc == "fifo" and max_sockets == 1:
+            check(self.ctx.handle, load().sg_outbound_create(self.ctx.handle, self.n, ip.ctypes.data, bw.ctypes.data,
+                                                             int(ring_cap), C.byref(h)))
+        else:
+            check(self.ctx.handle, load().sg_outbound_create_qdisc(self.ctx.handle, self.n, ip.ctypes.data,
+                                                                   bw.ctypes.data, int(ring_cap), self.QDISCS[qdisc],
+                                                                   int(max_sockets), C.byref(h)))
         self.handle = h
         self.cap = int(load().sg_outbound_ring_cap(h))
+        self.max_sockets = int(load().sg_outbound_max_sockets(h))
         self._sent = None
 
     def sent_buffers(self, cap: int, device):
@@ -230,16 +247,24 @@ class OutboundPipeline:
 
     def run(self, host, time_ns, packet, length, payload_len, dst_ipv4, window_end_ns: int, bootstrap_end_ns: int,
             sim_end_ns: int, fwd_time, pkt_status, event_ctr_ptr: Optional[int] = None, sent_cap: Optional[int] = None,
-            event_id=None, event_created_ns=None, collect: bool = True):
+            event_id=None, event_created_ns=None, collect: bool = True, socket=None):
         """Sends as device tensors (int32 host/packet/length/payload_len/dst_ipv4, int64 time); fwd_time
         (int64) and pkt_status (uint8) are indexed by packet id.  event_id / event_created_ns (int64
         device tensors, optional, together; they need event_ctr_ptr): the sending event's id (-1 =
         UINT64_MAX: a Packet event) and creation time, which order a send against a forward task at
         the same time (sg_outbound_sends).  Returns (PacketBatch of the packets sent, in send_packet
         order, and their packet ids), views of buffers reused by the next call; with collect=False no
-        sent batch is written (sent = NULL) and it returns (None, the number of packets sent)."""
+        sent batch is written (sent = NULL) and it returns (None, the number of packets sent).
+        socket (int32 device tensor, one per send): the sending socket's slot on a round-robin
+        pipeline, which needs it; a fifo pipeline ignores it (sg_outbound_run_qdisc)."""
         from .worker import PacketBatch
         n = int(host.numel())
+        if socket is not None or self.qdisc != "fifo":
+            sock = C.c_void_p(socket.data_ptr() if socket is not None else 0)
+            fn = load().sg_outbound_run_qdisc
+            run = lambda c, hd, s_, *rest: fn(c, hd, s_, sock, *rest)
+        else:
+            run = load().sg_outbound_run
         keyed = event_id is not None
         if keyed:
             _capi.require_abi(6, "OutboundPipeline.run with event ids")
@@ -249,21 +274,21 @@ class OutboundPipeline:
                                     event_created_ns.data_ptr() if event_created_ns is not None else None)
         ns = C.c_uint32()
         if not collect:
-            check(self.ctx.handle, load().sg_outbound_run(self.ctx.handle, self.handle, C.byref(s),
-                                                          int(window_end_ns), int(bootstrap_end_ns), int(sim_end_ns),
-                                                          C.c_void_p(event_ctr_ptr or 0), fwd_time.data_ptr(),
-                                                          pkt_status.data_ptr(), int(pkt_status.numel()), None,
-                                                          C.byref(ns)))
+            check(self.ctx.handle, run(self.ctx.handle, self.handle, C.byref(s),
+                                       int(window_end_ns), int(bootstrap_end_ns), int(sim_end_ns),
+                                       C.c_void_p(event_ctr_ptr or 0), fwd_time.data_ptr(),
+                                       pkt_status.data_ptr(), int(pkt_status.numel()), None,
+                                       C.byref(ns)))
             return None, ns.value
         cap = int(sent_cap if sent_cap is not None else n + self.n * 4)
         b = self.sent_buffers(max(cap, 1), fwd_time.device)
         o = _capi.sg_outbound_sent(cap, *(b[k].data_ptr() for k in ("src_host", "dst_ipv4", "payload_len",
                                                                      "send_time_ns", "packet")))
-        check(self.ctx.handle, load().sg_outbound_run(self.ctx.handle, self.handle, C.byref(s), int(window_end_ns),
-                                                      int(bootstrap_end_ns), int(sim_end_ns),
-                                                      C.c_void_p(event_ctr_ptr or 0), fwd_time.data_ptr(),
-                                                      pkt_status.data_ptr(), int(pkt_status.numel()), C.byref(o),
-                                                      C.byref(ns)))
+        check(self.ctx.handle, run(self.ctx.handle, self.handle, C.byref(s), int(window_end_ns),
+                                   int(bootstrap_end_ns), int(sim_end_ns),
+                                   C.c_void_p(event_ctr_ptr or 0), fwd_time.data_ptr(),
+                                   pkt_status.data_ptr(), int(pkt_status.numel()), C.byref(o),
+                                   C.byref(ns)))
         k = ns.value
         batch = PacketBatch(b["src_host"][:k], b["dst_ipv4"][:k], b["payload_len"][:k], b["send_time_ns"][:k])
         return batch, b["packet"][:k]
@@ -283,6 +308,25 @@ class OutboundPipeline:
         rs = _capi.sg_inbound_relay_state(v("rflags"), v("task_time"), None, None, v("tb_cap"), v("tb_bal"),
                                           v("tb_inc"), v("tb_last"), v("task_id"), v("task_born"))
         check(self.ctx.handle, load().sg_outbound_get_state(self.handle, C.byref(q), C.byref(rs)))
+        return st
+
+    def get_qdisc_state(self) -> dict:
+        """A round-robin pipeline's interfaces in canonical form (sg_outbound_qdisc_state: per host
+        the deque front to back with each socket's packet count, the queued packets socket by socket
+        in deque order, the cached packet) + the relay state under get_state()'s names."""
+        n, c, S = self.n, self.cap, self.max_sockets
+        u32 = lambda k: np.zeros(k, np.uint32)
+        st = dict(n_active=u32(n), active=u32(n * S), active_count=u32(n * S), n_queued=u32(n), q_packet=u32(n * c),
+                  q_len=u32(n * c), q_payload_len=u32(n * c), q_dst=u32(n * c), cached_packet=u32(n),
+                  cached_len=u32(n), cached_payload_len=u32(n), cached_dst=u32(n),
+                  rflags=np.zeros(n, np.uint8), task_time=np.zeros(n, np.uint64), task_id=np.zeros(n, np.uint64),
+                  task_born=np.zeros(n, np.uint64), tb_cap=np.zeros(n, np.uint64),
+                  tb_bal=np.zeros(n, np.uint64), tb_inc=np.zeros(n, np.uint64), tb_last=np.zeros(n, np.uint64))
+        v = lambda k: st[k].ctypes.data_as(C.c_void_p)
+        q = _capi.sg_outbound_qdisc_state(*(v(k) for k, _ in _capi.sg_outbound_qdisc_state._fields_))
+        rs = _capi.sg_inbound_relay_state(v("rflags"), v("task_time"), None, None, v("tb_cap"), v("tb_bal"),
+                                          v("tb_inc"), v("tb_last"), v("task_id"), v("task_born"))
+        check(self.ctx.handle, load().sg_outbound_get_qdisc_state(self.handle, C.byref(q), C.byref(rs)))
         return st
 
     def __del__(self):

@@ -436,6 +436,19 @@ unsafe extern "C" {
     pub fn sg_routing_min_latency(ctx: *mut sg_ctx, d_latency_ns: *const u64, count: usize, out_min: *mut u64)
         -> i32;
 
+    // ---- shortest-path trees: which links a path uses (graph/mod.rs:183-228, 322-331) ----
+    /// pred / first_hop rows (petgraph indices) from finished table rows; `nodes` is a permutation.
+    pub fn sg_routing_tree(ctx: *mut sg_ctx, net: *mut sg_net, nodes: *const u32, n_nodes: u32, row_begin: u32,
+                           row_end: u32, flags: u32, latency_ns: *const u64, packet_loss: *const f32,
+                           out_pred: *mut u32, out_first_hop: *mut u32) -> i32;
+    /// sg_routing_build over those rows, then the tree pass; needs SG_ROUTE_SHORTEST_PATH.
+    pub fn sg_routing_build_tree(ctx: *mut sg_ctx, net: *mut sg_net, nodes: *const u32, n_nodes: u32,
+                                 row_begin: u32, row_end: u32, flags: u32, out_latency_ns: *mut u64,
+                                 out_packet_loss: *mut f32, out_pred: *mut u32, out_first_hop: *mut u32) -> i32;
+    /// Host only: the node sequence src ... dst from one host pred row (the row of `src`).
+    pub fn sg_tree_path(pred_row: *const u32, nodes: *const u32, n_nodes: u32, src: u32, dst: u32,
+                        out_path: *mut u32, cap: u32, len: *mut u32) -> i32;
+
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;
     pub fn sg_routing_info_destroy(ri: *mut sg_routing_info);

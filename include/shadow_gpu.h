@@ -159,6 +159,70 @@ int32_t sg_routing_build(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32
 int32_t sg_routing_min_latency(sg_ctx* ctx, const uint64_t* d_latency_ns, size_t count,
                                uint64_t* out_min);
 
+/* ---- shortest-path trees: predecessor and first-hop rows (additive to ABI 7) --
+ * Which links a path uses.  The reference keeps no such table (a PathProperties
+ * is a latency and a loss, graph/mod.rs:297-303), but compute_shortest_paths
+ * (graph/mod.rs:183-228) and the left fold PathProperties::add
+ * (graph/mod.rs:322-331) pin one: a path is right exactly when default() + e1 +
+ * ... + ek over its edges gives the table's cell, latency and loss bits alike.
+ *
+ * For a source s let key[v] = (latency, loss bits) be s's row of the table, with
+ * key[s] = (0, +0.0f), the fold's default() (the diagonal cell holds the
+ * self-loop and is not read).  An in-arc u -> v (u != v, v != s; parallel edges
+ * each count) is tight when key[u].lat + w.lat == key[v].lat and the f32 fold
+ * 1 - (1 - key[u].loss) * (1 - w.loss), one rounding per operation, has exactly
+ * key[v]'s loss bits.  Then
+ *   pred[s][v]      = the smallest petgraph node index u among v's tight in-arcs
+ *                     (by value, never by arc position); pred[s][s] = s.  Arc
+ *                     latency is at least 1 ns, so every pred row is a tree rooted
+ *                     at s, and the fold along the tree path to v is key[v].
+ *   first_hop[s][v] = the node after s on that tree path (v itself when
+ *                     pred[s][v] == s); first_hop[s][s] = s.
+ * Both hold petgraph NodeIndex values, whatever the column order of `nodes`:
+ *   out_pred     [(i-row_begin)*n_nodes + j] = pred[nodes[i]][nodes[j]]
+ *   out_first_hop[(i-row_begin)*n_nodes + j] = first_hop[nodes[i]][nodes[j]]
+ *
+ * A tree spans every graph node, so the rows it is computed from must: n_nodes is
+ * the net's node count and `nodes` a permutation of 0 .. n_nodes-1.  A simulation
+ * with a used subset puts its used nodes first and takes rows [0, n_used): its
+ * used x used table is the leading n_used columns of those rows.
+ * The f32 fold is not associative: the rest of s's tree path from an
+ * intermediate node h need not be h's own tree path.  Expand a path inside one
+ * source's pred row (sg_tree_path), never first hop by first hop across rows.
+ *
+ * sg_routing_tree: rows [row_begin, row_end) of both outputs from the same rows
+ * of the table (latency_ns / packet_loss, row-major from row_begin, as
+ * sg_routing_build wrote them for the same `nodes`).  SG_ROUTE_OUT_DEVICE applies
+ * to inputs and outputs alike.  Either output may be NULL, not both.
+ * SG_ERR_INVALID_ARG, the outputs untouched, for n_nodes other than the net's node
+ * count, `nodes` not a permutation, a bad row range, NULL arguments.  A cell
+ * without a tight in-arc means the rows are not this graph's table:
+ * SG_ERR_INVALID_ARG with a message, sg_ctx_last_error_pair = the first such
+ * (row, col) in row-major order; the outputs are then undefined.  Synchronises.
+ * Row ranges shard across contexts exactly as the build's do.
+ *
+ * sg_routing_build_tree: sg_routing_build over those rows, then the tree pass;
+ * all four outputs are required.  The build's errors in the build's precedence;
+ * SG_ERR_INVALID_ARG (before anything is written) without SG_ROUTE_SHORTEST_PATH:
+ * direct paths have no tree. */
+int32_t sg_routing_tree(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_nodes,
+                        uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                        const uint64_t* latency_ns, const float* packet_loss,
+                        uint32_t* out_pred, uint32_t* out_first_hop);
+int32_t sg_routing_build_tree(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_nodes,
+                              uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                              uint64_t* out_latency_ns, float* out_packet_loss,
+                              uint32_t* out_pred, uint32_t* out_first_hop);
+/* Host only, no device: the node sequence src ... dst (petgraph indices) of the
+ * tree path, from one host pred row -- the row of source src, in the column
+ * order of `nodes` (NULL: the identity order).  *len = its length in nodes (1
+ * when src == dst).  SG_ERR_CAPACITY with *len set when cap is too small
+ * (nothing is written to out_path); SG_ERR_INVALID_ARG for src or dst out of
+ * range, `nodes` not a permutation, or a row that does not reach src within
+ * n_nodes steps: a garbage row ends, it never loops. */
+int32_t sg_tree_path(const uint32_t* pred_row, const uint32_t* nodes, uint32_t n_nodes, uint32_t src, uint32_t dst,
+                     uint32_t* out_path, uint32_t cap, uint32_t* len);
+
 /* ---- host-side dense RoutingInfo (graph/mod.rs:432-481) ------------------
  * RoutingInfo<u32> keyed by GML node id, as generate_routing_info builds it
  * (sim_config.rs:411-448), stored dense: row-major latency / loss arrays in

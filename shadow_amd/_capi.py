@@ -60,6 +60,7 @@ EXPORTED = [
     "sg_wire_push_records_padded",
     "sg_group_create", "sg_group_destroy", "sg_group_size", "sg_group_last_error", "sg_group_last_error_pair",
     "sg_group_routing_info_fill", "sg_group_exchange_padded", "sg_group_alltoallv_records",
+    "sg_routing_tree", "sg_routing_build_tree", "sg_tree_path",
 ]
 
 
@@ -223,6 +224,9 @@ def load(path: str | None = None):
         "sg_net_destroy": (None, [vp]),
         "sg_routing_build": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp]),
         "sg_routing_min_latency": (i32, [vp, vp, C.c_size_t, u64p]),
+        "sg_routing_tree": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
+        "sg_routing_build_tree": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
+        "sg_tree_path": (i32, [vp, vp, u32, u32, u32, vp, u32, u32p]),
         "sg_routing_info_create": (i32, [u32, vp, C.POINTER(vp)]),
         "sg_routing_info_destroy": (None, [vp]),
         "sg_routing_info_fill": (i32, [vp, vp, vp, u32, vp]),

@@ -108,6 +108,9 @@ struct sg_ctx {
   sg::DevBuf d_seg, d_dst, d_cnt, d_cur, d_keys, d_vals, d_keys2, d_vals2, d_keys3, d_keys4, d_misc,
       d_scan, d_lists, d_lists2, d_ctr0, d_blk, d_spill;
   sg::DevBuf m_scratch;
+  // shortest-path trees (sg_tree.hip): the node list and its inverse, the flag word, and the
+  // device rows of outputs the caller takes on the host or not at all
+  sg::DevBuf t_idx, t_flag, t_pred, t_fh;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

@@ -180,6 +180,70 @@ class PathTable:
             yield k, self[k]
 
 
+class PathTree:
+    """Shortest-path trees beside their table rows (sg_routing_build_tree).
+
+    `nodes` is a permutation of every graph node, the sources first; row i is source
+    nodes[i], column j is node nodes[j].  `latency_ns` / `packet_loss` are the full-width
+    rows [n_sources x n_nodes]; `pred` / `first_hop` hold petgraph node indices:
+    pred[i, j] = the node before nodes[j] on the path from nodes[i] (the smallest index
+    among the tight in-arcs), first_hop[i, j] = the node after nodes[i] on it.
+    The f32 loss fold is not associative, so a path is expanded inside its source's pred
+    row (`path`), never first hop by first hop across rows.
+    """
+
+    def __init__(self, graph: "NetworkGraph", nodes: np.ndarray, n_sources: int, latency_ns: np.ndarray,
+                 packet_loss: np.ndarray, pred: np.ndarray, first_hop: np.ndarray):
+        self._graph = graph
+        self.nodes = nodes
+        self.n_sources = int(n_sources)
+        self.index = {int(v): j for j, v in enumerate(nodes)}
+        self.latency_ns = latency_ns
+        self.packet_loss = packet_loss
+        self.pred = pred
+        self.first_hop = first_hop
+
+    def _row(self, src: int) -> int:
+        i = self.index.get(int(src))
+        if i is None or i >= self.n_sources:
+            raise KeyError(f"node {src} is not a source of this tree")
+        return i
+
+    def path(self, src: int, dst: int) -> List[int]:
+        """The node indices src ... dst of the tree path (sg_tree_path)."""
+        row = np.ascontiguousarray(self.pred[self._row(src)])
+        n = len(self.nodes)
+        out = np.empty(n, np.uint32)
+        ln = C.c_uint32()
+        rc = load().sg_tree_path(row.ctypes.data, self.nodes.ctypes.data, n, int(src), int(dst), out.ctypes.data, n,
+                                 C.byref(ln))
+        if rc != _capi.SG_OK:
+            raise ShadowGpuError(rc, f"sg_tree_path({src}, {dst}) failed with status {rc}")
+        return out[:ln.value].tolist()
+
+    def path_properties(self, src: int, dst: int) -> PathProperties:
+        """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
+        taking at each step any arc that is tight: one whose fold gives the table's cell of the
+        step's head, latency and loss bits.  Equals the table's cell for (src, dst); for
+        src == dst it is default(), not the self-loop the table's diagonal holds."""
+        i = self._row(src)
+        arcs = self._graph._arcs_between()
+        acc = DEFAULT_PATH
+        nodes = self.path(src, dst)
+        for u, v in zip(nodes[:-1], nodes[1:]):
+            j = self.index[v]
+            want = (int(self.latency_ns[i, j]), np.float32(self.packet_loss[i, j]).view(np.uint32))
+            for e in arcs.get((u, v), ()):
+                got = acc + PathProperties(int(self._graph.edge_latency_ns[e]), self._graph.edge_packet_loss[e])
+                if (got.latency_ns, np.float32(got.packet_loss).view(np.uint32)) == want:
+                    acc = got
+                    break
+            else:
+                raise ShadowGpuError(_capi.SG_ERR_INVALID_ARG, f"no tight arc {u} -> {v} on the path {src} -> {dst}",
+                                     (i, j))
+        return acc
+
+
 # ---------------------------------------------------------------------------
 # NetworkGraph (graph/mod.rs:113-294)
 # ---------------------------------------------------------------------------
@@ -334,6 +398,55 @@ class NetworkGraph:
         check(self.ctx.handle, L.sg_routing_build(self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used),
                                                   int(row_begin), int(row_end), flags, C.c_void_p(out_latency_ptr),
                                                   C.c_void_p(out_loss_ptr)))
+
+    # -- shortest-path trees -------------------------------------------------
+    def _arcs_between(self):
+        """(u, v) -> the edges that give an arc u -> v (self-loops left out), built once."""
+        if getattr(self, "_arc_index", None) is None:
+            idx: Dict[Tuple[int, int], List[int]] = {}
+            for e, (a, b) in enumerate(zip(self.edge_src.tolist(), self.edge_dst.tolist())):
+                if a == b:
+                    continue
+                idx.setdefault((a, b), []).append(e)
+                if not self.directed:
+                    idx.setdefault((b, a), []).append(e)
+            self._arc_index = idx
+        return self._arc_index
+
+    def tree_permutation(self, sources: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Every graph node once, `sources` first (in their order), the rest ascending."""
+        if sources is None:
+            return np.arange(self.n_nodes, dtype=np.uint32)
+        first = np.ascontiguousarray(sources, dtype=np.uint32)
+        rest = np.setdiff1d(np.arange(self.n_nodes, dtype=np.uint32), first)
+        return np.ascontiguousarray(np.concatenate([first, rest]), dtype=np.uint32)
+
+    def compute_shortest_path_tree(self, sources: Optional[Sequence[int]] = None) -> PathTree:
+        """compute_shortest_paths (graph/mod.rs:183-228) from `sources` (petgraph indices, default
+        all) to every graph node, with the predecessor and first-hop rows of those paths
+        (sg_routing_build_tree).  The sources come first in the result's node order, so its
+        leading len(sources) columns are compute_shortest_paths(sources)."""
+        nodes = self.tree_permutation(sources)
+        n, k = len(nodes), self.n_nodes if sources is None else len(sources)
+        lat = np.zeros((k, n), np.uint64)
+        loss = np.zeros((k, n), np.float32)
+        pred = np.zeros((k, n), np.uint32)
+        hop = np.zeros((k, n), np.uint32)
+        check(self.ctx.handle, load().sg_routing_build_tree(
+            self.ctx.handle, self._ensure_net(), nodes.ctypes.data, n, 0, k, _capi.SG_ROUTE_SHORTEST_PATH,
+            lat.ctypes.data, loss.ctypes.data, pred.ctypes.data, hop.ctypes.data))
+        return PathTree(self, nodes, k, lat, loss, pred, hop)
+
+    def tree_rows_device(self, nodes: Sequence[int], row_begin: int, row_end: int, latency_ptr: int, loss_ptr: int,
+                         out_pred_ptr: int, out_first_hop_ptr: int) -> None:
+        """Rows [row_begin, row_end) of pred / first_hop from the same rows of a device table
+        (as build_rows_device wrote them for the same `nodes`, a permutation of every node), into
+        caller-owned device buffers; either output pointer may be 0 (sg_routing_tree)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        check(self.ctx.handle, load().sg_routing_tree(
+            self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used), int(row_begin), int(row_end),
+            _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(latency_ptr), C.c_void_p(loss_ptr),
+            C.c_void_p(out_pred_ptr or None), C.c_void_p(out_first_hop_ptr or None)))
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

@@ -1,9 +1,12 @@
-// sg_lanes.h -- what the lane-per-host kernels share (sg_codel.hip: the routers' CoDel queues,
-// the inbound relay, the outbound pipeline's fifo interface; sg_qdisc.hip: its round-robin
-// interface): the block shape, the two chunk layouts, the relay's token bucket, the per-block
-// sums' prefix, and the outbound object.  Each translation unit gets its own copy of the device
-// code (an unnamed namespace).
+// sg_lanes.h -- what the lane-per-host kernels share (sg_codel.hip: the routers' CoDel queues;
+// sg_inbound.hip: the inbound relay; sg_outbound.hip: the outbound pipeline's fifo interface;
+// sg_qdisc.hip: its round-robin interface): the block shape, the contiguous chunk's staging, the
+// two chunk layouts, the relay's token bucket, the per-block sums and their prefix, the outbound
+// object, and the launch's choice of layout.  Each translation unit gets its own copy of the
+// device code (an unnamed namespace).
 #pragma once
+
+#include <type_traits>
 
 #include "sg_device.h"
 #include "sg_internal.h"
@@ -34,6 +37,28 @@ constexpr int CD_HOSTS = 64;
 constexpr int CD_CHUNK = 1024;
 constexpr int CD_OUT_CHUNK = 896;  // k_outbound: 24 B per send, 21 KB, 7 blocks per CU
 static_assert(CD_THREADS == CD_HOSTS, "a block is its walkers");
+
+// s_waitcnt vmcnt(0) as the immediate of __builtin_amdgcn_s_waitcnt (gfx9: lgkmcnt and expcnt
+// left at their maxima)
+constexpr int VMCNT0 = 0x0F70;
+
+// Chunk [c0, c1) staged by the block: ld(i, u) loads element i into slot u of
+// the lane's registers, st(k, u) stores slot u to LDS index k.  Indices past
+// c1 load element c1 - 1 (always valid, unconditional loads: no branch for the
+// compiler to drain each load at) and are not stored.
+template <typename LD, typename ST>
+__device__ __forceinline__ void stage_chunk(uint32_t c0, uint32_t c1, LD&& ld, ST&& st) {
+  const uint32_t t = threadIdx.x;
+  for (uint32_t base = c0; base < c1; base += CD_THREADS * CD_UNROLL) {
+#pragma unroll
+    for (int u = 0; u < CD_UNROLL; u++) ld(min(base + u * CD_THREADS + t, c1 - 1), u);
+#pragma unroll
+    for (int u = 0; u < CD_UNROLL; u++) {
+      const uint32_t i = base + u * CD_THREADS + t;
+      if (i < c1) st(i - c0, u);
+    }
+  }
+}
 
 // A block's events in chunks of CH LDS positions.  Contiguous: chunk c is the
 // block's events [p0 + c CH, ...), the hosts in order -- at C4 (~20 events per
@@ -225,11 +250,42 @@ struct Relay {
 // k_outbound / k_qdisc: a host's sends out of execution order
 enum : uint32_t { E_ORDER = 128 };
 
+// Sums the blocks' drop counts, ORs their error flags (and the grouping
+// check's) into the pinned host-mapped return block.  (Not every file that includes this
+// header launches it, nor k_blk_offsets: hence [[maybe_unused]].)
+[[maybe_unused]] __global__ void __launch_bounds__(1024) k_codel_reduce(const unsigned long long* __restrict__ blk, uint32_t n,
+                                                       const uint32_t* __restrict__ group_err,
+                                                       unsigned long long* __restrict__ ret) {
+  __shared__ unsigned long long r[2][16];
+  unsigned long long d = 0, e = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += 1024) {
+    d += blk[2 * i];
+    e |= blk[2 * i + 1];
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    d += __shfl_xor(d, s, 64);
+    e |= __shfl_xor(e, s, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    r[0][threadIdx.x >> 6] = d;
+    r[1][threadIdx.x >> 6] = e;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 16; i++) {
+      d += r[0][i];
+      e |= r[1][i];
+    }
+    ret[0] = d;
+    ret[1] = e | *group_err;
+  }
+}
+
 // Exclusive prefix of the k_outbound blocks' sent counts (blk[2b]) -> boff[b]:
 // where each block's slice of the sent batch starts; and k_codel_reduce's sums
 // (the total sent, the error flags) into the mapped return block, in the same
 // launch.  One block.
-__global__ void __launch_bounds__(1024) k_blk_offsets(const unsigned long long* __restrict__ blk, uint32_t nb,
+[[maybe_unused]] __global__ void __launch_bounds__(1024) k_blk_offsets(const unsigned long long* __restrict__ blk, uint32_t nb,
                                                       uint32_t* __restrict__ boff,
                                                       const uint32_t* __restrict__ group_err,
                                                       unsigned long long* __restrict__ ret) {
@@ -313,5 +369,13 @@ __host__ __device__ inline size_t qd_slot(uint32_t h, uint32_t s, uint32_t n_soc
 // diagnostic (SG_LANE_DIAG) of the lane kernels
 int lane_major_env();
 int lane_major_launch(int mode, size_t n_events, uint32_t nb, uint32_t ch);
+// lane_major_launch's result as a compile-time LM: f(std::integral_constant<int, LM>) launches the
+// kernel instantiated for it
+template <class F>
+inline void with_lane_mode(int lm, F&& f) {
+  if (lm == 2) f(std::integral_constant<int, 2>{});
+  else if (lm == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
 unsigned long long* lane_diag_alloc(uint32_t nb);
 void lane_diag_report(hipStream_t st, const char* name, unsigned long long* d, uint32_t nb);

@@ -8,7 +8,7 @@
 // (:227-259) takes the front socket and its oldest packet and pushes the socket to the back if
 // it still holds one.  The relay above it (relay/mod.rs:111-273) is k_outbound's.
 //
-// k_qdisc has k_outbound's shape (sg_codel.hip): one wave per block, one lane per host, the
+// k_qdisc has k_outbound's shape (sg_outbound.hip): one wave per block, one lane per host, the
 // block's sends staged through LDS in chunks of either layout (ChunkMap).  Per host:
 //   pool     `cap` record slots, bump-allocated (slot = top++).  ring_cap bounds the packets
 //            queued at a call's start plus the call's sends, so a pool that starts a call
@@ -40,9 +40,6 @@ constexpr uint32_t QD_LDS_SOCKETS = 16;
 // socket state (16 sockets x 64 hosts x (4 + 4 + 1) B) + 0.5 KB = 21.5 KB, 7 blocks per CU
 constexpr uint32_t QD_CHUNK = 384, QD_CHUNK_KEYED = 256;
 enum : uint32_t { E_SOCKET = 256 };
-// s_waitcnt vmcnt(0) as the immediate of __builtin_amdgcn_s_waitcnt (gfx9: lgkmcnt and expcnt
-// left at their maxima), as sg_codel.hip's
-constexpr int QD_VMCNT0 = 0x0F70;
 
 typedef __attribute__((address_space(3))) const uint4 lds_rec;
 typedef __attribute__((address_space(3))) uint32_t lds_link;
@@ -127,13 +124,13 @@ struct QdQ {
     // otherwise the wait lands where the two paths join and on every later use of the record,
     // and the walkers that read LDS wait there for the last forward's stores
     const uint4 r = pool[slot];
-    __builtin_amdgcn_s_waitcnt(QD_VMCNT0);
+    __builtin_amdgcn_s_waitcnt(VMCNT0);
     return r;
   }
   __device__ uint32_t next_at(uint32_t slot) const {
     if (in_window(slot)) return wn[wb + (slot - t0)];
     const uint32_t v = nxt[slot];
-    __builtin_amdgcn_s_waitcnt(QD_VMCNT0);
+    __builtin_amdgcn_s_waitcnt(VMCNT0);
     return v;
   }
   __device__ void load_front() {
@@ -206,7 +203,7 @@ struct QdQ {
   }
 };
 
-// The relay's forward task at `now` (out_task, sg_codel.hip), the round-robin interface as its
+// The relay's forward task at `now` (out_task, sg_outbound.hip), the round-robin interface as its
 // source; the records handed to the router go to the log.
 template <bool SL>
 __device__ void qd_task(QdQ<SL>& q, Relay& r, uint64_t now, const QdiscArgs& a, uint64_t& ctr_inc) {

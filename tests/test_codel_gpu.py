@@ -5,6 +5,7 @@ packet statuses and the whole per-host state, across consecutive calls."""
 import numpy as np
 import pytest
 
+import lane_cases
 from shadow_amd import ShadowGpuError, _capi
 from shadow_amd.router import CoDelEvents, CoDelQueues
 
@@ -80,7 +81,7 @@ def test_reference_drop_many_sequence(oracle, ctx):
                                                   (1, 0.3, "1")])
 def test_random_streams_over_calls(oracle, ctx, monkeypatch, gap_ms, p_pop, layout):
     """500 hosts, three consecutive calls of 60k events: state carries over.  ~120 events
-    per host: the blocks take lane-major chunks by default (sg_codel.hip ChunkMap); layout
+    per host: the blocks take lane-major chunks by default (sg_lanes.h ChunkMap); layout
     forces contiguous ("0") or lane-major ("1") chunks."""
     if layout:
         monkeypatch.setenv("SG_LANE_MAJOR", layout)
@@ -96,6 +97,33 @@ def test_random_streams_over_calls(oracle, ctx, monkeypatch, gap_ms, p_pop, layo
         t0 = int(ev[2].max()) + 1
     _same_state(oracle, q.get_state(), os_)
     assert (ostat == 2).any() and (ostat == 1).any()
+
+
+@pytest.mark.parametrize("layout", lane_cases.LAYOUTS)
+def test_layout_matrix(oracle, ctx, monkeypatch, layout):
+    """k_codel's four walk sites on one small shape (lane_cases.py: 128 hosts, 64 x 48 events,
+    one host of 3,000, two of 3; E = 6,078).  CH = 1,024, LK = 16: unset launches LM = 2 (6,078 >
+    2 x 1,024 x 2 = 4,096), where block 0 goes lane-major (3 x (10 + 16) = 78 against 3 x (10 + 48)
+    = 174) and block 1 stays contiguous (188 x 26 = 4,888 against 3 x (10 + 1,002) = 3,036); "0"
+    launches LM = 0 and "1" LM = 1.  Two calls (state carries over), drawn as _stream draws them."""
+    lane_cases.set_layout(monkeypatch, layout)
+    rng = np.random.default_rng(31)
+    host = lane_cases.host_column()
+    H, E = lane_cases.H, len(host)
+    q = CoDelQueues(H, lane_cases.RING_CAP, ctx=ctx)
+    os_ = oracle.codel_state(H, q.cap)
+    gstat, ostat = _status(2 * E), np.zeros(2 * E, np.uint8)
+    t0 = T0 + 10**9
+    for c in range(2):
+        kind = (rng.random(E) < 0.45).astype(np.uint8)
+        t = _host_times(host, rng.integers(0, 3 * MS, E), t0)
+        pkt = (c * E + np.arange(E)).astype(np.uint32)
+        ln = rng.integers(40, 1500, E).astype(np.uint32)
+        _run_both(oracle, q, os_, gstat, ostat, host, kind, t, pkt, ln)
+        _same_state(oracle, q.get_state(), os_)
+        t0 = int(t.max()) + 1
+    assert (ostat == 2).any() and (ostat == 1).any()
+    assert (os_["tail"] != os_["head"]).any()  # live ring slots were compared
 
 
 @pytest.mark.parametrize("layout", ["", "1"])

@@ -5,6 +5,7 @@ over consecutive windows (pending forward tasks carry over)."""
 import numpy as np
 import pytest
 
+import lane_cases
 from shadow_amd import ShadowGpuError, _capi
 from shadow_amd.router import InboundPipeline
 
@@ -82,7 +83,7 @@ def _same(O, got, want):
 def test_windows_match_oracle(oracle, ctx, monkeypatch, bw_mbit, boot_ms, layout, ordered):
     """300 hosts, 5 windows of 60 ms, 60k arrivals: from unthrottled to heavily
     throttled (standing queues, CoDel drop mode, tasks pending across windows).  ~40
-    arrivals per host: lane-major chunks by default (sg_codel.hip ChunkMap); layout "0"
+    arrivals per host: lane-major chunks by default (sg_lanes.h ChunkMap); layout "0"
     forces contiguous ones.  ordered: sg_inbound_run_ordered (fates in arrival order;
     packets carried from earlier windows by id), the queued rings checked too."""
     import torch
@@ -159,9 +160,10 @@ def test_arrival_after_window_rejected(ctx):
     assert e.value.code == _capi.SG_ERR_INVALID_ARG
 
 
-def _run_windows(oracle, ctx, bw, cap, windows, boot, sim_end=T0 + 10**12, ordered=False):
+def _run_windows(oracle, ctx, bw, cap, windows, boot, sim_end=T0 + 10**12, ordered=False, ring=False):
     """Consecutive windows (host, t, ln, window_end) on the GPU and the oracle,
-    everything compared after each (statuses, forward times, counters, state, ids)."""
+    everything compared after each (statuses, forward times, counters, state, ids; the
+    queued ring slots too for an ordered call or with `ring`)."""
     import torch
 
     H = len(bw)
@@ -185,11 +187,38 @@ def _run_windows(oracle, ctx, bw, cap, windows, boot, sim_end=T0 + 10**12, order
         assert np.array_equal(ctr_g.cpu().numpy().view(np.uint64), ctr_o)
         got = ib.get_state()
         _same(oracle, got, ost)
-        if ordered:
+        if ordered or ring:
             _live_ring_same(got, ost)
         for k in ("task_id", "task_born"):
             assert np.array_equal(got[k], ost[k]), k
     return st_o, ost
+
+
+@pytest.mark.parametrize("layout", lane_cases.LAYOUTS)
+@pytest.mark.parametrize("ordered", [False, True])
+def test_layout_matrix(oracle, ctx, monkeypatch, ordered, layout):
+    """k_inbound's four walk sites, plain and ordered, on one small shape (lane_cases.py: 128
+    hosts, 64 x 48 arrivals, one host of 3,000, two of 3; E = 6,078).  CH = 1,024, LK = 16: unset
+    launches LM = 2 (6,078 > 2 x 1,024 x 2 = 4,096), where block 0 goes lane-major (3 x (10 + 16)
+    = 78 against 3 x (10 + 48) = 174) and block 1 stays contiguous (188 x 26 = 4,888 against
+    3 x (10 + 1,002) = 3,036); "0" launches LM = 0 and "1" LM = 1.  Two windows of 60 ms, drawn
+    as _arrivals draws them; 1 Mbit/s relays (200 Mbit/s at the long host: ~2.1 MB arrive per
+    window and ~1.5 MB pass), so queues stand, CoDel drops and tasks stay pending."""
+    lane_cases.set_layout(monkeypatch, layout)
+    rng = np.random.default_rng(43)
+    host = lane_cases.host_column()
+    bw = np.full(lane_cases.H, 10**6, np.uint64)
+    bw[64] = 200 * 10**6
+    windows = []
+    for w in range(2):
+        t0, t1 = T0 + w * 60 * MS, T0 + (w + 1) * 60 * MS
+        t = rng.integers(t0, t1, len(host)).astype(np.uint64)
+        t = t[np.lexsort((t, host))]  # per host ascending time
+        ln = rng.choice(np.array([28, 1476, 600], np.uint32), len(host))
+        windows.append((host, t, ln, t1))
+    st_o, ost = _run_windows(oracle, ctx, bw, lane_cases.RING_CAP, windows, boot=0, ordered=ordered, ring=True)
+    assert (st_o == 1).any() and (st_o == 2).any() and (st_o == 0).any()
+    assert (ost["rflags"] & oracle.RL_PENDING).any() and (ost["tail"] != ost["head"]).any()
 
 
 @pytest.mark.parametrize("ordered", [False, True])

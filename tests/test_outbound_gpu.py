@@ -7,6 +7,7 @@ runs through sg_deliver_round like any round's packets."""
 import numpy as np
 import pytest
 
+import lane_cases
 from shadow_amd import ShadowGpuError, _capi, synth
 from shadow_amd.router import OutboundPipeline
 from shadow_amd.worker import DeviceTable, HostTable, deliver_round
@@ -23,8 +24,10 @@ def _dev(a, np_dtype, torch_dtype):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype).view(torch_dtype)).cuda()
 
 
-def _sends(hosts, n, t0, t1, seed, p_local=0.05):
+def _sends(hosts, n, t0, t1, seed, p_local=0.05, src=None):
     pk = synth.make_packets(n, hosts, t0, t1, seed=seed)
+    if src is not None:  # a given host column (grouped by host) instead of the drawn one
+        pk["src"], pk["send_time"] = src, pk["send_time"][np.lexsort((pk["send_time"], src))]
     rng = np.random.default_rng(seed + 1000)
     loc = rng.random(n) < p_local
     dst = np.where(loc, hosts["ip"][pk["src"]], pk["dst_ip"]).astype(np.uint32)
@@ -49,7 +52,7 @@ def _live_same(got, want):
 def test_windows_match_oracle(oracle, ctx, monkeypatch, bw_mbit, boot_ms, layout):
     """2000 hosts, 5 windows of 2 ms, 40k sends each: unthrottled to heavily throttled
     (queues and cached packets carried across windows, tasks pending).  layout "1" forces
-    lane-major chunks (sg_codel.hip ChunkMap; ~20 sends per host take contiguous ones)."""
+    lane-major chunks (sg_lanes.h ChunkMap; ~20 sends per host take contiguous ones)."""
     import torch
 
     if layout:
@@ -97,12 +100,12 @@ def test_windows_match_oracle(oracle, ctx, monkeypatch, bw_mbit, boot_ms, layout
         assert (st_o == 0).any() and (ost["rflags"] & oracle.RL_PENDING).any() and total < n_pk
 
 
-def _keyed_sends(hosts, n, t0, t1, seed):
+def _keyed_sends(hosts, n, t0, t1, seed, src=None):
     """Sends of which half land exactly on a refill boundary (T0 + k ms, where a blocked
     relay's wake-up falls), each made by a random event: a Packet event (id UINT64_MAX) or a
     Local one created up to 3 ms earlier with a random id.  Per (host, time) the sends are put
     in execution order: Packet events first, then Local ones by (created, id)."""
-    host, t, ln, pay, dst = _sends(hosts, n, t0, t1, seed)
+    host, t, ln, pay, dst = _sends(hosts, n, t0, t1, seed, src=src)
     rng = np.random.default_rng(seed + 7)
     snap = rng.random(n) < 0.5
     t = np.where(snap, (t - T0) // MS * MS + T0, t).astype(np.uint64)
@@ -169,6 +172,70 @@ def test_same_time_ties_match_oracle(oracle, ctx, monkeypatch, bw_mbit, layout):
                                 event_id=eid, event_created=b2)
     for k in alt:  # the ties went both ways
         assert not np.array_equal(ctr_alt[k], ctr_o), k
+
+
+@pytest.mark.parametrize("layout", lane_cases.LAYOUTS)
+@pytest.mark.parametrize("keyed", [False, True])
+def test_layout_matrix(oracle, ctx, monkeypatch, keyed, layout):
+    """k_outbound's four walk sites, unkeyed and keyed, on one small shape (lane_cases.py: 128
+    hosts, 64 x 48 sends, one host of 3,000, two of 3; E = 6,078).  CH = 896 (keyed 512), LK = 14
+    (8): unset launches LM = 2 (6,078 > 2 CH x 2 = 3,584 (2,048)), where block 0 goes lane-major
+    (4 x (10 + 14) = 96 against 4 x (10 + 48) = 232; keyed 6 x 18 = 108 against 6 x 58 = 348) and
+    block 1 stays contiguous (215 x 24 = 5,160 against 4 x (10 + 896) = 3,624; keyed 375 x 18 =
+    6,750 against 6 x (10 + 512) = 3,132); "0" launches LM = 0 and "1" LM = 1.  Two windows of
+    60 ms, drawn as _sends / _keyed_sends draw them; 2 Mbit/s relays (400 Mbit/s at the long host:
+    ~3.6 MB sent per window and ~3 MB pass), so packets stay queued and cached and tasks pending."""
+    import torch
+
+    lane_cases.set_layout(monkeypatch, layout)
+    H, W = lane_cases.H, 60 * MS
+    src = lane_cases.host_column()
+    per = len(src)
+    hosts = synth.make_hosts(H, 64, exact_seeds=False)
+    bw = np.full(H, 2 * 10**6, np.uint64)
+    bw[64] = 400 * 10**6
+    ob = OutboundPipeline(hosts["ip"], bw, lane_cases.RING_CAP, ctx=ctx)
+    ost = oracle.outbound_state(hosts["ip"], bw, ob.cap)
+    n_pk = 2 * per
+    fwd_g = torch.full((n_pk,), -1, dtype=torch.int64, device="cuda")
+    st_g = torch.zeros(n_pk, dtype=torch.uint8, device="cuda")
+    ctr_g = torch.zeros(H, dtype=torch.int64, device="cuda")
+    fwd_o, st_o, ctr_o = np.full(n_pk, np.uint64(2**64 - 1)), np.zeros(n_pk, np.uint8), np.zeros(H, np.uint64)
+    sim_end = T0 + 10**12
+    total = 0
+    for w in range(2):
+        t0, t1 = T0 + w * W, T0 + (w + 1) * W
+        gkeys, okeys = {}, {}
+        if keyed:
+            host, t, ln, pay, dst, eid, born = _keyed_sends(hosts, per, t0, t1, seed=70 + w, src=src)
+            gkeys = dict(event_id=_dev(eid, np.uint64, np.int64), event_created_ns=_dev(born, np.uint64, np.int64))
+            okeys = dict(event_id=eid, event_created=born)
+        else:
+            host, t, ln, pay, dst = _sends(hosts, per, t0, t1, seed=70 + w, src=src)
+        assert np.array_equal(host, src)
+        pkt = np.arange(w * per, (w + 1) * per, dtype=np.uint32)
+        batch, ids = ob.run(_dev(host, np.uint32, np.int32), _dev(t, np.uint64, np.int64),
+                            _dev(pkt, np.uint32, np.int32), _dev(ln, np.uint32, np.int32),
+                            _dev(pay, np.uint32, np.int32), _dev(dst, np.uint32, np.int32), t1, 0, sim_end,
+                            fwd_g, st_g, ctr_g.data_ptr(), **gkeys)
+        want = oracle.outbound_run(ost, host, t, pkt, ln, pay, dst, t1, 0, sim_end, ctr_o, fwd_o, st_o, **okeys)
+        assert np.array_equal(st_g.cpu().numpy(), st_o)
+        m = st_o != 0
+        assert np.array_equal(fwd_g.cpu().numpy().view(np.uint64)[m], fwd_o[m])
+        assert np.array_equal(ctr_g.cpu().numpy().view(np.uint64), ctr_o)
+        assert len(batch) == len(want["packet"])
+        assert np.array_equal(batch.src_host.cpu().numpy().view(np.uint32), want["src_host"])
+        assert np.array_equal(batch.dst_ipv4.cpu().numpy().view(np.uint32), want["dst_ipv4"])
+        assert np.array_equal(batch.payload_len.cpu().numpy().view(np.uint32), want["payload_len"])
+        assert np.array_equal(batch.send_time_ns.cpu().numpy().view(np.uint64), want["send_time"])
+        assert np.array_equal(ids.cpu().numpy().view(np.uint32), want["packet"])
+        got = ob.get_state()
+        for k in RKEYS:
+            assert np.array_equal(got[k], ost[k]), k
+        _live_same(got, ost)
+        total += len(want["packet"])
+    assert (st_o == 1).any() and (st_o == 2).any() and (st_o == 0).any() and total < n_pk
+    assert (ost["rflags"] & oracle.RL_PENDING).any() and (ost["rflags"] & 4).any()  # pending, cached
 
 
 def test_keyed_send_errors(ctx):

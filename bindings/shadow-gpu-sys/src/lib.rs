@@ -449,6 +449,17 @@ unsafe extern "C" {
     pub fn sg_tree_path(pred_row: *const u32, nodes: *const u32, n_nodes: u32, src: u32, dst: u32,
                         out_path: *mut u32, cap: u32, len: *mut u32) -> i32;
 
+    // ---- link loads: a per-pair u64 matrix folded onto the graph's links through pred rows ----
+    /// The link list (distinct ordered node pairs joined by an edge), ascending (head, tail).
+    pub fn sg_net_links(ctx: *mut sg_ctx, net: *mut sg_net, n_links: *mut u32, out_tail: *mut u32,
+                        out_head: *mut u32, cap: u32) -> i32;
+    /// Each edge's link numbers: (src -> dst), and (dst -> src) or u32::MAX on a directed graph.
+    pub fn sg_net_edge_links(ctx: *mut sg_ctx, net: *mut sg_net, out_fwd: *mut u32, out_rev: *mut u32) -> i32;
+    /// Adds rows [row_begin, row_end) of `counts` onto the links and nodes of their tree paths.
+    pub fn sg_link_load(ctx: *mut sg_ctx, net: *mut sg_net, nodes: *const u32, n_nodes: u32, row_begin: u32,
+                        row_end: u32, flags: u32, pred: *const u32, counts: *const u64, count_cols: u32,
+                        out_link_load: *mut u64, out_node_load: *mut u64) -> i32;
+
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;
     pub fn sg_routing_info_destroy(ri: *mut sg_routing_info);

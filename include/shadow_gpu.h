@@ -223,6 +223,66 @@ int32_t sg_routing_build_tree(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, u
 int32_t sg_tree_path(const uint32_t* pred_row, const uint32_t* nodes, uint32_t n_nodes, uint32_t src, uint32_t dst,
                      uint32_t* out_path, uint32_t cap, uint32_t* len);
 
+/* ---- link loads: per-pair counters folded onto graph links (additive to ABI 7) --
+ * How much crossed each link: a u64 matrix per (source row, destination column)
+ * -- the packet counters of sg_ctx_set_packet_counters, or bytes a caller
+ * accumulates -- attributed to the links of each cell's tree path through the
+ * pred rows of sg_routing_tree.  Exact (integer adds only) and independent of
+ * order; the delivery round itself is not touched.
+ *
+ * A link is a distinct ordered node pair (u, v) joined by at least one edge: an
+ * undirected edge {a, b} gives (a, b) and (b, a), a directed edge one link, a
+ * self-loop (a, a).  Parallel edges between one pair are ONE link (pred is
+ * defined by node).  Link order: ascending (head v, tail u), so the links into
+ * one node are contiguous.
+ *
+ * sg_net_links: the link list to host arrays; *n_links is always set.
+ * SG_ERR_CAPACITY, nothing written, when cap < *n_links.  Built once per net on
+ * first use (a device-to-host copy of the edge list and a host sort).
+ * sg_net_edge_links: host arrays of n_edges entries; out_fwd[e] = the link of
+ * edge e as (src -> dst), out_rev[e] = the link (dst -> src) on an undirected
+ * graph, UINT32_MAX on a directed one; for a self-loop both name the same link.
+ * Parallel edges share their link's number: load_of_edge[e] =
+ * link_load[out_fwd[e]] (+ link_load[out_rev[e]]) is the pair's load.
+ *
+ * sg_link_load: rows [row_begin, row_end), row i of source s = nodes[i]; `pred`
+ * (as sg_routing_tree writes it: petgraph indices, columns in `nodes` order) and
+ * `counts` (u64, count_cols <= n_nodes columns; columns at or past count_cols
+ * count zero) are row-major from row_begin.  With sub_i[v] = the sum of
+ * counts[i][j] over the columns j != i whose node nodes[j] lies in v's subtree of
+ * row i's tree, v included:
+ *   out_link_load[link (pred_i[v], v)] += sub_i[v]      for every v != s
+ *   out_link_load[link (s, s)]         += counts[i][i]  (the diagonal cell's path
+ *                                          is the self-loop, get_edge_weight's rule)
+ *   out_node_load[v]                   += sub_i[v]      for v != s: what arrives at
+ *                                          or passes through v
+ * out_link_load has *n_links entries in link order, out_node_load n_nodes entries
+ * by petgraph index.  All sums are u64 and WRAP on overflow.  They are ADDED to
+ * what the arrays hold: the caller zeroes them, and row blocks, group members and
+ * successive measurement intervals sum into one array.  Either output may be
+ * NULL, not both.  SG_ROUTE_OUT_DEVICE applies to pred, counts and both outputs
+ * alike.  `nodes` is a permutation of 0 .. n_nodes-1, as for the tree; a
+ * simulation with a used subset puts its used nodes first and passes count_cols =
+ * n_used when its delivery table is n_used wide.  Synchronises once.
+ * SG_ERR_INVALID_ARG, the outputs untouched, for NULL arguments, a bad row range,
+ * n_nodes other than the net's, `nodes` not a permutation, count_cols > n_nodes,
+ * both outputs NULL.  SG_ERR_INVALID_ARG with a message and
+ * sg_ctx_last_error_pair = the first (row, col) in row-major order, the outputs
+ * then undefined, for a pred row that holds a value >= n_nodes, does not have
+ * pred[s] == s, names a pair that is not a link, or leaves nodes unreleased (a
+ * cycle: not a tree); never a trap, never a loop.  Within one row the first two
+ * kinds are reported ahead of the others.  A row whose counters are all zero is
+ * skipped: its pred row is not validated.  A node whose subtree sum is zero is
+ * not looked up: a pair that is not a link is reported only where traffic
+ * crosses it. */
+int32_t sg_net_links(sg_ctx* ctx, sg_net* net, uint32_t* n_links, uint32_t* out_tail, uint32_t* out_head,
+                     uint32_t cap);
+int32_t sg_net_edge_links(sg_ctx* ctx, sg_net* net, uint32_t* out_fwd, uint32_t* out_rev);
+int32_t sg_link_load(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_nodes,
+                     uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                     const uint32_t* pred, const uint64_t* counts, uint32_t count_cols,
+                     uint64_t* out_link_load, uint64_t* out_node_load);
+
 /* ---- host-side dense RoutingInfo (graph/mod.rs:432-481) ------------------
  * RoutingInfo<u32> keyed by GML node id, as generate_routing_info builds it
  * (sim_config.rs:411-448), stored dense: row-major latency / loss arrays in

@@ -4,7 +4,9 @@ Two stages of Shadow's network core run as HIP kernels for gfx950 behind the
 C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 
 * routing-table build (NetworkGraph::compute_shortest_paths / get_direct_paths,
-  src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`;
+  src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`, with the paths' trees
+  (`graph.PathTree`) and the traffic they carried per link (`PathTree.link_load`,
+  `NetworkGraph.links`);
 * per-round packet delivery (Worker::send_packet, src/main/core/worker.rs:322-397)
   -> `worker.deliver_round`;
 * the packets in flight between a delivery round and their arrival (the per-host

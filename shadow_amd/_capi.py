@@ -61,6 +61,7 @@ EXPORTED = [
     "sg_group_create", "sg_group_destroy", "sg_group_size", "sg_group_last_error", "sg_group_last_error_pair",
     "sg_group_routing_info_fill", "sg_group_exchange_padded", "sg_group_alltoallv_records",
     "sg_routing_tree", "sg_routing_build_tree", "sg_tree_path",
+    "sg_net_links", "sg_net_edge_links", "sg_link_load",
 ]
 
 
@@ -227,6 +228,9 @@ def load(path: str | None = None):
         "sg_routing_tree": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
         "sg_routing_build_tree": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
         "sg_tree_path": (i32, [vp, vp, u32, u32, u32, vp, u32, u32p]),
+        "sg_net_links": (i32, [vp, vp, u32p, vp, vp, u32]),
+        "sg_net_edge_links": (i32, [vp, vp, vp, vp]),
+        "sg_link_load": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, u32, vp, vp]),
         "sg_routing_info_create": (i32, [u32, vp, C.POINTER(vp)]),
         "sg_routing_info_destroy": (None, [vp]),
         "sg_routing_info_fill": (i32, [vp, vp, vp, u32, vp]),

@@ -111,6 +111,9 @@ struct sg_ctx {
   // shortest-path trees (sg_tree.hip): the node list and its inverse, the flag word, and the
   // device rows of outputs the caller takes on the host or not at all
   sg::DevBuf t_idx, t_flag, t_pred, t_fh;
+  // link loads (sg_link.hip): the node list and its inverse, the flag words, the device copies of
+  // host inputs and outputs, and the global path's per-workgroup rows
+  sg::DevBuf l_idx, l_flag, l_pred, l_cnt, l_link, l_node, l_scratch;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];
@@ -214,8 +217,18 @@ struct sg_net {
   uint32_t* self_edge = nullptr;
   void* mem = nullptr;  // one device block holding every array above (from the context's pool)
   size_t mem_bytes = 0;
+  // links (sg_link.hip ensure_links, on first use): the distinct ordered node pairs joined by an
+  // edge, ascending (head, tail).  Host: the list and each edge's link numbers; device (lk_mem, a
+  // block of its own): lk_off[n_nodes + 1] by head, lk_tail[n_links]
+  bool links = false;
+  uint32_t n_links = 0;
+  std::vector<uint32_t> lk_tail_h, lk_head_h, e_fwd, e_rev;
+  uint32_t* lk_off = nullptr;
+  uint32_t* lk_tail = nullptr;
+  void* lk_mem = nullptr;
   ~sg_net() {
     if (mem) (void)hipFree(mem);  // (sg_net_destroy hands it back to the pool instead)
+    if (lk_mem) (void)hipFree(lk_mem);
   }
 };
 
@@ -431,6 +444,8 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l);
 // only); a node's GML id as text, for error messages; two zero fills as one launch on the
 // context stream
 void ensure_csc(sg_ctx* ctx, sg_net* net);
+// sg_link.hip: the net's link list (sg_net::lk_*), built on its first use
+void ensure_links(sg_ctx* ctx, sg_net* net);
 std::string node_name(const sg_net* net, uint32_t idx);
 void launch_zero2(sg_ctx* ctx, uint32_t* a, uint32_t na, uint32_t* b, uint32_t nb);
 

@@ -221,6 +221,25 @@ class PathTree:
             raise ShadowGpuError(rc, f"sg_tree_path({src}, {dst}) failed with status {rc}")
         return out[:ln.value].tolist()
 
+    def link_load(self, counts) -> Tuple[np.ndarray, np.ndarray]:
+        """(link_load, node_load), both u64, of a host matrix counts[i, j] = what source nodes[i]
+        sent to nodes[j] (n_sources rows, up to n_nodes columns; missing columns count zero):
+        every cell added to each link of its tree path (in NetworkGraph.links() order) and to
+        each node the path reaches after the source; a diagonal cell goes to its node's
+        self-loop link (sg_link_load)."""
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        n = len(self.nodes)
+        if c.ndim != 2 or c.shape[0] != self.n_sources or c.shape[1] > n:
+            raise ValueError(f"counts: {self.n_sources} rows of at most {n} columns")
+        g = self._graph
+        n_links = len(g.links()[0])
+        link, node = np.zeros(n_links, np.uint64), np.zeros(n, np.uint64)
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        check(g.ctx.handle, load().sg_link_load(
+            g.ctx.handle, g._ensure_net(), self.nodes.ctypes.data, n, 0, self.n_sources, 0, pred.ctypes.data,
+            c.ctypes.data, c.shape[1], link.ctypes.data, node.ctypes.data))
+        return link, node
+
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
         taking at each step any arc that is tight: one whose fold gives the table's cell of the
@@ -447,6 +466,42 @@ class NetworkGraph:
             self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used), int(row_begin), int(row_end),
             _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(latency_ptr), C.c_void_p(loss_ptr),
             C.c_void_p(out_pred_ptr or None), C.c_void_p(out_first_hop_ptr or None)))
+
+    # -- link loads -----------------------------------------------------------
+    def links(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(tail, head) of every link: the distinct ordered node pairs joined by an edge (an
+        undirected edge gives both directions, parallel edges one link), ascending (head, tail)
+        (sg_net_links).  link_load arrays are in this order."""
+        L, n = load(), C.c_uint32()
+        net = self._ensure_net()
+        rc = L.sg_net_links(self.ctx.handle, net, C.byref(n), None, None, 0)
+        if rc not in (_capi.SG_OK, _capi.SG_ERR_CAPACITY):
+            check(self.ctx.handle, rc)
+        tail, head = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        check(self.ctx.handle, L.sg_net_links(self.ctx.handle, net, C.byref(n), tail.ctypes.data, head.ctypes.data,
+                                              n.value))
+        return tail, head
+
+    def edge_links(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(fwd, rev): per edge, the link (src -> dst) and the link (dst -> src), the latter
+        0xFFFFFFFF on a directed graph (sg_net_edge_links).  Parallel edges share a link."""
+        m = len(self.edge_src)
+        fwd, rev = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        check(self.ctx.handle, load().sg_net_edge_links(self.ctx.handle, self._ensure_net(), fwd.ctypes.data,
+                                                        rev.ctypes.data))
+        return fwd, rev
+
+    def link_load_device(self, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int, counts_ptr: int,
+                         count_cols: int, link_ptr: int, node_ptr: int) -> None:
+        """Rows [row_begin, row_end) of a device u64 matrix (count_cols columns) added onto the
+        links and nodes of their tree paths through the same rows of device pred rows (as
+        tree_rows_device wrote them for the same `nodes`); the device outputs (u64, one per
+        link in links() order / one per node) are added to, and either may be 0 (sg_link_load)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        check(self.ctx.handle, load().sg_link_load(
+            self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used), int(row_begin), int(row_end),
+            _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(counts_ptr or None), int(count_cols),
+            C.c_void_p(link_ptr or None), C.c_void_p(node_ptr or None)))
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

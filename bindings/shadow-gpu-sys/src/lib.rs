@@ -459,6 +459,12 @@ unsafe extern "C" {
     pub fn sg_link_load(ctx: *mut sg_ctx, net: *mut sg_net, nodes: *const u32, n_nodes: u32, row_begin: u32,
                         row_end: u32, flags: u32, pred: *const u32, counts: *const u64, count_cols: u32,
                         out_link_load: *mut u64, out_node_load: *mut u64) -> i32;
+    /// The same sums from one round's batch: every counted packet walks its tree path, adding its
+    /// weight (1 when `weight` is null) to each link and node on it; `out_hops[p]` = its hop count.
+    pub fn sg_link_load_packets(ctx: *mut sg_ctx, net: *mut sg_net, hosts: *mut sg_hosts, nodes: *const u32,
+                                n_nodes: u32, row_begin: u32, row_end: u32, flags: u32, pred: *const u32,
+                                packets: *const sg_packets, status: *const u8, weight: *const u32,
+                                out_link_load: *mut u64, out_node_load: *mut u64, out_hops: *mut u32) -> i32;
 
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;

@@ -274,7 +274,12 @@ int32_t sg_tree_path(const uint32_t* pred_row, const uint32_t* nodes, uint32_t n
  * kinds are reported ahead of the others.  A row whose counters are all zero is
  * skipped: its pred row is not validated.  A node whose subtree sum is zero is
  * not looked up: a pair that is not a link is reported only where traffic
- * crosses it. */
+ * crosses it.
+ *
+ * sg_link_load_packets gives the same sums straight from one round's batch,
+ * without the counter matrix and with a weight per packet; it takes the
+ * delivery types, so it is declared after them ("link loads from a round's
+ * packets", below sg_deliver_bucket). */
 int32_t sg_net_links(sg_ctx* ctx, sg_net* net, uint32_t* n_links, uint32_t* out_tail, uint32_t* out_head,
                      uint32_t cap);
 int32_t sg_net_edge_links(sg_ctx* ctx, sg_net* net, uint32_t* out_fwd, uint32_t* out_rev);
@@ -503,6 +508,64 @@ int32_t sg_deliver_source(sg_ctx* ctx, sg_hosts* hosts, const sg_table* table, c
 int32_t sg_deliver_bucket(sg_ctx* ctx, const sg_record* recv, uint32_t n_records,
                           const uint32_t* host_local, uint32_t n_hosts, uint32_t n_local_hosts,
                           uint32_t* dst_order, uint32_t* dst_offsets);
+
+/* ---- link loads from a round's packets (additive to ABI 7) ------------------
+ * What sg_link_load gives for a run's counter matrix, for one round's batch and
+ * with a weight per packet: every counted packet walks its tree path through the
+ * pred rows of sg_routing_tree and adds its weight to each link and node on it.
+ * Cost in proportion to packets x hops; no n x n matrix, no node limit.  Links
+ * and their order are those of sg_net_links.
+ *
+ * `nodes` / n_nodes as for sg_link_load (a permutation of the net's nodes);
+ * `pred` holds rows [row_begin, row_end) as sg_routing_tree writes them,
+ * row-major from row_begin.  packets->src_host and packets->dst_ipv4 are read:
+ * device arrays as for sg_deliver_round, but no grouping by source host is
+ * required.  `status`: device, n_packets SG_PKT_* values, what sg_deliver_round
+ * or sg_deliver_source wrote; a packet counts iff its status is
+ * SG_PKT_DELIVERED; NULL: every packet counts.  `weight`: device u32 per packet
+ * (payload_len, or a total size the caller computed); NULL: 1.  Every counted
+ * packet is walked, whatever its weight.  Per counted packet p: row i =
+ * host_route_idx[src_host[p]], column j = the route index of the host that
+ * dst_ipv4[p] resolves to (the delivery walk's address map), s = nodes[i], d =
+ * nodes[j], w = its weight:
+ *   d == s:  out_link_load[link (s, s)] += w, hops = 1 (get_edge_weight's
+ *            self-loop rule, as sg_link_load treats the diagonal)
+ *   else, for every v on the tree path from d up to (excluding) s in row i:
+ *            out_link_load[link (pred_i[v], v)] += w, out_node_load[v] += w;
+ *            hops = the number of such v
+ *   out_hops[p] = hops; UINT32_MAX for a packet that does not count.
+ * All sums are u64, WRAP, and are ADDED to what the arrays hold: row blocks,
+ * ranks, group members and successive rounds sum into one array.  Any output may
+ * be NULL, but not all three.  SG_ROUTE_OUT_DEVICE applies to pred and the three
+ * outputs, as in sg_link_load; without it they are host arrays (the library
+ * uploads pred and adds the device sums into the host arrays).  The packet
+ * arrays, status and weight are always device memory.  Synchronises once.
+ * For weight == NULL, out_link_load and out_node_load equal what sg_link_load
+ * gives on the counters sg_ctx_set_packet_counters collected for the same round.
+ * SG_ERR_INVALID_ARG, the outputs untouched, for NULL arguments, hosts or net of
+ * another context, n_nodes other than the net's, `nodes` not a permutation, a bad
+ * row range, no output at all.  Found on the device (SG_ERR_INVALID_ARG with a
+ * message, the outputs then undefined; never a trap, never a loop: every walk is
+ * bounded by n_nodes steps), packet kinds first, sg_ctx_last_error_pair =
+ * (smallest failing packet index, UINT32_MAX): a source host >= the host count,
+ * a source whose route row lies outside [row_begin, row_end) (both for every
+ * packet, counted or not), a counted packet whose address does not resolve, a
+ * resolved route index >= n_nodes.  Then pred kinds, sg_ctx_last_error_pair =
+ * the smallest (row, col) in row-major order over all failing packets: a value
+ * >= n_nodes or a (pred, node) pair that is not a link (col = the column of the
+ * node at which the walk failed), a walk that has not reached s after n_nodes
+ * steps (a cycle; col = the packet's destination column).  Only cells that some
+ * counted packet's path crosses are validated; pred[s] is not read.
+ * Timers: "link_packets" (work = packets walked); read_timer(
+ * "link_packets_counted") gives the packets the last call counted. */
+int32_t sg_link_load_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
+                             const uint32_t* nodes, uint32_t n_nodes,
+                             uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                             const uint32_t* pred,
+                             const sg_packets* packets, const uint8_t* status,
+                             const uint32_t* weight,
+                             uint64_t* out_link_load, uint64_t* out_node_load,
+                             uint32_t* out_hops);
 
 /* ---- sharded delivery with a fixed-split exchange (no host round trip) ----
  * The same round as sg_deliver_source / sg_deliver_bucket, with every rank's

@@ -5,8 +5,8 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 
 * routing-table build (NetworkGraph::compute_shortest_paths / get_direct_paths,
   src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`, with the paths' trees
-  (`graph.PathTree`) and the traffic they carried per link (`PathTree.link_load`,
-  `NetworkGraph.links`);
+  (`graph.PathTree`) and the traffic they carried per link (`PathTree.link_load` from per-pair
+  counters, `PathTree.link_load_round` from a round's packets, `NetworkGraph.links`);
 * per-round packet delivery (Worker::send_packet, src/main/core/worker.rs:322-397)
   -> `worker.deliver_round`;
 * the packets in flight between a delivery round and their arrival (the per-host

@@ -29,33 +29,12 @@
 #include <vector>
 
 #include "sg_device.h"
+#include "sg_hosts.h"
 #include "sg_internal.h"
 #include "sg_knobs.h"
 
-struct sg_hosts {
-  sg_ctx* ctx = nullptr;
-  uint32_t n = 0;
-  uint32_t* route = nullptr;  // host -> routing-table index
-  uint64_t* rng = nullptr;    // SoA [4][n]
-  uint64_t* ctr = nullptr;    // n
-  // address -> (host, routing index): dense window or sorted table (the pair
-  // in one 8-byte entry, so resolving a destination is one dependent load)
-  uint32_t ip_base = 0, dense_span = 0;
-  uint2* dense = nullptr;
-  uint32_t* sorted_ip = nullptr;
-  uint2* sorted_host = nullptr;
-  uint32_t max_route = 0;  // largest routing-table index of any host
-  uint32_t min_route = 0;  // smallest (with max_route: a table shard holding every host's row needs no per-round check)
-  ~sg_hosts() {
-    void* ps[] = {route, rng, ctr, dense, sorted_ip, sorted_host};
-    for (void* p : ps)
-      if (p) (void)hipFree(p);
-  }
-};
-
 namespace sg {
 
-constexpr uint32_t NONE = ~0u;
 constexpr int SMALL_BUCKET = 32;
 constexpr uint32_t INBLOCK_RANK_SMALL = 32;  // region path: rank sort up to this many entries per slot,
 constexpr uint32_t WAVE_SORT_MAX = 256;      // in-wave bitonic sort up to this many, the block's beyond
@@ -66,29 +45,6 @@ constexpr int SORT_CHUNK = 2048;  // elements sorted in LDS per chunk
 enum : uint32_t { ERR_UNSORTED = 1, ERR_SRC_RANGE = 2, ERR_ROUTE_RANGE = 4, ERR_NOT_LOCAL = 8, ERR_TIME_OVERFLOW = 16 };
 // flags that reject a whole batch before any host state changes (raised by k_host_off)
 constexpr uint32_t ERR_BATCH = ERR_UNSORTED | ERR_SRC_RANGE | ERR_ROUTE_RANGE;
-
-struct HostMap {
-  uint32_t ip_base, dense_span, n_sorted;
-  const uint2* dense;
-  const uint32_t* sorted_ip;
-  const uint2* sorted_host;
-  // Dns::addr_to_host_id (dns.rs:174-176): (host, its routing index), host = NONE if unknown
-  __device__ __forceinline__ uint2 resolve(uint32_t ip) const {
-    if (dense) {
-      uint32_t off = ip - ip_base;
-      return off < dense_span ? dense[off] : make_uint2(NONE, 0);
-    }
-    uint32_t lo = 0, hi = n_sorted;
-    while (lo < hi) {
-      uint32_t mid = (lo + hi) >> 1;
-      if (sorted_ip[mid] < ip)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-    return (lo < n_sorted && sorted_ip[lo] == ip) ? sorted_host[lo] : make_uint2(NONE, 0);
-  }
-};
 
 __global__ void k_seed_hosts(const uint64_t* __restrict__ seed, uint32_t n, uint64_t* __restrict__ rng) {
   for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < n; h += gridDim.x * blockDim.x) {

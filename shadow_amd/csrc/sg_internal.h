@@ -112,8 +112,9 @@ struct sg_ctx {
   // device rows of outputs the caller takes on the host or not at all
   sg::DevBuf t_idx, t_flag, t_pred, t_fh;
   // link loads (sg_link.hip): the node list and its inverse, the flag words, the device copies of
-  // host inputs and outputs, and the global path's per-workgroup rows
-  sg::DevBuf l_idx, l_flag, l_pred, l_cnt, l_link, l_node, l_scratch;
+  // host inputs and outputs (l_hops: sg_link_load_packets' per-packet hops), and the global
+  // path's per-workgroup rows
+  sg::DevBuf l_idx, l_flag, l_pred, l_cnt, l_link, l_node, l_scratch, l_hops;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

@@ -72,6 +72,7 @@
 //   SG_BUILD_FUSED | 1 | 0, 1 | tune | one-shot build: 0 copies an identity used list and keeps the plan's bound rows ahead of phase 0
 //   SG_TREE_LDS | 1 | 0, 1 | test | shortest-path trees: 0 takes every row on the global path (keys read from the row in memory)
 //   SG_LINK_LDS | 1 | 0, 1 | test | link loads: 0 takes every row on the global path (subtree sums and child counters in a scratch row)
+//   SG_LINK_COMBINE | 1 | 0, 1 | tune | link loads from packets: 0 walks every packet on its own; 1 sums a wave's equal (row, column) pairs first, one lane walking per distinct pair
 //   SG_RI_BLOCK_ROWS | n_used / 8; a group member: half its rows | >= 64, whole 64-row batches | test | RoutingInfo fill: rows per block
 //   SG_GML_THREADS | min(hardware threads, 16) | >= 1 | tune | GML parser: threads
 #pragma once

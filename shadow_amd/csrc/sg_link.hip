@@ -50,12 +50,19 @@
 // before the decrement.
 // Errors go through u64 mins into flag words, one per kind, read at the call's one
 // synchronisation: the first (row, col) in row-major order.
+//
+// sg_link_load_packets (k_link_packets, below the fold): the same sums straight from a round's
+// batch, without the counter matrix.  A lane per packet: the source's route row, the destination
+// resolved through the hosts' address map, then the tree path walked from the destination up to
+// the source, the packet's weight added to every link and node on the way.  Cost in proportion
+// to packets x hops; no per-row state, so no node limit and one path for every graph size.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "sg_device.h"
+#include "sg_hosts.h"
 #include "sg_internal.h"
 #include "sg_knobs.h"
 
@@ -301,6 +308,164 @@ __global__ void __launch_bounds__(1024) k_link_load(const LinkArgs a) {
   }
 }
 
+// ---- sg_link_load_packets: a lane per packet walks its tree path
+// Flag words: the smallest failing (packet << 2) | kind; the first (row << 32) | col of each
+// pred kind; the packets counted.
+enum { LP_BAD_PACKET = 0, LP_BAD_RANGE = 1, LP_BAD_LINK = 2, LP_BAD_CYCLE = 3, LP_COUNTED = 4, LP_WORDS = 5 };
+enum { LP_PKT_SRC = 0, LP_PKT_ROW = 1, LP_PKT_DST = 2, LP_PKT_ROUTE = 3 };
+// Hops walked between two flushes of the global adds.  A no-return atomic stays counted in vmcnt
+// for hundreds of cycles, and the next dependent load waits for everything issued before it (every
+// wait in the code object is vmcnt(0)): with the adds after every hop each hop would pay that
+// wait; held back, LP_HOPS hops pay it once.  (The per-hop form was not measured.)
+constexpr int LP_HOPS = 4;
+
+struct LinkPacketArgs {
+  LinkArgs l;  // (counts, count_cols, scratch and vec unused; bad = LP_WORDS words)
+  HostMap map;
+  const uint32_t* route;  // host -> route index
+  uint32_t n_hosts, n_packets;
+  const uint32_t* src_host;
+  const uint32_t* dst_ipv4;
+  const uint8_t* status;   // or null: every packet counts
+  const uint32_t* weight;  // or null: 1
+  uint32_t* hops;          // or null
+};
+
+// One counted packet's walk: weight w from column j up row i's tree; returns its hops.
+__device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t i, uint32_t j, unsigned long long w) {
+  const uint32_t n = l.n;
+  const uint32_t s = l.nodes[i], d = l.nodes[j];
+  const uint32_t* __restrict__ row = l.pred + (size_t)(i - l.row_begin) * n;
+  const unsigned long long cell = (unsigned long long)i << 32;
+  if (d == s) {  // the self-loop (get_edge_weight's rule), one hop
+    const uint32_t k = link_find(l, s, s);
+    if (k == LINK_NONE)
+      atomicMin(&l.bad[LP_BAD_LINK], cell | j);
+    else if (l.link_load)
+      atomicAdd(&l.link_load[k], w);
+    return 1u;
+  }
+  // v climbs from d; cv its column; pv = pred_i[v], gathered one hop ahead
+  uint32_t v = d, cv = j, pv = row[j], steps = 0;
+  bool go = true;
+  while (go) {
+    uint32_t ks[LP_HOPS], vs[LP_HOPS];
+#pragma unroll
+    for (int q = 0; q < LP_HOPS; q++) {
+      ks[q] = LINK_NONE;
+      vs[q] = 0u;
+      if (!go) continue;
+      if (steps >= n) {  // n steps and not at s: a cycle
+        atomicMin(&l.bad[LP_BAD_CYCLE], cell | j);
+        go = false;
+        continue;
+      }
+      const uint32_t u = pv;
+      if (u >= n) {
+        atomicMin(&l.bad[LP_BAD_RANGE], cell | cv);
+        go = false;
+        continue;
+      }
+      // the next hop's gather ahead of this hop's search: the search's dependent loads overlap it
+      uint32_t cu = 0u;
+      if (u != s) {
+        cu = l.pos[u];
+        pv = row[cu];
+      }
+      const uint32_t k = link_find(l, u, v);
+      if (k == LINK_NONE) {
+        atomicMin(&l.bad[LP_BAD_LINK], cell | cv);
+        go = false;
+        continue;
+      }
+      ks[q] = k;
+      vs[q] = v;
+      steps++;
+      v = u;
+      cv = cu;
+      go = u != s;
+    }
+#pragma unroll
+    for (int q = 0; q < LP_HOPS; q++) {
+      if (ks[q] == LINK_NONE) continue;
+      if (l.link_load) atomicAdd(&l.link_load[ks[q]], w);
+      if (l.node_load) atomicAdd(&l.node_load[vs[q]], w);
+    }
+  }
+  return steps;
+}
+
+// COMBINE (the default; SG_LINK_COMBINE=0 is the plain form): a wave first sums the weights of its
+// lanes' equal (row, column) pairs into the lowest such lane, which walks for all of them; the
+// others take its hop count.  A batch grouped by source host repeats pairs among neighbours: at
+// C3, 1M packets over 20,000 pairs took 0.112 ms against the plain form's 1.139; on uniform pairs,
+// where nothing combines, it was no slower.
+template <bool COMBINE>
+__global__ void __launch_bounds__(256) k_link_packets(const LinkPacketArgs a) {
+  __shared__ uint32_t s_counted;
+  const LinkArgs& l = a.l;
+  if (threadIdx.x == 0) s_counted = 0u;
+  __syncthreads();
+  uint32_t counted = 0;
+  // (the trip count is the same for every lane of a workgroup: COMBINE exchanges across a wave)
+  for (uint32_t base = blockIdx.x * blockDim.x; base < a.n_packets; base += gridDim.x * blockDim.x) {
+    const uint32_t p = base + threadIdx.x;
+    uint32_t hops = LINK_NONE, i = 0, j = 0;
+    unsigned long long w = 0ull;
+    bool walk = false;
+    if (p < a.n_packets) {
+      const uint32_t h = a.src_host[p];
+      const bool counts = !a.status || a.status[p] == SG_PKT_DELIVERED;
+      uint32_t bad_packet = LINK_NONE;
+      if (h >= a.n_hosts) {
+        bad_packet = LP_PKT_SRC;
+      } else {
+        i = a.route[h];
+        if (i < l.row_begin || i - l.row_begin >= l.rows) bad_packet = LP_PKT_ROW;
+      }
+      if (bad_packet == LINK_NONE && counts) {
+        const uint2 r = a.map.resolve(a.dst_ipv4[p]);
+        j = r.y;
+        if (r.x == NONE) {
+          bad_packet = LP_PKT_DST;
+        } else if (j >= l.n) {
+          bad_packet = LP_PKT_ROUTE;
+        } else {
+          walk = true;
+          counted++;
+          w = a.weight ? (unsigned long long)a.weight[p] : 1ull;
+        }
+      }
+      if (bad_packet != LINK_NONE) atomicMin(&l.bad[LP_BAD_PACKET], ((unsigned long long)p << 2) | bad_packet);
+    }
+    if (COMBINE) {
+      const uint32_t lane = threadIdx.x & 63u;
+      // (a lane that does not walk gets a key of its own: row ~0 is no row)
+      const uint32_t ki = walk ? i : 0xFFFFFFFFu, kj = walk ? j : lane;
+      uint32_t first = lane;
+      unsigned long long sum = 0ull;
+      for (int q = 63; q >= 0; q--) {
+        const uint32_t qi = __builtin_amdgcn_readlane(ki, q), qj = __builtin_amdgcn_readlane(kj, q);
+        const uint32_t wlo = __builtin_amdgcn_readlane((uint32_t)w, q);
+        const uint32_t whi = __builtin_amdgcn_readlane((uint32_t)(w >> 32), q);
+        if (qi == ki && qj == kj) {
+          first = (uint32_t)q;
+          sum += ((unsigned long long)whi << 32) | wlo;
+        }
+      }
+      if (walk && first == lane) hops = link_packet_walk(l, i, j, sum);
+      const uint32_t got = __shfl(hops, first);
+      if (walk) hops = got;
+    } else if (walk) {
+      hops = link_packet_walk(l, i, j, w);
+    }
+    if (a.hops && p < a.n_packets) a.hops[p] = hops;
+  }
+  if (counted) atomicAdd(&s_counted, counted);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_counted) atomicAdd(&l.bad[LP_COUNTED], (unsigned long long)s_counted);
+}
+
 // The most nodes the LDS path takes on this device: 14 bytes a node in what a workgroup may
 // allocate (lds_bytes), and u16 parents.
 static uint32_t link_lds_max(const sg_ctx* ctx, size_t* lds_bytes) {
@@ -370,6 +535,18 @@ void ensure_links(sg_ctx* ctx, sg_net* net) {
   net->links = true;
 }
 
+// `nodes`, then its inverse, on the device (queued on the context stream).
+static uint32_t* link_node_index(sg_ctx* ctx, const uint32_t* h_nodes, uint32_t n) {
+  uint32_t* d_idx = ctx->l_idx.get<uint32_t>(2 * (size_t)n);
+  char* hu = stage_acquire(ctx, 1, 2 * (size_t)n * 4);
+  uint32_t* hn = (uint32_t*)hu;
+  memcpy(hn, h_nodes, (size_t)n * 4);
+  for (uint32_t j = 0; j < n; j++) hn[n + h_nodes[j]] = j;
+  SG_HIP(hipMemcpyAsync(d_idx, hu, 2 * (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  stage_release(ctx, 1);
+  return d_idx;
+}
+
 // Rows [row_begin, row_end) folded into the device outputs (d_* row-major from row_begin).
 // Queues everything and synchronises once, on the flag words; `after` runs between the kernel
 // and that synchronisation (the copies of host outputs).
@@ -379,16 +556,7 @@ static void link_rows(sg_ctx* ctx, sg_net* net, const uint32_t* h_nodes, uint32_
                       uint64_t* d_node, F after) {
   hipStream_t stq = ctx->stream;
   const uint32_t n = net->n_nodes, rows = row_end - row_begin;
-  // nodes, then its inverse
-  uint32_t* d_idx = ctx->l_idx.get<uint32_t>(2 * (size_t)n);
-  {
-    char* hu = stage_acquire(ctx, 1, 2 * (size_t)n * 4);
-    uint32_t* hn = (uint32_t*)hu;
-    memcpy(hn, h_nodes, (size_t)n * 4);
-    for (uint32_t j = 0; j < n; j++) hn[n + h_nodes[j]] = j;
-    SG_HIP(hipMemcpyAsync(d_idx, hu, 2 * (size_t)n * 4, hipMemcpyHostToDevice, stq));
-    stage_release(ctx, 1);
-  }
+  uint32_t* d_idx = link_node_index(ctx, h_nodes, n);
   unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LINK_BAD_KINDS);
   SG_HIP(hipMemsetAsync(bad, 0xff, LINK_BAD_KINDS * 8, stq));
   LinkArgs a;
@@ -527,6 +695,121 @@ int32_t sg_link_load(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n
     });
     for (uint32_t k = 0; k < (d_link ? nl : 0u); k++) out_link_load[k] += h_link[k];
     for (uint32_t v = 0; v < (d_node ? n : 0u); v++) out_node_load[v] += h_node[v];
+  });
+}
+
+int32_t sg_link_load_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts, const uint32_t* nodes, uint32_t n_nodes,
+                             uint32_t row_begin, uint32_t row_end, uint32_t flags, const uint32_t* pred,
+                             const sg_packets* packets, const uint8_t* status, const uint32_t* weight,
+                             uint64_t* out_link_load, uint64_t* out_node_load, uint32_t* out_hops) {
+  return sg::guarded(ctx, [&] {
+    using namespace sg;
+    link_check_net(ctx, net);
+    if (!hosts || hosts->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
+    if (n_nodes != net->n_nodes)
+      throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
+    if (n_nodes && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
+    if (row_begin > row_end || row_end > n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+    check_node_list(net, nodes, n_nodes);  // in range and none twice: with n_nodes entries, a permutation
+    if (!out_link_load && !out_node_load && !out_hops) throw Error(SG_ERR_INVALID_ARG, "null output");
+    if (!packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
+    const uint32_t np = packets->n_packets;
+    if (np && (!packets->src_host || !packets->dst_ipv4)) throw Error(SG_ERR_INVALID_ARG, "null packet arrays");
+    if (row_end > row_begin && !pred) throw Error(SG_ERR_INVALID_ARG, "null pred rows");
+    if (np == 0) return;
+    ensure_links(ctx, net);
+    hipStream_t st = ctx->stream;
+    const uint32_t n = n_nodes, rows = row_end - row_begin, nl = net->n_links;
+    const bool dev = (flags & SG_ROUTE_OUT_DEVICE) != 0;
+    // host rows in, host sums out: the device sums start at zero and are added on the host
+    const uint32_t* d_pred = pred;
+    uint64_t* d_link = out_link_load;
+    uint64_t* d_node = out_node_load;
+    uint32_t* d_hops = out_hops;
+    if (!dev) {
+      uint32_t* up = ctx->l_pred.get<uint32_t>((size_t)rows * n);
+      if (rows) SG_HIP(hipMemcpyAsync(up, pred, (size_t)rows * n * 4, hipMemcpyHostToDevice, st));
+      d_pred = up;
+      d_link = out_link_load ? ctx->l_link.get<uint64_t>(nl) : nullptr;
+      d_node = out_node_load ? ctx->l_node.get<uint64_t>(n) : nullptr;
+      d_hops = out_hops ? ctx->l_hops.get<uint32_t>(np) : nullptr;
+      if (d_link) SG_HIP(hipMemsetAsync(d_link, 0, std::max<size_t>((size_t)nl * 8, 8), st));
+      if (d_node) SG_HIP(hipMemsetAsync(d_node, 0, (size_t)n * 8, st));
+    }
+    uint32_t* d_idx = link_node_index(ctx, nodes, n);
+    unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LP_WORDS);
+    SG_HIP(hipMemsetAsync(bad, 0xff, LP_COUNTED * 8, st));
+    SG_HIP(hipMemsetAsync(bad + LP_COUNTED, 0, 8, st));
+    LinkPacketArgs a;
+    a.l.lk_off = net->lk_off;
+    a.l.lk_tail = net->lk_tail;
+    a.l.nodes = d_idx;
+    a.l.pos = d_idx + n;
+    a.l.n = n;
+    a.l.row_begin = row_begin;
+    a.l.rows = rows;
+    a.l.count_cols = 0;
+    a.l.pred = d_pred;
+    a.l.counts = nullptr;
+    a.l.link_load = (unsigned long long*)d_link;
+    a.l.node_load = (unsigned long long*)d_node;
+    a.l.bad = bad;
+    a.l.scratch = nullptr;
+    a.l.vec = 0;
+    a.map = HostMap{hosts->ip_base, hosts->dense_span, hosts->n, hosts->dense, hosts->sorted_ip, hosts->sorted_host};
+    a.route = hosts->route;
+    a.n_hosts = hosts->n;
+    a.n_packets = np;
+    a.src_host = packets->src_host;
+    a.dst_ipv4 = packets->dst_ipv4;
+    a.status = status;
+    a.weight = weight;
+    a.hops = d_hops;
+    {
+      // (work = the packets walked, added below once the count is read)
+      TimedLaunch tl(ctx, "link_packets", 0.0);
+      const dim3 grid(grid_for(np, 256, 16u * (unsigned)ctx->n_cu));
+      if (knob_int("SG_LINK_COMBINE", 1) != 0)
+        hipLaunchKernelGGL(k_link_packets<true>, grid, dim3(256), 0, st, a);
+      else
+        hipLaunchKernelGGL(k_link_packets<false>, grid, dim3(256), 0, st, a);
+      SG_CHECK_LAUNCH();
+    }
+    std::vector<uint64_t> h_link(!dev && d_link ? nl : 0), h_node(!dev && d_node ? n : 0);
+    if (!dev) {
+      if (d_link && nl) SG_HIP(hipMemcpyAsync(h_link.data(), d_link, (size_t)nl * 8, hipMemcpyDeviceToHost, st));
+      if (d_node) SG_HIP(hipMemcpyAsync(h_node.data(), d_node, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+      if (d_hops) SG_HIP(hipMemcpyAsync(out_hops, d_hops, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    }
+    unsigned long long h[LP_WORDS];
+    copy_to_host(ctx, h, bad, sizeof(h));
+    timer_add_work(ctx, "link_packets", (double)h[LP_COUNTED]);
+    // read_timer("link_packets_counted") = (0, the packets the last call counted, 0)
+    timer_set_counter(ctx, "link_packets_counted", 0.0, h[LP_COUNTED]);
+    if (h[LP_BAD_PACKET] != ~0ull) {
+      const uint64_t p = h[LP_BAD_PACKET] >> 2;
+      static const char* const why[4] = {
+          "has a source host past the host table", "has a source host whose route row lies outside the row block",
+          "counts and has a destination address that no host holds",
+          "resolves to a route index that is not below n_nodes"};
+      throw Error(SG_ERR_INVALID_ARG, "packet " + std::to_string(p) + " " + why[h[LP_BAD_PACKET] & 3], (uint32_t)p,
+                  0xFFFFFFFFu);
+    }
+    int kind = -1;
+    for (int k = LP_BAD_RANGE; k <= LP_BAD_CYCLE; k++)
+      if (h[k] != ~0ull && (kind < 0 || h[k] < h[kind])) kind = k;
+    if (kind >= 0) {
+      const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
+      static const char* const why[LP_BAD_CYCLE + 1] = {
+          "", "holds a node index out of range at node ",
+          "names a predecessor that no link joins to the node (not a link) at node ",
+          "does not reach its source within n_nodes steps (a cycle) from node "};
+      throw Error(SG_ERR_INVALID_ARG,
+                  "the pred row of source node " + node_name(net, nodes[i]) + " " + why[kind] + node_name(net, nodes[j]), i,
+                  j);
+    }
+    for (uint32_t k = 0; k < (uint32_t)h_link.size(); k++) out_link_load[k] += h_link[k];
+    for (uint32_t v = 0; v < (uint32_t)h_node.size(); v++) out_node_load[v] += h_node[v];
   });
 }
 

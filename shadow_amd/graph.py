@@ -240,6 +240,54 @@ class PathTree:
             c.ctypes.data, c.shape[1], link.ctypes.data, node.ctypes.data))
         return link, node
 
+    def link_load_round(self, hosts, packets, status=None, weight=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(link_load, node_load, hops) of one round's batch: every counted packet of `packets`
+        (a PacketBatch sent by hosts of `hosts`, a HostTable whose route indices are this tree's
+        columns, every sender on a source row) adds its weight to each link of its tree path (in
+        NetworkGraph.links() order) and to each node the path reaches after the source; a packet
+        to its own node goes to the self-loop link.  hops[p] = the links packet p crossed,
+        0xFFFFFFFF where it does not count.  status: the round's statuses (a Deliveries, or a
+        torch / numpy u8 array of SG_PKT_*), a packet counting when delivered; None: every packet.
+        weight: None (1 per packet), "payload" (the batch's payload_len) or a u32 array
+        (sg_link_load_packets)."""
+        import torch
+
+        n, npk = len(self.nodes), len(packets)
+        dev = packets.src_host.device
+
+        def to_dev(x, np_dtype, t_dtype, what):
+            if isinstance(x, torch.Tensor):
+                x = x.to(device=dev).contiguous()
+                if x.element_size() != np.dtype(np_dtype).itemsize or x.is_floating_point():
+                    raise ValueError(f"{what}: a {np.dtype(np_dtype).name} array")
+                x = x.view(t_dtype)
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).view(
+                    np.int32 if t_dtype == torch.int32 else np.uint8)).to(dev)
+            if x.numel() < npk:
+                raise ValueError(f"{what}: {npk} entries, one per packet")
+            return x
+
+        if status is not None:
+            status = to_dev(getattr(status, "status", status), np.uint8, torch.uint8, "status")
+        if isinstance(weight, str):
+            if weight != "payload":
+                raise ValueError('weight: None, "payload" or an array')
+            weight = packets.payload_len
+        if weight is not None:
+            weight = to_dev(weight, np.uint32, torch.int32, "weight")
+        g = self._graph
+        link, node = np.zeros(len(g.links()[0]), np.uint64), np.zeros(n, np.uint64)
+        hops = np.zeros(npk, np.uint32)
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        p = packets.c_struct()
+        check(g.ctx.handle, load().sg_link_load_packets(
+            g.ctx.handle, g._ensure_net(), hosts.handle, self.nodes.ctypes.data, n, 0, self.n_sources, 0,
+            pred.ctypes.data, C.byref(p), None if status is None else C.c_void_p(status.data_ptr()),
+            None if weight is None else C.c_void_p(weight.data_ptr()), link.ctypes.data, node.ctypes.data,
+            hops.ctypes.data))
+        return link, node, hops
+
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
         taking at each step any arc that is tight: one whose fold gives the table's cell of the
@@ -502,6 +550,22 @@ class NetworkGraph:
             self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used), int(row_begin), int(row_end),
             _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(counts_ptr or None), int(count_cols),
             C.c_void_p(link_ptr or None), C.c_void_p(node_ptr or None)))
+
+    def link_load_packets_device(self, hosts, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int,
+                                 packets, status_ptr: int, weight_ptr: int, link_ptr: int, node_ptr: int,
+                                 hops_ptr: int) -> None:
+        """One round's batch (a PacketBatch from hosts of `hosts`, a HostTable) added onto the links
+        and nodes of its packets' tree paths through device pred rows [row_begin, row_end): a
+        packet counts when its status (device u8, 0: every packet) is SG_PKT_DELIVERED and adds
+        its weight (device u32, 0: 1); the device outputs (u64 per link / per node, added to; u32
+        hops per packet, written) may be 0, not all three (sg_link_load_packets)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        p = packets.c_struct()
+        check(self.ctx.handle, load().sg_link_load_packets(
+            self.ctx.handle, self._ensure_net(), hosts.handle, used.ctypes.data, len(used), int(row_begin),
+            int(row_end), _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.byref(p), C.c_void_p(status_ptr or None),
+            C.c_void_p(weight_ptr or None), C.c_void_p(link_ptr or None), C.c_void_p(node_ptr or None),
+            C.c_void_p(hops_ptr or None)))
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

@@ -466,6 +466,23 @@ unsafe extern "C" {
                                 packets: *const sg_packets, status: *const u8, weight: *const u32,
                                 out_link_load: *mut u64, out_node_load: *mut u64, out_hops: *mut u32) -> i32;
 
+    // ---- batched tree paths: hop records (node, link, cumulative latency and loss) in CSR ----
+    /// The hop records of the pairs (pair_row[p], pair_col[p]), source to destination; pair p owns
+    /// records [out_off[p], out_off[p + 1]).  SG_ERR_CAPACITY with out_off and *total complete
+    /// when *total > cap.
+    pub fn sg_tree_paths(ctx: *mut sg_ctx, net: *mut sg_net, nodes: *const u32, n_nodes: u32, row_begin: u32,
+                         row_end: u32, flags: u32, pred: *const u32, latency_ns: *const u64,
+                         packet_loss: *const f32, n_pairs: u32, pair_row: *const u32, pair_col: *const u32,
+                         out_off: *mut u64, out_node: *mut u32, out_link: *mut u32, out_latency_ns: *mut u64,
+                         out_packet_loss: *mut f32, cap: u64, total: *mut u64) -> i32;
+    /// The same for the counted packets of one round's batch (pairs as in sg_link_load_packets).
+    pub fn sg_tree_paths_packets(ctx: *mut sg_ctx, net: *mut sg_net, hosts: *mut sg_hosts, nodes: *const u32,
+                                 n_nodes: u32, row_begin: u32, row_end: u32, flags: u32, pred: *const u32,
+                                 latency_ns: *const u64, packet_loss: *const f32, packets: *const sg_packets,
+                                 status: *const u8, out_off: *mut u64, out_node: *mut u32, out_link: *mut u32,
+                                 out_latency_ns: *mut u64, out_packet_loss: *mut f32, cap: u64,
+                                 total: *mut u64) -> i32;
+
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;
     pub fn sg_routing_info_destroy(ri: *mut sg_routing_info);

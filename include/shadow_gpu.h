@@ -567,6 +567,79 @@ int32_t sg_link_load_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
                              uint64_t* out_link_load, uint64_t* out_node_load,
                              uint32_t* out_hops);
 
+/* ---- batched tree paths: per-pair and per-packet hop lists (additive to ABI 7) --
+ * The links a path crosses, kept instead of summed: the device batch form of
+ * sg_tree_path.  A HOP RECORD is one link crossed.  For source row i (s =
+ * nodes[i]) and destination column j (d = nodes[j]):
+ *   d != s: the tree path s = v0, v1, ..., vh = d in row i's pred row gives h
+ *           records in SOURCE-TO-DESTINATION order; record k (1 <= k <= h) holds
+ *             node        = vk (petgraph index)
+ *             link        = the number of link (v(k-1), vk) in sg_net_links order
+ *             latency_ns  = latency_ns [i][pos[vk]]   (pos = the inverse of nodes)
+ *             packet_loss = packet_loss[i][pos[vk]]
+ *           the cumulative (latency, loss) at a hop is the row's own table cell
+ *           of the intermediate node, bit for bit.  The source itself is implicit.
+ *   d == s: one record, as sg_link_load_packets counts that case: node = s, link =
+ *           the self-loop link (s, s), latency_ns / packet_loss = the diagonal
+ *           cell (get_edge_weight's rule).
+ * A packet that does not count (status other than SG_PKT_DELIVERED) has no record.
+ * So a counted packet's record count is sg_link_load_packets' out_hops[p], and for
+ * d != s, s followed by the pair's out_node entries is what sg_tree_path returns.
+ *
+ * Output (CSR, deterministic): out_off has n + 1 u64 entries (n = n_pairs or
+ * packets->n_packets), out_off[0] = 0; pair or packet p owns records
+ * [out_off[p], out_off[p + 1]).  out_node u32, out_link u32, out_latency_ns u64,
+ * out_packet_loss f32, each of capacity `cap` records; any may be NULL, not all
+ * four.  out_latency_ns needs the latency_ns rows [row_begin, row_end) as the
+ * build wrote them (row-major from row_begin), out_packet_loss the packet_loss
+ * rows; an output requested without its input is SG_ERR_INVALID_ARG, and an input
+ * whose output is NULL is not read.  With out_link == NULL no link is looked up
+ * and a (pred, node) pair that is not a link is not reported.  *total always
+ * receives the record count.  total > cap: SG_ERR_CAPACITY, out_off and *total
+ * complete, nothing written to the record arrays; grow them and call again.  A
+ * sizing call passes at least one real record array and takes that error.
+ *
+ * sg_tree_paths: the pairs as (pair_row[p], pair_col[p]), row and column indices
+ * in `nodes` order.  SG_ROUTE_OUT_DEVICE applies to pred, the table rows, the
+ * pair arrays and every output alike; without it all of them are host arrays,
+ * which the library stages as sg_link_load_packets does.
+ * sg_tree_paths_packets: the pairs of a round's packets exactly as in
+ * sg_link_load_packets (row = host_route_idx[src_host[p]], column through the
+ * hosts' address map); the packet arrays and status are always device memory.
+ * `total` is a host pointer in either form.  Synchronises twice.
+ *
+ * SG_ERR_INVALID_ARG, every output untouched, for NULL arguments, a net or hosts
+ * of another context, n_nodes other than the net's, `nodes` not a permutation, a
+ * bad row range, no record output.  Found on the device (SG_ERR_INVALID_ARG with
+ * a message, the outputs then undefined; never a trap, never a loop: every walk
+ * ends after n_nodes steps, a value >= n_nodes is caught before it forms an
+ * index): pair or packet kinds first, sg_ctx_last_error_pair = (smallest failing
+ * index, UINT32_MAX): a source host >= the host count, a row outside
+ * [row_begin, row_end), a column or route index >= n_nodes, a counted packet
+ * whose address does not resolve.  Then pred kinds, the smallest (row, col) in
+ * row-major order: a value >= n_nodes (col = the column of the node at which the
+ * walk failed) or a walk that has not reached s after n_nodes steps (a cycle; col
+ * = the destination column), both found while counting, ahead of a (pred, node)
+ * pair that is not a link (col = the node's column), found while filling.  Only
+ * cells that some path crosses are validated; pred[s] is not read.
+ * Timers: "tree_paths_count" and "tree_paths_fill" (work = records), and
+ * "tree_paths_scan" (work = pairs or packets). */
+int32_t sg_tree_paths(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_nodes,
+                      uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                      const uint32_t* pred, const uint64_t* latency_ns, const float* packet_loss,
+                      uint32_t n_pairs, const uint32_t* pair_row, const uint32_t* pair_col,
+                      uint64_t* out_off, uint32_t* out_node, uint32_t* out_link,
+                      uint64_t* out_latency_ns, float* out_packet_loss,
+                      uint64_t cap, uint64_t* total);
+int32_t sg_tree_paths_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
+                              const uint32_t* nodes, uint32_t n_nodes,
+                              uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                              const uint32_t* pred, const uint64_t* latency_ns, const float* packet_loss,
+                              const sg_packets* packets, const uint8_t* status,
+                              uint64_t* out_off, uint32_t* out_node, uint32_t* out_link,
+                              uint64_t* out_latency_ns, float* out_packet_loss,
+                              uint64_t cap, uint64_t* total);
+
 /* ---- sharded delivery with a fixed-split exchange (no host round trip) ----
  * The same round as sg_deliver_source / sg_deliver_bucket, with every rank's
  * records for rank r in a block of `cap` slots, so the exchange is one

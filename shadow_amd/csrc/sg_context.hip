@@ -272,6 +272,7 @@ void sg_ctx_destroy(sg_ctx* ctx) {
     if (ctx->stage_copied[b]) (void)hipEventDestroy(ctx->stage_copied[b]);
   }
   if (ctx->apsp_ret) (void)hipHostFree(ctx->apsp_ret);
+  if (ctx->paths_ret) (void)hipHostFree(ctx->paths_ret);
   for (auto& b : ctx->net_pool) {
     (void)hipEventDestroy(b.freed);
     (void)hipFree(b.p);

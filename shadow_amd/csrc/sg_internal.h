@@ -115,6 +115,11 @@ struct sg_ctx {
   // host inputs and outputs (l_hops: sg_link_load_packets' per-packet hops), and the global
   // path's per-workgroup rows
   sg::DevBuf l_idx, l_flag, l_pred, l_cnt, l_link, l_node, l_scratch, l_hops;
+  // tree paths (sg_paths.hip; it shares l_idx, l_flag and l_pred): the hop count per pair and the
+  // scan's block sums, the device copies of host inputs (table rows, pair arrays) and outputs,
+  // and the pinned, mapped word that receives the record total (allocated on first use)
+  sg::DevBuf p_cnt, p_sums, p_lat, p_loss, p_pair, p_off, p_node, p_link, p_olat, p_oloss;
+  unsigned long long* paths_ret = nullptr;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

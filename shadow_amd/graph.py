@@ -288,6 +288,82 @@ class PathTree:
             hops.ctypes.data))
         return link, node, hops
 
+    def _hop_records(self, n_items: int, call) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(off, node, link, latency_ns, packet_loss) from call(off, node, link, lat, loss, cap, total),
+        one of the two sg_tree_paths entry points on host arrays: a first call at a guessed capacity,
+        a second at the total the first one reported when that was too small."""
+        off = np.zeros(n_items + 1, np.uint64)
+        total = C.c_uint64()
+        cap = 8 * n_items + 64
+        while True:
+            node, link = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+            lat, loss = np.zeros(cap, np.uint64), np.zeros(cap, np.float32)
+            rc = call(off.ctypes.data, node.ctypes.data, link.ctypes.data, lat.ctypes.data, loss.ctypes.data, cap,
+                      C.byref(total))
+            if rc != _capi.SG_ERR_CAPACITY or total.value <= cap:
+                break
+            cap = total.value
+        check(self._graph.ctx.handle, rc)
+        t = total.value
+        return off, node[:t], link[:t], lat[:t], loss[:t]
+
+    def paths(self, src, dst) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The tree paths of the pairs (src[p], dst[p]) (node indices, every src a source of this
+        tree) as hop records, (off, node, link, latency_ns, packet_loss): pair p owns records
+        off[p] .. off[p + 1], one per link crossed, source to destination: the node reached, the
+        link (in NetworkGraph.links() order) and the table's (latency, loss) of that node in the
+        source's row.  [src[p]] + node[off[p]:off[p + 1]] is path(src[p], dst[p]); a pair with
+        src == dst has one record, its node's self-loop link and diagonal cell (sg_tree_paths)."""
+        src, dst = np.atleast_1d(np.asarray(src)), np.atleast_1d(np.asarray(dst))
+        if src.shape != dst.shape or src.ndim != 1:
+            raise ValueError("paths: src and dst are two 1-d arrays of one length")
+        rows = np.array([self._row(v) for v in src.tolist()], np.uint32)
+        cols = np.array([self.index[int(v)] for v in dst.tolist()], np.uint32)
+        g, n = self._graph, len(self.nodes)
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        tlat = np.ascontiguousarray(self.latency_ns, dtype=np.uint64)
+        tloss = np.ascontiguousarray(self.packet_loss, dtype=np.float32)
+
+        def call(off, node, link, lat, loss, cap, total):
+            return load().sg_tree_paths(
+                g.ctx.handle, g._ensure_net(), self.nodes.ctypes.data, n, 0, self.n_sources, 0, pred.ctypes.data,
+                tlat.ctypes.data, tloss.ctypes.data, len(rows), rows.ctypes.data, cols.ctypes.data, off, node, link,
+                lat, loss, cap, total)
+
+        return self._hop_records(len(rows), call)
+
+    def trace_round(self, hosts, packets, status=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray,
+                                                                 np.ndarray]:
+        """The hop records of one round's batch, (off, node, link, latency_ns, packet_loss) as
+        `paths` gives them: packet p of `packets` (a PacketBatch sent by hosts of `hosts`, a
+        HostTable whose route indices are this tree's columns, every sender on a source row) owns
+        records off[p] .. off[p + 1], none when it does not count.  status: the round's statuses (a
+        Deliveries, or a torch / numpy u8 array of SG_PKT_*), a packet counting when delivered;
+        None: every packet (sg_tree_paths_packets)."""
+        import torch
+
+        npk = len(packets)
+        if status is not None:
+            status = getattr(status, "status", status)
+            if not isinstance(status, torch.Tensor):
+                status = torch.from_numpy(np.ascontiguousarray(status, dtype=np.uint8))
+            status = status.to(device=packets.src_host.device).contiguous()
+            if status.element_size() != 1 or status.numel() < npk:
+                raise ValueError(f"status: {npk} u8 entries, one per packet")
+        g, n = self._graph, len(self.nodes)
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        tlat = np.ascontiguousarray(self.latency_ns, dtype=np.uint64)
+        tloss = np.ascontiguousarray(self.packet_loss, dtype=np.float32)
+        p = packets.c_struct()
+
+        def call(off, node, link, lat, loss, cap, total):
+            return load().sg_tree_paths_packets(
+                g.ctx.handle, g._ensure_net(), hosts.handle, self.nodes.ctypes.data, n, 0, self.n_sources, 0,
+                pred.ctypes.data, tlat.ctypes.data, tloss.ctypes.data, C.byref(p),
+                None if status is None else C.c_void_p(status.data_ptr()), off, node, link, lat, loss, cap, total)
+
+        return self._hop_records(npk, call)
+
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
         taking at each step any arc that is tight: one whose fold gives the table's cell of the
@@ -566,6 +642,49 @@ class NetworkGraph:
             int(row_end), _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.byref(p), C.c_void_p(status_ptr or None),
             C.c_void_p(weight_ptr or None), C.c_void_p(link_ptr or None), C.c_void_p(node_ptr or None),
             C.c_void_p(hops_ptr or None)))
+
+    def tree_paths_device(self, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int, latency_ptr: int,
+                          loss_ptr: int, n_pairs: int, pair_row_ptr: int, pair_col_ptr: int, off_ptr: int,
+                          node_ptr: int, link_ptr: int, out_latency_ptr: int, out_loss_ptr: int, cap: int) -> int:
+        """The hop records of n_pairs pairs (device u32 row / column indices in `nodes` order)
+        through device pred rows [row_begin, row_end) and the same rows of the device table, into
+        caller-owned device arrays: off (u64, n_pairs + 1), then per record node u32, link u32,
+        latency u64, loss f32, each of `cap` records; any record array may be 0, not all four,
+        and a table pointer may be 0 when its output is.  Returns the record total; when it
+        exceeds `cap`, off is complete and no record was written (sg_tree_paths)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        total = C.c_uint64()
+        rc = load().sg_tree_paths(
+            self.ctx.handle, self._ensure_net(), used.ctypes.data, len(used), int(row_begin), int(row_end),
+            _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(latency_ptr or None),
+            C.c_void_p(loss_ptr or None), int(n_pairs), C.c_void_p(pair_row_ptr or None),
+            C.c_void_p(pair_col_ptr or None), C.c_void_p(off_ptr or None), C.c_void_p(node_ptr or None),
+            C.c_void_p(link_ptr or None), C.c_void_p(out_latency_ptr or None), C.c_void_p(out_loss_ptr or None),
+            int(cap), C.byref(total))
+        if rc != _capi.SG_ERR_CAPACITY:
+            check(self.ctx.handle, rc)
+        return total.value
+
+    def tree_paths_packets_device(self, hosts, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int,
+                                  latency_ptr: int, loss_ptr: int, packets, status_ptr: int, off_ptr: int,
+                                  node_ptr: int, link_ptr: int, out_latency_ptr: int, out_loss_ptr: int,
+                                  cap: int) -> int:
+        """tree_paths_device for one round's batch (a PacketBatch from hosts of `hosts`, a
+        HostTable): packet p owns records off[p] .. off[p + 1], none unless its status (device u8,
+        0: every packet) is SG_PKT_DELIVERED; the pairs are link_load_packets_device's
+        (sg_tree_paths_packets)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        total = C.c_uint64()
+        p = packets.c_struct()
+        rc = load().sg_tree_paths_packets(
+            self.ctx.handle, self._ensure_net(), hosts.handle, used.ctypes.data, len(used), int(row_begin),
+            int(row_end), _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(latency_ptr or None),
+            C.c_void_p(loss_ptr or None), C.byref(p), C.c_void_p(status_ptr or None), C.c_void_p(off_ptr or None),
+            C.c_void_p(node_ptr or None), C.c_void_p(link_ptr or None), C.c_void_p(out_latency_ptr or None),
+            C.c_void_p(out_loss_ptr or None), int(cap), C.byref(total))
+        if rc != _capi.SG_ERR_CAPACITY:
+            check(self.ctx.handle, rc)
+        return total.value
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

@@ -4,8 +4,8 @@ and holds the only getenv calls for them; DESIGN.md's "Knobs" appendix has one r
 Text only (nothing is built or loaded):
   * no other file of shadow_amd/csrc calls getenv with an SG_ name, and every knob a source
     file reads through the header's readers is in the header's list;
-  * every knob the tests, tests/conftest.py or bench.py name (the routing, delivery, lane and
-    parser prefixes below) is in the list: a test cannot set a knob the library dropped;
+  * every knob the tests, tests/conftest.py or bench.py name (the routing, build, tree, link-load,
+    tree-path, delivery, lane and parser prefixes below) is in the list: a test cannot set a knob the library dropped;
   * the list and the appendix name the same knobs.
 """
 import glob
@@ -18,7 +18,7 @@ HEADER = os.path.join(CSRC, "sg_knobs.h")
 DESIGN = os.path.join(ROOT, "DESIGN.md")
 
 PREFIXES = ("SG_APSP_", "SG_SSSP_", "SG_DENSE_", "SG_BUCKET_", "SG_BAND_", "SG_NET_", "SG_PLAN_", "SG_LANE_",
-            "SG_RI_", "SG_GML_")
+            "SG_RI_", "SG_GML_", "SG_TREE_", "SG_LINK_", "SG_PATHS_", "SG_BUILD_")
 NAME = r"SG_[A-Z0-9]+(?:_[A-Z0-9]+)+"
 KINDS = {"test", "tune", "diag"}
 

@@ -482,6 +482,16 @@ unsafe extern "C" {
                                  status: *const u8, out_off: *mut u64, out_node: *mut u32, out_link: *mut u32,
                                  out_latency_ns: *mut u64, out_packet_loss: *mut f32, cap: u64,
                                  total: *mut u64) -> i32;
+    /// Link trace: the same crossings grouped by link (sg_net_links order) and sorted by
+    /// (enter_ns, packet); link L owns records [out_link_off[L], out_link_off[L + 1]).  `watch`
+    /// (NULL or n_links u8) empties the segments of links it marks 0.  SG_ERR_CAPACITY with
+    /// out_link_off and *total complete when *total > cap.
+    pub fn sg_link_trace_packets(ctx: *mut sg_ctx, net: *mut sg_net, hosts: *mut sg_hosts, nodes: *const u32,
+                                 n_nodes: u32, row_begin: u32, row_end: u32, flags: u32, pred: *const u32,
+                                 latency_ns: *const u64, packets: *const sg_packets, status: *const u8,
+                                 watch: *const u8, out_link_off: *mut u64, out_packet: *mut u32,
+                                 out_hop: *mut u32, out_enter_ns: *mut u64, out_exit_ns: *mut u64, cap: u64,
+                                 total: *mut u64) -> i32;
 
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;

@@ -640,6 +640,65 @@ int32_t sg_tree_paths_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
                               uint64_t* out_latency_ns, float* out_packet_loss,
                               uint64_t cap, uint64_t* total);
 
+/* ---- link trace: a round's packets per link, in time order (additive to ABI 7) --
+ * The crossings of sg_tree_paths_packets grouped by LINK and sorted by time: which
+ * packets crossed a link, and when.  Pairs, counting rule, `nodes`, `pred`, the
+ * latency_ns rows, the row block and the address resolution are exactly as in
+ * sg_tree_paths_packets; latency_ns is always required (the order depends on it),
+ * packet_loss is not taken, packets->send_time_ns is read.
+ * A TRACE RECORD is one (counted packet p, link crossed).  Packet p has row i,
+ * source s, destination d and the tree path s = v0, ..., vh = d; cum(v) =
+ * latency_ns[i][pos[v]], cum(s) = 0:
+ *   d != s: hop k (1 <= k <= h) gives one record on link (v(k-1), vk):
+ *             packet   = p
+ *             hop      = k
+ *             enter_ns = send_time_ns[p] + cum(v(k-1))
+ *             exit_ns  = send_time_ns[p] + cum(vk)
+ *   d == s: one record on the self-loop link (s, s): hop = 1, enter_ns =
+ *           send_time_ns[p], exit_ns = send_time_ns[p] + the diagonal cell.
+ * So record out_off[p] + hop - 1 of sg_tree_paths_packets is the same crossing.
+ *
+ * Output: links are numbered in sg_net_links order.  out_link_off (required) has
+ * n_links + 1 u64 entries, out_link_off[0] = 0; link L owns records
+ * [out_link_off[L], out_link_off[L + 1]) in ascending (enter_ns, packet) order.  A
+ * tree path crosses a link at most once, so the key is unique and the output is a
+ * function of the inputs alone.  out_packet u32, out_hop u32, out_enter_ns u64,
+ * out_exit_ns u64, each of capacity `cap` records; any may be NULL, not all four.
+ * watch: NULL, or n_links u8; a link with watch[L] == 0 gets an empty segment and
+ * counts nothing towards *total, its crossings are still walked and validated.
+ * total > cap: SG_ERR_CAPACITY, out_link_off and *total complete, nothing written
+ * to the record arrays (the contract of sg_tree_paths, its sizing call included).
+ * With no packets out_link_off is all zero and *total = 0.
+ *
+ * SG_ROUTE_OUT_DEVICE applies to pred, latency_ns, watch and every output alike;
+ * without it they are host arrays, staged as the sibling calls stage theirs.  The
+ * packet arrays and status are always device memory, `total` a host pointer.
+ * Synchronises twice.
+ *
+ * Errors: precedence and sg_ctx_last_error_pair as in sg_tree_paths_packets.
+ * Argument errors (those of sg_tree_paths_packets; NULL latency_ns or
+ * send_time_ns) leave every output untouched.  Packet kinds come first, the
+ * smallest failing packet as (packet, UINT32_MAX); to its kinds one is added, the
+ * last of them: a counted packet whose send_time_ns + latency_ns[i][j] passes
+ * 2^64 - 1 gives SG_ERR_TIME_OVERFLOW (no earlier hop can overflow when the
+ * destination's sum does not: arc latency is at least 1 ns, cum rises along the
+ * path).  Then the pred kinds: a value >= n_nodes or a cycle, ahead of a (pred,
+ * node) pair that is not a link; every crossing is looked up, so a non-link is
+ * reported whichever outputs are NULL and whether or not a link is watched.  Every
+ * walk ends after n_nodes steps: never a trap, never a loop.
+ * Timers: "link_trace_count", "link_trace_fill", "link_trace_sort" (work =
+ * records). */
+int32_t sg_link_trace_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
+                              const uint32_t* nodes, uint32_t n_nodes,
+                              uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                              const uint32_t* pred, const uint64_t* latency_ns,
+                              const sg_packets* packets, const uint8_t* status,
+                              const uint8_t* watch,
+                              uint64_t* out_link_off,
+                              uint32_t* out_packet, uint32_t* out_hop,
+                              uint64_t* out_enter_ns, uint64_t* out_exit_ns,
+                              uint64_t cap, uint64_t* total);
+
 /* ---- sharded delivery with a fixed-split exchange (no host round trip) ----
  * The same round as sg_deliver_source / sg_deliver_bucket, with every rank's
  * records for rank r in a block of `cap` slots, so the exchange is one

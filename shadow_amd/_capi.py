@@ -62,7 +62,7 @@ EXPORTED = [
     "sg_group_routing_info_fill", "sg_group_exchange_padded", "sg_group_alltoallv_records",
     "sg_routing_tree", "sg_routing_build_tree", "sg_tree_path",
     "sg_net_links", "sg_net_edge_links", "sg_link_load", "sg_link_load_packets",
-    "sg_tree_paths", "sg_tree_paths_packets",
+    "sg_tree_paths", "sg_tree_paths_packets", "sg_link_trace_packets",
 ]
 
 
@@ -236,6 +236,8 @@ def load(path: str | None = None):
                                        vp, vp, vp]),
         "sg_tree_paths": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, u64, u64p]),
         "sg_tree_paths_packets": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, C.POINTER(sg_packets), vp,
+                                        vp, vp, vp, vp, vp, u64, u64p]),
+        "sg_link_trace_packets": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, C.POINTER(sg_packets), vp, vp,
                                         vp, vp, vp, vp, vp, u64, u64p]),
         "sg_routing_info_create": (i32, [u32, vp, C.POINTER(vp)]),
         "sg_routing_info_destroy": (None, [vp]),

@@ -120,6 +120,11 @@ struct sg_ctx {
   // and the pinned, mapped word that receives the record total (allocated on first use)
   sg::DevBuf p_cnt, p_sums, p_lat, p_loss, p_pair, p_off, p_node, p_link, p_olat, p_oloss;
   unsigned long long* paths_ret = nullptr;
+  // link trace (sg_trace.hip; it shares l_idx, l_flag, l_pred, p_cnt, p_sums, p_lat, p_off, the
+  // p_* outputs and paths_ret): the link counters with the fill's cursors and the work counter,
+  // the two staging arrays (keys, exit times), the sort's work entries, the device copies of a
+  // host watch array and of out_exit_ns
+  sg::DevBuf tr_cnt, tr_key, tr_key2, tr_exit, tr_exit2, tr_work, tr_watch, tr_oexit;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

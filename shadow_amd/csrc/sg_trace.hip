@@ -1,0 +1,702 @@
+// sg_trace.hip -- link trace: a round's packets per link, in time order.
+//
+// sg_tree_paths_packets (sg_paths.hip) keeps a round's hop records grouped by packet; this file
+// gives the same crossings grouped by LINK and sorted by time.  A TRACE RECORD is one (counted
+// packet p, link crossed).  Packet p has row i, source s = nodes[i], destination d and the tree
+// path s = v0 .. vh = d of row i's pred row; cum(v) = latency_ns[i][pos[v]], cum(s) = 0.  d != s:
+// hop k (1 <= k <= h) gives a record on link (v(k-1), vk) with (packet p, hop k, enter =
+// send_time[p] + cum(v(k-1)), exit = send_time[p] + cum(vk)).  d == s: one record on the self-loop
+// link (s, s), hop 1, enter = send_time[p], exit = send_time[p] + the diagonal cell.  Link L (in
+// sg_net_links order) owns records [out_link_off[L], out_link_off[L + 1]) in ascending (enter,
+// packet) order; a tree path crosses a link at most once, so the key is unique and the output a
+// function of the inputs alone.  A link with watch[L] == 0 owns nothing; its crossings are
+// walked and validated all the same.
+//
+// Steps on the context stream:
+//   1. count (k_trace_count): a lane per packet, grid-stride; sg_paths.hip's count walk with the
+//      link search (link_find, sg_links.h) per hop and a u32 add into the link's counter.  Writes
+//      the packet's hop count and every flag word: the walk is validated here once, whole.
+//   2. scan: the exclusive u64 scan of the link counters into out_link_off, reduce-then-scan in
+//      three launches (block sums; one workgroup over the sums, which also writes
+//      out_link_off[n_links] and the total into a pinned, mapped word; the add).  No workgroup
+//      waits on another inside a launch.
+//   3. fill (k_trace_fill): the walk again; a record reserves its slot with an add on the link's
+//      cursor and stores its staging record there: the key (enter, packet) with the hop in one
+//      16-byte word, the exit time beside it when out_exit_ns is wanted.  The order inside a
+//      segment is whatever the adds gave.
+//   4. sort, per link, in three tiers after sg_wire.hip's segmented sort:
+//        k_trace_sort_small  a wave per link: up to 64 records are ranked in the wave's registers
+//                            (keys are unique, so ranks are a permutation); a longer segment is
+//                            cut into pieces of P records, work entry = (link, piece);
+//        k_trace_sort_lds    a workgroup per piece: bitonic sort of its keys in LDS (16 bytes a
+//                            key, 32 KiB at P = 2048); a segment of one piece is written out, a
+//                            piece of a longer one goes sorted to the second staging array;
+//        k_trace_merge       the pieces of a longer segment are merged by rank: a record's place
+//                            is its index in its piece plus, for every other piece, the number of
+//                            keys below its own (a binary search).
+// The host reads the flag words and the total between 2 and 3 (total > cap: SG_ERR_CAPACITY, with
+// out_link_off and *total complete and no record written) and waits for the stream after 4: two
+// synchronisations.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "sg_device.h"
+#include "sg_hosts.h"
+#include "sg_internal.h"
+#include "sg_knobs.h"
+#include "sg_links.h"
+
+namespace sg {
+namespace {
+
+// Flag words: the smallest failing (packet << 3) | kind; the first (row << 32) | col of each pred kind.
+enum { TR_BAD_ITEM = 0, TR_BAD_RANGE = 1, TR_BAD_LINK = 2, TR_BAD_CYCLE = 3, TR_WORDS = 4 };
+enum { TR_ITEM_SRC = 0, TR_ITEM_ROW = 1, TR_ITEM_DST = 2, TR_ITEM_COL = 3, TR_ITEM_TIME = 4 };
+constexpr uint32_t TR_THREADS = 256;
+constexpr uint32_t TR_SCAN_PER = 8;  // counters per thread of the scan
+constexpr uint32_t TR_SCAN_TILE = TR_THREADS * TR_SCAN_PER;
+constexpr uint32_t TR_SUMS_THREADS = 1024;
+constexpr uint32_t TR_RANK_MAX = 64;     // a segment up to one wave: rank sort in registers
+constexpr uint32_t TR_PIECE_MAX = 2048;  // keys of one piece in LDS: 16 bytes x 2048 = 32 KiB
+
+struct TraceArgs {
+  LinkArgs l;  // (counts, count_cols, link_load, node_load, scratch and vec unused; bad = TR_WORDS words)
+  HostMap map;
+  const uint32_t* route;  // host -> route index
+  uint32_t n_hosts;
+  const uint32_t* src_host;
+  const uint32_t* dst_ipv4;
+  const unsigned long long* send_time;
+  const uint8_t* status;  // or null: every packet counts
+  uint32_t n_items;       // packets
+  uint32_t* hops;         // per packet, from the count walk
+  const unsigned long long* lat;  // rows [row_begin, row_begin + rows) of the table
+  const uint8_t* watch;           // per link, or null: every link
+  uint32_t n_links;
+  uint32_t* cnt;  // records per link
+  uint32_t* cur;  // the fill's cursor per link
+  unsigned long long* sums;  // the scan's block sums, then their exclusive prefix
+  unsigned long long* off;   // out_link_off
+  unsigned long long* total;  // the mapped word
+  // staging: (enter lo, enter hi, packet, hop) and the exit time (or null)
+  uint4* key;
+  unsigned long long* exit;
+};
+
+// The four record arrays, any of them null.
+struct TraceOut {
+  uint32_t* packet;
+  uint32_t* hop;
+  unsigned long long* enter;
+  unsigned long long* exit;
+};
+
+// Packet p's (row, column); returns whether it has records.  kind: TR_ITEM_* when the packet is in
+// error, else LINK_NONE.  sg_link_load_packets' rule, the resolve sg_hosts.h's.
+__device__ __forceinline__ bool trace_item(const TraceArgs& a, uint32_t p, uint32_t& i, uint32_t& j, uint32_t& kind) {
+  const LinkArgs& l = a.l;
+  kind = LINK_NONE;
+  i = j = 0;
+  const uint32_t h = a.src_host[p];
+  const bool counts = !a.status || a.status[p] == SG_PKT_DELIVERED;
+  if (h >= a.n_hosts) {
+    kind = TR_ITEM_SRC;
+    return false;
+  }
+  i = a.route[h];
+  if (i < l.row_begin || i - l.row_begin >= l.rows) {
+    kind = TR_ITEM_ROW;
+    return false;
+  }
+  if (!counts) return false;
+  const uint2 r = a.map.resolve(a.dst_ipv4[p]);
+  j = r.y;
+  if (r.x == NONE) {
+    kind = TR_ITEM_DST;
+    return false;
+  }
+  if (j >= l.n) {
+    kind = TR_ITEM_COL;
+    return false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ bool watched(const TraceArgs& a, uint32_t link) { return !a.watch || a.watch[link] != 0; }
+
+// ---- 1. count
+__global__ void __launch_bounds__(TR_THREADS) k_trace_count(const TraceArgs a) {
+  const LinkArgs& l = a.l;
+  const uint32_t n = l.n;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_items; q += stride) {
+    const uint32_t p = (uint32_t)q;
+    uint32_t i, j, kind;
+    const bool walk = trace_item(a, p, i, j, kind);
+    if (kind != LINK_NONE) atomicMin(&l.bad[TR_BAD_ITEM], ((unsigned long long)p << 3) | kind);
+    uint32_t hops = 0;
+    if (walk) {
+      const size_t r = (size_t)(i - l.row_begin) * n;
+      const unsigned long long cell = (unsigned long long)i << 32;
+      // the destination's time bounds every hop's: arc latency is at least 1 ns, cum rises along the path
+      if (a.send_time[p] + a.lat[r + j] < a.send_time[p])
+        atomicMin(&l.bad[TR_BAD_ITEM], ((unsigned long long)p << 3) | TR_ITEM_TIME);
+      const uint32_t s = l.nodes[i], d = l.nodes[j];
+      if (d == s) {  // the self-loop (get_edge_weight's rule), one hop
+        const uint32_t link = link_find(l, s, s);
+        if (link == LINK_NONE)
+          atomicMin(&l.bad[TR_BAD_LINK], cell | j);
+        else if (watched(a, link))
+          atomicAdd(&a.cnt[link], 1u);
+        hops = 1u;
+      } else {
+        const uint32_t* __restrict__ row = l.pred + r;
+        // v = the node the walk stands on, cv its column; pv = its predecessor
+        uint32_t v = d, cv = j, pv = row[j], steps = 0;
+        for (;;) {
+          if (steps >= n) {  // n steps and not at s: a cycle
+            atomicMin(&l.bad[TR_BAD_CYCLE], cell | j);
+            steps = 0;
+            break;
+          }
+          if (pv >= n) {
+            atomicMin(&l.bad[TR_BAD_RANGE], cell | cv);
+            steps = 0;
+            break;
+          }
+          steps++;
+          const uint32_t link = link_find(l, pv, v);
+          if (link == LINK_NONE)
+            atomicMin(&l.bad[TR_BAD_LINK], cell | cv);
+          else if (watched(a, link))
+            atomicAdd(&a.cnt[link], 1u);
+          if (pv == s) break;
+          v = pv;
+          cv = l.pos[pv];
+          pv = row[cv];
+        }
+        hops = steps;
+      }
+    }
+    a.hops[p] = hops;
+  }
+}
+
+// ---- 2. scan (sg_paths.hip's form over the link counters)
+__device__ __forceinline__ unsigned long long tr_wave_inclusive(unsigned long long x) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const unsigned long long y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  return x;
+}
+
+// The exclusive prefix of x over the workgroup's threads (blockDim.x a multiple of 64, at most
+// 1024); *total = the sum.  s_wave: 16 words of LDS; every thread calls.
+__device__ __forceinline__ unsigned long long tr_block_exclusive(unsigned long long x, unsigned long long* s_wave,
+                                                                 unsigned long long* total) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const unsigned long long inc = tr_wave_inclusive(x);
+  __syncthreads();  // (the last call's reads of s_wave)
+  if (lane == 63) s_wave[w] = inc;
+  __syncthreads();
+  unsigned long long before = 0ull, all = 0ull;
+  for (uint32_t k = 0; k < nw; k++) {
+    const unsigned long long t = s_wave[k];
+    if (k < w) before += t;
+    all += t;
+  }
+  *total = all;
+  return before + inc - x;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) k_trace_block_sums(const TraceArgs a) {
+  __shared__ unsigned long long s_wave[16];
+  const size_t base = (size_t)blockIdx.x * TR_SCAN_TILE + (size_t)threadIdx.x * TR_SCAN_PER;
+  unsigned long long x = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < TR_SCAN_PER; k++)
+    if (base + k < a.n_links) x += a.cnt[base + k];
+  unsigned long long total;
+  tr_block_exclusive(x, s_wave, &total);
+  if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+}
+
+// One workgroup: the block sums to their exclusive prefix, in place; out_link_off[n_links] and the total.
+__global__ void __launch_bounds__(TR_SUMS_THREADS) k_trace_scan_sums(const TraceArgs a, uint32_t n_blocks) {
+  __shared__ unsigned long long s_wave[16];
+  unsigned long long carry = 0ull;
+  for (uint32_t base = 0; base < n_blocks; base += blockDim.x) {
+    const uint32_t b = base + threadIdx.x;
+    const unsigned long long x = b < n_blocks ? a.sums[b] : 0ull;
+    unsigned long long total;
+    const unsigned long long ex = tr_block_exclusive(x, s_wave, &total);
+    if (b < n_blocks) a.sums[b] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    a.off[a.n_links] = carry;
+    *a.total = carry;
+  }
+}
+
+__global__ void __launch_bounds__(TR_THREADS) k_trace_scan_add(const TraceArgs a) {
+  __shared__ unsigned long long s_wave[16];
+  const size_t base = (size_t)blockIdx.x * TR_SCAN_TILE + (size_t)threadIdx.x * TR_SCAN_PER;
+  uint32_t c[TR_SCAN_PER];
+  unsigned long long x = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < TR_SCAN_PER; k++) {
+    c[k] = base + k < a.n_links ? a.cnt[base + k] : 0u;
+    x += c[k];
+  }
+  unsigned long long total;
+  unsigned long long at = a.sums[blockIdx.x] + tr_block_exclusive(x, s_wave, &total);
+#pragma unroll
+  for (uint32_t k = 0; k < TR_SCAN_PER; k++) {
+    if (base + k < a.n_links) a.off[base + k] = at;
+    at += c[k];
+  }
+}
+
+// ---- 3. fill
+__global__ void __launch_bounds__(TR_THREADS) k_trace_fill(const TraceArgs a) {
+  const LinkArgs& l = a.l;
+  const uint32_t n = l.n;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_items; q += stride) {
+    const uint32_t p = (uint32_t)q;
+    uint32_t k = a.hops[p];  // the hop number of the record at hand: the walk climbs from d
+    uint32_t i, j, kind;
+    if (k == 0 || !trace_item(a, p, i, j, kind)) continue;
+    const uint32_t s = l.nodes[i];
+    const size_t r = (size_t)(i - l.row_begin) * n;
+    const uint32_t* __restrict__ row = l.pred + r;
+    const unsigned long long send = a.send_time[p];
+    // v climbs from d; cv its column; pv = pred_i[v] (s itself for the self-loop's record),
+    // gathered one hop ahead of the link search
+    uint32_t v = l.nodes[j], cv = j;
+    uint32_t pv = v == s ? s : row[j];
+    unsigned long long exit = send + a.lat[r + cv];
+    while (k > 0) {  // (the count's own bound)
+      const uint32_t u = pv;
+      if (u >= n) break;  // (the count pass reported it)
+      uint32_t cu = 0u;
+      unsigned long long enter = send;
+      if (u != s) {
+        cu = l.pos[u];
+        pv = row[cu];
+        enter = send + a.lat[r + cu];
+      }
+      const uint32_t link = link_find(l, u, v);
+      if (link != LINK_NONE && watched(a, link)) {
+        // (a slot past the segment cannot be reserved while the inputs are what the count walked;
+        // the bound keeps the store inside the arrays whatever they are)
+        const unsigned long long at = a.off[link] + atomicAdd(&a.cur[link], 1u);
+        if (at < a.off[link + 1]) {
+          a.key[at] = make_uint4((uint32_t)enter, (uint32_t)(enter >> 32), p, k);
+          if (a.exit) a.exit[at] = exit;
+        }
+      }
+      if (u == s) break;
+      k--;
+      v = u;
+      cv = cu;
+      exit = enter;
+    }
+  }
+}
+
+// ---- 4. sort
+struct TraceRec {
+  unsigned long long enter, exit;
+  uint32_t packet, hop;
+};
+
+__device__ __forceinline__ TraceRec trace_load(const uint4* key, const unsigned long long* exit, size_t at) {
+  const uint4 k = key[at];
+  return TraceRec{((unsigned long long)k.y << 32) | k.x, exit ? exit[at] : 0ull, k.z, k.w};
+}
+
+__device__ __forceinline__ void trace_store(uint4* key, unsigned long long* exit, size_t at, const TraceRec& r) {
+  key[at] = make_uint4((uint32_t)r.enter, (uint32_t)(r.enter >> 32), r.packet, r.hop);
+  if (exit) exit[at] = r.exit;
+}
+
+__device__ __forceinline__ void trace_emit(const TraceOut& o, size_t at, const TraceRec& r) {
+  if (o.packet) o.packet[at] = r.packet;
+  if (o.hop) o.hop[at] = r.hop;
+  if (o.enter) o.enter[at] = r.enter;
+  if (o.exit) o.exit[at] = r.exit;
+}
+
+__device__ __forceinline__ bool trace_less(unsigned long long ta, uint32_t pa, unsigned long long tb, uint32_t pb) {
+  return ta < tb || (ta == tb && pa < pb);
+}
+
+// Tier 1, a wave per link.  n_work (one word, zeroed) counts the work entries of the longer segments.
+__global__ void __launch_bounds__(TR_THREADS) k_trace_sort_small(const unsigned long long* off, uint32_t n_links,
+                                                                const uint4* key, const unsigned long long* exit,
+                                                                TraceOut out, uint32_t piece, uint2* work,
+                                                                uint32_t work_cap, uint32_t* n_work) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * TR_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * TR_THREADS) >> 6;
+  for (uint32_t lk = wave; lk < n_links; lk += n_waves) {
+    const unsigned long long s0 = off[lk];
+    const uint32_t n = __builtin_amdgcn_readfirstlane((uint32_t)(off[lk + 1] - s0));
+    if (n == 0) continue;
+    if (n <= TR_RANK_MAX) {
+      TraceRec r = {};
+      if (lane < n) r = trace_load(key, exit, (size_t)s0 + lane);
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < n; j++) {
+        const unsigned long long tj = __shfl(r.enter, (int)j, 64);
+        const uint32_t pj = __shfl(r.packet, (int)j, 64);
+        rank += trace_less(tj, pj, r.enter, r.packet) ? 1u : 0u;
+      }
+      if (lane < n) trace_emit(out, (size_t)s0 + rank, r);
+    } else {
+      const uint32_t pieces = (n + piece - 1) / piece;
+      uint32_t at = 0;
+      if (lane == 0) at = atomicAdd(n_work, pieces);
+      at = __shfl(at, 0, 64);
+      for (uint32_t c = lane; c < pieces; c += 64)
+        if (at + c < work_cap) work[at + c] = make_uint2(lk, c);
+    }
+  }
+}
+
+struct TraceKey {
+  unsigned long long t;
+  uint32_t p, idx;
+};
+
+// Tier 2, a workgroup per piece: bitonic sort of the keys in LDS.  A segment of one piece is
+// final: written out.  A piece of a longer segment goes, sorted, to the second staging array.
+__global__ void __launch_bounds__(TR_THREADS) k_trace_sort_lds(const unsigned long long* off, const uint4* key,
+                                                              const unsigned long long* exit, uint4* key2,
+                                                              unsigned long long* exit2, TraceOut out, uint32_t piece,
+                                                              const uint2* work, uint32_t work_cap,
+                                                              const uint32_t* n_work_p) {
+  __shared__ TraceKey s_key[TR_PIECE_MAX];
+  const uint32_t n_work = min(*n_work_p, work_cap);
+  for (uint32_t wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
+    const uint2 we = work[wi];
+    const unsigned long long s0 = off[we.x];
+    const uint32_t n = (uint32_t)(off[we.x + 1] - s0);
+    const uint32_t p0 = we.y * piece, m = min(n - p0, piece);
+    uint32_t P = 64;
+    while (P < m) P <<= 1;  // <= TR_PIECE_MAX: piece is
+    for (uint32_t i = threadIdx.x; i < P; i += TR_THREADS) {
+      TraceKey k = {~0ull, ~0u, ~0u};  // padding sorts last (no packet index is UINT32_MAX)
+      if (i < m) {
+        const uint4 q = key[(size_t)s0 + p0 + i];
+        k = TraceKey{((unsigned long long)q.y << 32) | q.x, q.z, i};
+      }
+      s_key[i] = k;
+    }
+    __syncthreads();
+    for (uint32_t k = 2; k <= P; k <<= 1)
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        for (uint32_t i = threadIdx.x; i < P; i += TR_THREADS) {
+          const uint32_t x = i ^ j;
+          if (x > i) {
+            const TraceKey a = s_key[i], b = s_key[x];
+            const bool up = (i & k) == 0;
+            if (trace_less(b.t, b.p, a.t, a.p) == up) {
+              s_key[i] = b;
+              s_key[x] = a;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    for (uint32_t i = threadIdx.x; i < m; i += TR_THREADS) {
+      const uint32_t idx = s_key[i].idx;
+      if (idx >= m) continue;  // (padding never sorts below a record)
+      const TraceRec r = trace_load(key, exit, (size_t)s0 + p0 + idx);
+      if (n <= piece)
+        trace_emit(out, (size_t)s0 + i, r);
+      else
+        trace_store(key2, exit2, (size_t)s0 + p0 + i, r);
+    }
+    __syncthreads();
+  }
+}
+
+// Tier 3, a hot link: the segment's sorted pieces are merged by rank -- a record's final position
+// is its index in its own piece plus, for every other piece, the number of keys below its own (a
+// binary search; unique keys, so no tie rule is needed).
+__global__ void __launch_bounds__(TR_THREADS) k_trace_merge(const unsigned long long* off, const uint4* key2,
+                                                           const unsigned long long* exit2, TraceOut out, uint32_t piece,
+                                                           const uint2* work, uint32_t work_cap,
+                                                           const uint32_t* n_work_p) {
+  const uint32_t n_work = min(*n_work_p, work_cap);
+  for (uint32_t wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
+    const uint2 we = work[wi];
+    const unsigned long long s0 = off[we.x];
+    const uint32_t n = (uint32_t)(off[we.x + 1] - s0);
+    if (n <= piece) continue;
+    const uint32_t pieces = (n + piece - 1) / piece;
+    const uint32_t p0 = we.y * piece, m = min(n - p0, piece);
+    for (uint32_t i = threadIdx.x; i < m; i += TR_THREADS) {
+      const TraceRec r = trace_load(key2, exit2, (size_t)s0 + p0 + i);
+      uint32_t rank = i;
+      for (uint32_t c = 0; c < pieces; c++) {
+        if (c == we.y) continue;
+        const uint32_t q0 = c * piece, qm = min(n - q0, piece);
+        uint32_t lo = 0, hi = qm;  // the first index of piece c whose key is not below r's
+        for (int it = 0; it < 32 && lo < hi; it++) {
+          const uint32_t mid = lo + (hi - lo) / 2;
+          const uint4 q = key2[(size_t)s0 + q0 + mid];
+          if (trace_less(((unsigned long long)q.y << 32) | q.x, q.z, r.enter, r.packet))
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        rank += lo;
+      }
+      if (rank < n) trace_emit(out, (size_t)s0 + rank, r);  // (always, with unique keys)
+    }
+  }
+}
+
+// ---- host
+struct TraceCall {
+  sg_ctx* ctx;
+  sg_net* net;
+  sg_hosts* hosts;
+  const uint32_t* nodes;
+  uint32_t n_nodes, row_begin, row_end, flags;
+  const uint32_t* pred;
+  const uint64_t* lat;
+  const sg_packets* packets;
+  const uint8_t* status;
+  const uint8_t* watch;
+  uint64_t* out_off;
+  uint32_t* out_packet;
+  uint32_t* out_hop;
+  uint64_t* out_enter;
+  uint64_t* out_exit;
+  uint64_t cap;
+  uint64_t* total;
+};
+
+void trace_run(const TraceCall& c) {
+  sg_ctx* ctx = c.ctx;
+  sg_net* net = c.net;
+  if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
+  if (c.n_nodes != net->n_nodes)
+    throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
+  if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
+  if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  check_node_list(net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
+  if (!c.out_packet && !c.out_hop && !c.out_enter && !c.out_exit) throw Error(SG_ERR_INVALID_ARG, "no record output");
+  if (!c.out_off || !c.total) throw Error(SG_ERR_INVALID_ARG, "null out_link_off or total");
+  if (!c.hosts || c.hosts->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
+  if (!c.packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
+  const uint32_t ni = c.packets->n_packets;
+  if (ni && (!c.packets->src_host || !c.packets->dst_ipv4 || !c.packets->send_time_ns))
+    throw Error(SG_ERR_INVALID_ARG, "null packet arrays");
+  if (c.row_end > c.row_begin && (!c.pred || !c.lat)) throw Error(SG_ERR_INVALID_ARG, "null pred or latency_ns rows");
+  hipStream_t st = ctx->stream;
+  const bool dev = (c.flags & SG_ROUTE_OUT_DEVICE) != 0;
+  const uint32_t n = c.n_nodes, rows = c.row_end - c.row_begin;
+  ensure_links(ctx, net);
+  const uint32_t nl = net->n_links;
+  if (ni == 0) {
+    if (dev) {
+      SG_HIP(hipMemsetAsync(c.out_off, 0, ((size_t)nl + 1) * 8, st));
+      SG_HIP(hipStreamSynchronize(st));
+    } else {
+      std::fill(c.out_off, c.out_off + nl + 1, (uint64_t)0);
+    }
+    *c.total = 0;
+    return;
+  }
+  if (!ctx->paths_ret) SG_HIP(hipHostMalloc(&ctx->paths_ret, 16, hipHostMallocMapped | hipHostMallocCoherent));
+  // host arrays in: device copies
+  const uint32_t* d_pred = c.pred;
+  const uint64_t* d_lat = c.lat;
+  const uint8_t* d_watch = c.watch;
+  uint64_t* d_off = c.out_off;
+  if (!dev) {
+    const size_t cells = (size_t)rows * n;
+    uint32_t* up = ctx->l_pred.get<uint32_t>(cells);
+    uint64_t* ul = ctx->p_lat.get<uint64_t>(cells);
+    if (cells) {
+      SG_HIP(hipMemcpyAsync(up, c.pred, cells * 4, hipMemcpyHostToDevice, st));
+      SG_HIP(hipMemcpyAsync(ul, c.lat, cells * 8, hipMemcpyHostToDevice, st));
+    }
+    d_pred = up;
+    d_lat = ul;
+    if (c.watch) {
+      uint8_t* uw = ctx->tr_watch.get<uint8_t>(nl);
+      if (nl) SG_HIP(hipMemcpyAsync(uw, c.watch, nl, hipMemcpyHostToDevice, st));
+      d_watch = uw;
+    }
+    d_off = ctx->p_off.get<uint64_t>((size_t)nl + 1);
+  }
+  uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
+  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(TR_WORDS);
+  SG_HIP(hipMemsetAsync(bad, 0xff, TR_WORDS * 8, st));
+  // the link counters, the fill's cursors and the work counter: one block, zeroed
+  uint32_t* ctr = ctx->tr_cnt.get<uint32_t>(2 * (size_t)nl + 1);
+  SG_HIP(hipMemsetAsync(ctr, 0, (2 * (size_t)nl + 1) * 4, st));
+  const uint32_t n_blocks = std::max(1u, (uint32_t)(((size_t)nl + TR_SCAN_TILE - 1) / TR_SCAN_TILE));
+  const sg_hosts* h = c.hosts;
+  TraceArgs a;
+  a.l.lk_off = net->lk_off;
+  a.l.lk_tail = net->lk_tail;
+  a.l.nodes = d_idx;
+  a.l.pos = d_idx + n;
+  a.l.n = n;
+  a.l.row_begin = c.row_begin;
+  a.l.rows = rows;
+  a.l.count_cols = 0;
+  a.l.pred = d_pred;
+  a.l.counts = nullptr;
+  a.l.link_load = nullptr;
+  a.l.node_load = nullptr;
+  a.l.bad = bad;
+  a.l.scratch = nullptr;
+  a.l.vec = 0;
+  a.map = HostMap{h->ip_base, h->dense_span, h->n, h->dense, h->sorted_ip, h->sorted_host};
+  a.route = h->route;
+  a.n_hosts = h->n;
+  a.src_host = c.packets->src_host;
+  a.dst_ipv4 = c.packets->dst_ipv4;
+  a.send_time = (const unsigned long long*)c.packets->send_time_ns;
+  a.status = c.status;
+  a.n_items = ni;
+  a.hops = ctx->p_cnt.get<uint32_t>(ni);
+  a.lat = (const unsigned long long*)d_lat;
+  a.watch = d_watch;
+  a.n_links = nl;
+  a.cnt = ctr;
+  a.cur = ctr + nl;
+  a.sums = ctx->p_sums.get<unsigned long long>(n_blocks);
+  a.off = (unsigned long long*)d_off;
+  a.total = ctx->paths_ret;
+  a.key = nullptr;
+  a.exit = nullptr;
+  uint32_t* n_work = ctr + 2 * (size_t)nl;
+  const dim3 grid(grid_for(ni, TR_THREADS, 16u * (unsigned)ctx->n_cu));
+  {
+    // (work = the records, added below once the total is read)
+    TimedLaunch tl(ctx, "link_trace_count", 0.0);
+    hipLaunchKernelGGL(k_trace_count, grid, dim3(TR_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_trace_block_sums, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_trace_scan_sums, dim3(1), dim3(TR_SUMS_THREADS), 0, st, a, n_blocks);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_trace_scan_add, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
+  SG_CHECK_LAUNCH();
+  if (!dev) SG_HIP(hipMemcpyAsync(c.out_off, d_off, ((size_t)nl + 1) * 8, hipMemcpyDeviceToHost, st));
+  unsigned long long hw[TR_WORDS];
+  copy_to_host(ctx, hw, bad, sizeof(hw));
+  const uint64_t tot = *ctx->paths_ret;
+  timer_add_work(ctx, "link_trace_count", (double)tot);
+  if (hw[TR_BAD_ITEM] != ~0ull) {
+    const uint64_t p = hw[TR_BAD_ITEM] >> 3;
+    const uint32_t kind = (uint32_t)(hw[TR_BAD_ITEM] & 7);
+    static const char* const why[5] = {
+        "has a source host past the host table", "has a source host whose route row lies outside the row block",
+        "counts and has a destination address that no host holds",
+        "resolves to a route index that is not below n_nodes",
+        "counts and has a send time plus path latency past 2^64 - 1 ns"};
+    throw Error(kind == TR_ITEM_TIME ? SG_ERR_TIME_OVERFLOW : SG_ERR_INVALID_ARG,
+                "packet " + std::to_string(p) + " " + why[kind], (uint32_t)p, 0xFFFFFFFFu);
+  }
+  auto pred_error = [&](int kind) {
+    const uint32_t i = (uint32_t)(hw[kind] >> 32), j = (uint32_t)hw[kind];
+    static const char* const why[TR_WORDS] = {
+        "", "holds a node index out of range at node ",
+        "names a predecessor that no link joins to the node (not a link) at node ",
+        "does not reach its source within n_nodes steps (a cycle) from node "};
+    throw Error(SG_ERR_INVALID_ARG,
+                "the pred row of source node " + node_name(net, c.nodes[i]) + " " + why[kind] + node_name(net, c.nodes[j]),
+                i, j);
+  };
+  if (hw[TR_BAD_RANGE] != ~0ull || hw[TR_BAD_CYCLE] != ~0ull)
+    pred_error(hw[TR_BAD_RANGE] <= hw[TR_BAD_CYCLE] ? TR_BAD_RANGE : TR_BAD_CYCLE);
+  if (hw[TR_BAD_LINK] != ~0ull) pred_error(TR_BAD_LINK);
+  *c.total = tot;
+  if (tot > c.cap)
+    throw Error(SG_ERR_CAPACITY,
+                "the trace holds " + std::to_string(tot) + " records, the arrays " + std::to_string(c.cap));
+  if (tot == 0) return;
+  // staging, and the device copies of host outputs
+  const uint32_t piece = (uint32_t)knob_int("SG_LINK_TRACE_PIECE", (int)TR_PIECE_MAX, (int)TR_RANK_MAX, (int)TR_PIECE_MAX);
+  const uint64_t work_cap64 = tot / piece + tot / TR_RANK_MAX + 1;  // pieces of the segments past TR_RANK_MAX, at most
+  if (work_cap64 > 0xFFFFFFFFull) throw Error(SG_ERR_CAPACITY, "the trace holds more records than one call sorts");
+  const uint32_t work_cap = (uint32_t)work_cap64;
+  a.key = ctx->tr_key.get<uint4>(tot);
+  uint4* key2 = ctx->tr_key2.get<uint4>(tot);
+  unsigned long long* exit2 = nullptr;
+  if (c.out_exit) {
+    a.exit = ctx->tr_exit.get<unsigned long long>(tot);
+    exit2 = ctx->tr_exit2.get<unsigned long long>(tot);
+  }
+  uint2* work = ctx->tr_work.get<uint2>(work_cap);
+  TraceOut out = {c.out_packet, c.out_hop, (unsigned long long*)c.out_enter, (unsigned long long*)c.out_exit};
+  if (!dev) {
+    if (c.out_packet) out.packet = ctx->p_node.get<uint32_t>(tot);
+    if (c.out_hop) out.hop = ctx->p_link.get<uint32_t>(tot);
+    if (c.out_enter) out.enter = ctx->p_olat.get<unsigned long long>(tot);
+    if (c.out_exit) out.exit = ctx->tr_oexit.get<unsigned long long>(tot);
+  }
+  {
+    TimedLaunch tl(ctx, "link_trace_fill", (double)tot);
+    hipLaunchKernelGGL(k_trace_fill, grid, dim3(TR_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+  }
+  {
+    TimedLaunch tl(ctx, "link_trace_sort", (double)tot);
+    const unsigned long long* off = a.off;
+    const dim3 g_small(grid_for((size_t)nl * 64, TR_THREADS, 16u * (unsigned)ctx->n_cu));
+    const dim3 g_work(grid_for(work_cap, 1, 8u * (unsigned)ctx->n_cu));
+    hipLaunchKernelGGL(k_trace_sort_small, g_small, dim3(TR_THREADS), 0, st, off, nl, (const uint4*)a.key,
+                       (const unsigned long long*)a.exit, out, piece, work, work_cap, n_work);
+    SG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_trace_sort_lds, g_work, dim3(TR_THREADS), 0, st, off, (const uint4*)a.key,
+                       (const unsigned long long*)a.exit, key2, exit2, out, piece, (const uint2*)work, work_cap,
+                       (const uint32_t*)n_work);
+    SG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_trace_merge, g_work, dim3(TR_THREADS), 0, st, off, (const uint4*)key2,
+                       (const unsigned long long*)exit2, out, piece, (const uint2*)work, work_cap,
+                       (const uint32_t*)n_work);
+    SG_CHECK_LAUNCH();
+  }
+  if (!dev) {
+    if (c.out_packet) SG_HIP(hipMemcpyAsync(c.out_packet, out.packet, tot * 4, hipMemcpyDeviceToHost, st));
+    if (c.out_hop) SG_HIP(hipMemcpyAsync(c.out_hop, out.hop, tot * 4, hipMemcpyDeviceToHost, st));
+    if (c.out_enter) SG_HIP(hipMemcpyAsync(c.out_enter, out.enter, tot * 8, hipMemcpyDeviceToHost, st));
+    if (c.out_exit) SG_HIP(hipMemcpyAsync(c.out_exit, out.exit, tot * 8, hipMemcpyDeviceToHost, st));
+  }
+  SG_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+}  // namespace sg
+
+extern "C" {
+
+int32_t sg_link_trace_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts, const uint32_t* nodes, uint32_t n_nodes,
+                              uint32_t row_begin, uint32_t row_end, uint32_t flags, const uint32_t* pred,
+                              const uint64_t* latency_ns, const sg_packets* packets, const uint8_t* status,
+                              const uint8_t* watch, uint64_t* out_link_off, uint32_t* out_packet, uint32_t* out_hop,
+                              uint64_t* out_enter_ns, uint64_t* out_exit_ns, uint64_t cap, uint64_t* total) {
+  return sg::guarded(ctx, [&] {
+    sg::trace_run(sg::TraceCall{ctx, net, hosts, nodes, n_nodes, row_begin, row_end, flags, pred, latency_ns, packets,
+                                status, watch, out_link_off, out_packet, out_hop, out_enter_ns, out_exit_ns, cap,
+                                total});
+  });
+}
+
+}  // extern "C"

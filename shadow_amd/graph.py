@@ -364,6 +364,63 @@ class PathTree:
 
         return self._hop_records(npk, call)
 
+    def link_trace_round(self, hosts, packets, status=None, watch=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray,
+                                                                                 np.ndarray, np.ndarray]:
+        """The link trace of one round's batch, (link_off, packet, hop, enter_ns, exit_ns): link L
+        (in NetworkGraph.links() order) owns records link_off[L] .. link_off[L + 1], one per counted
+        packet that crossed it, in ascending (enter_ns, packet) order; hop is the crossing's place
+        on the packet's path (record off[packet] + hop - 1 of trace_round), enter_ns / exit_ns the
+        packet's send time plus the table's latency of the link's tail / head in the sender's row.
+        hosts, packets and status as in trace_round.  watch: None (every link), a u8 / bool mask
+        of one entry per link, or a list of link numbers; a link not watched owns no record
+        (sg_link_trace_packets)."""
+        import torch
+
+        npk = len(packets)
+        if status is not None:
+            status = getattr(status, "status", status)
+            if not isinstance(status, torch.Tensor):
+                status = torch.from_numpy(np.ascontiguousarray(status, dtype=np.uint8))
+            status = status.to(device=packets.src_host.device).contiguous()
+            if status.element_size() != 1 or status.numel() < npk:
+                raise ValueError(f"status: {npk} u8 entries, one per packet")
+        g, n = self._graph, len(self.nodes)
+        n_links = len(g.links()[0])
+        if watch is not None:
+            w = np.asarray(watch)
+            if w.dtype == np.bool_ or (w.dtype == np.uint8 and w.shape == (n_links,)):
+                if w.shape != (n_links,):
+                    raise ValueError(f"watch: a mask of {n_links} entries, one per link")
+                mask = w.astype(np.uint8)
+            else:
+                idx = w.astype(np.int64).ravel()
+                if len(idx) and (idx.min() < 0 or idx.max() >= n_links):
+                    raise ValueError(f"watch: link numbers below {n_links}")
+                mask = np.zeros(n_links, np.uint8)
+                mask[idx] = 1
+            watch = np.ascontiguousarray(mask)
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        tlat = np.ascontiguousarray(self.latency_ns, dtype=np.uint64)
+        p = packets.c_struct()
+        off = np.zeros(n_links + 1, np.uint64)
+        total = C.c_uint64()
+        cap = 8 * npk + 64
+        while True:  # a first call at a guessed capacity, a second at the total the first reported
+            pkt, hop = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+            enter, leave = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+            rc = load().sg_link_trace_packets(
+                g.ctx.handle, g._ensure_net(), hosts.handle, self.nodes.ctypes.data, n, 0, self.n_sources, 0,
+                pred.ctypes.data, tlat.ctypes.data, C.byref(p),
+                None if status is None else C.c_void_p(status.data_ptr()),
+                None if watch is None else watch.ctypes.data, off.ctypes.data, pkt.ctypes.data, hop.ctypes.data,
+                enter.ctypes.data, leave.ctypes.data, cap, C.byref(total))
+            if rc != _capi.SG_ERR_CAPACITY or total.value <= cap:
+                break
+            cap = total.value
+        check(g.ctx.handle, rc)
+        t = total.value
+        return off, pkt[:t], hop[:t], enter[:t], leave[:t]
+
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
         taking at each step any arc that is tight: one whose fold gives the table's cell of the
@@ -685,6 +742,33 @@ class NetworkGraph:
         if rc != _capi.SG_ERR_CAPACITY:
             check(self.ctx.handle, rc)
         return total.value
+
+    def link_trace_packets_device(self, hosts, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int,
+                                  latency_ptr: int, packets, status_ptr: int, watch_ptr: int, link_off_ptr: int,
+                                  packet_ptr: int, hop_ptr: int, enter_ptr: int, exit_ptr: int,
+                                  cap: int) -> Tuple[int, int]:
+        """The link trace of one round's batch (a PacketBatch from hosts of `hosts`, a HostTable)
+        through device pred rows [row_begin, row_end) and the same rows of the device latency
+        table, into caller-owned device arrays: link_off (u64, one entry per link of links() and
+        one more), then per record packet u32, hop u32, enter_ns u64, exit_ns u64, each of `cap`
+        records and sorted by (enter_ns, packet) inside a link's segment; any record array may be
+        0, not all four.  status (device u8, 0: every packet) as in tree_paths_packets_device;
+        watch (device u8 per link, 0: every link) empties the segments of the links it marks 0.
+        Returns (status code, record total): SG_OK, or SG_ERR_CAPACITY when the total exceeds
+        `cap` (link_off is complete then and no record was written); any other status raises
+        (sg_link_trace_packets)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        total = C.c_uint64()
+        p = packets.c_struct()
+        rc = load().sg_link_trace_packets(
+            self.ctx.handle, self._ensure_net(), hosts.handle, used.ctypes.data, len(used), int(row_begin),
+            int(row_end), _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(latency_ptr or None),
+            C.byref(p), C.c_void_p(status_ptr or None), C.c_void_p(watch_ptr or None),
+            C.c_void_p(link_off_ptr or None), C.c_void_p(packet_ptr or None), C.c_void_p(hop_ptr or None),
+            C.c_void_p(enter_ptr or None), C.c_void_p(exit_ptr or None), int(cap), C.byref(total))
+        if rc != _capi.SG_ERR_CAPACITY:
+            check(self.ctx.handle, rc)
+        return rc, total.value
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

@@ -666,4 +666,25 @@ unsafe extern "C" {
     /// The exact exchange: counts is the host n x n matrix (member b's records for member r).
     pub fn sg_group_alltoallv_records(g: *mut sg_group, send: *mut *const sg_record, counts: *const u32,
                                       recv: *mut *mut sg_record) -> i32;
+
+    // ---- link loads and link trace across a group: a round sharded by source row block ----
+    /// The member whose device-found error the group's last call reported, or u32::MAX.
+    pub fn sg_group_last_error_member(g: *const sg_group) -> u32;
+    /// sg_link_load_packets on every member at once; the members' sums are added into root's
+    /// arrays by one kernel, after every member validated: any error leaves them untouched.
+    pub fn sg_group_link_load_packets(g: *mut sg_group, nets: *mut *mut sg_net, hosts: *mut *mut sg_hosts,
+                                      nodes: *const u32, n_nodes: u32, row_begin: *const u32, row_end: *const u32,
+                                      pred: *mut *const u32, packets: *const sg_packets, status: *mut *const u8,
+                                      weight: *mut *const u32, root: u32, out_link_load: *mut u64,
+                                      out_node_load: *mut u64, out_hops: *mut *mut u32) -> i32;
+    /// sg_link_trace_packets on every member at once, the members' sorted segments merged on root:
+    /// link L's records ascend in (enter_ns, member, member-local packet); out_packet = packet_base[m] + p.
+    pub fn sg_group_link_trace_packets(g: *mut sg_group, nets: *mut *mut sg_net, hosts: *mut *mut sg_hosts,
+                                       nodes: *const u32, n_nodes: u32, row_begin: *const u32, row_end: *const u32,
+                                       pred: *mut *const u32, latency_ns: *mut *const u64,
+                                       packets: *const sg_packets, status: *mut *const u8, watch: *const u8,
+                                       packet_base: *const u32, root: u32, out_link_off: *mut u64,
+                                       out_packet: *mut u32, out_member: *mut u8, out_hop: *mut u32,
+                                       out_enter_ns: *mut u64, out_exit_ns: *mut u64, cap: u64,
+                                       total: *mut u64) -> i32;
 }

@@ -1263,6 +1263,97 @@ int32_t sg_group_exchange_padded(sg_group* g, const sg_record** send_padded, sg_
  * event ordering.  Does not synchronise. */
 int32_t sg_group_alltoallv_records(sg_group* g, const sg_record** send, const uint32_t* counts, sg_record** recv);
 
+/* ---- link loads and link trace across a group (additive to ABI 7) -----------
+ * sg_link_load_packets and sg_link_trace_packets for a round that a group shards by
+ * source row block: member m holds rows [row_begin[m], row_end[m]) of the tree (and,
+ * for the trace, of the table), and packets[m] are the sends of its own sources.
+ * Rounds, packets, the counting rule, address resolution, link numbering, the record
+ * and the error kinds are those calls'; nothing is redefined here.  Every member
+ * walks its own batch on its own stream, all members at once, and the results are
+ * combined on the device of member `root`.  (sg_tree_paths[_packets] needs no group
+ * form: its output is per packet and a member's packets are its own, so n calls, one
+ * per member, are the answer.)
+ *
+ * Per member, arrays of n entries, entry m on member m's context and device (always
+ * device memory; there is no host-array mode): nets[m], the same graph on every
+ * member, checked as in sg_group_routing_info_fill; hosts[m]; pred[m] (and
+ * latency_ns[m]), rows [row_begin[m], row_end[m]) row-major from row_begin[m];
+ * packets[m], an sg_packets in the host array `packets` whose pointers are device
+ * memory of member m; status[m], or NULL (`status` itself may be NULL: every packet of
+ * every member counts).  row_begin and row_end are host arrays; the ranges need not be
+ * row_range's, an empty one is legal, and so is n_packets == 0.  `nodes` (n_nodes
+ * entries, host) is one permutation for all members.
+ *
+ * sg_group_link_load_packets: weight[m] as `weight` of sg_link_load_packets (NULL, or
+ * a NULL `weight`: 1).  out_link_load (n_links u64) and out_node_load (n_nodes u64)
+ * lie on root's device and are ADDED to; out_hops[m] (n_packets of m, u32) lies on
+ * member m's device.  Any may be NULL (out_hops itself, or single entries), not all.
+ * Each member sums into a zeroed accumulator of its own; after every member's flags
+ * have been read, one kernel on root's stream adds the n accumulators into the
+ * caller's arrays, and the call returns when it has finished.  The result equals
+ * sg_link_load_packets on one context holding all rows and the members' batches
+ * concatenated in member order.  Because the add is deferred, ANY error leaves
+ * out_link_load and out_node_load untouched (stronger than the single call);
+ * out_hops is undefined after a device-found error.
+ *
+ * sg_group_link_trace_packets: `watch` is a HOST mask of n_links u8, or NULL; the
+ * library uploads it to every member.  packet_base: host, n u32, or NULL = the
+ * exclusive prefix sums of the members' n_packets (the packet's index in the
+ * concatenated batch).  Outputs on root's device: out_link_off (n_links + 1 u64,
+ * required), out_packet u32, out_member u8, out_hop u32, out_enter_ns u64,
+ * out_exit_ns u64, each of capacity `cap` records; any record array may be NULL, not
+ * all five.  `total` is a host pointer.  Link L owns records
+ * [out_link_off[L], out_link_off[L + 1]) in ascending (enter_ns, member, member-local
+ * packet index) order; out_member = m, out_packet = packet_base[m] + p.  The key is
+ * unique whatever the bases are.  With the default bases the output equals
+ * sg_link_trace_packets on one context with all rows and the concatenated batch, and
+ * out_member tells where each record came from; with n = 1 it is that call's output,
+ * bit for bit.  total > cap: SG_ERR_CAPACITY, out_link_off and *total complete, no
+ * record array written; the sizing call works as there (a real record array, cap 0).
+ * With no packet in any member out_link_off is all zero and *total = 0.  Every member
+ * counts and scans; the host reads flags and totals; root sums the members' offsets
+ * (no second scan); every member fills and sorts its own segments; one kernel on root
+ * places each record by rank among the members' sorted segments of its link (binary
+ * searches on enter_ns alone); the call ends with one wait on root's stream.
+ *
+ * Errors.  SG_ERR_INVALID_ARG with every output untouched: NULL arguments; a net or
+ * hosts not of its member's context; graphs that differ; root >= n; no output at all;
+ * `nodes` not a permutation; a bad row range; NULL pred (or latency_ns) rows of a
+ * non-empty range; NULL packet arrays of a non-empty batch.  Found on the device: the
+ * single call's kinds with its precedence inside a member (packet kinds, then the
+ * time overflow, then pred kinds); across members the LOWEST-NUMBERED failing member
+ * is reported: sg_group_last_error names it ("member 2: packet 17 ..."),
+ * sg_group_last_error_pair gives its pair (a packet index there is member-local) and
+ * sg_group_last_error_member the member.  out_link_off, the record arrays and the
+ * load arrays are untouched after a device-found error.
+ * sg_group_last_error_member: the member whose device-found error the group's last
+ * call reported; UINT32_MAX when that call succeeded, failed for another reason, or g
+ * is NULL.
+ * Timers, on root's context: "group_link_reduce" (work = accumulator words read),
+ * "group_trace_offsets" and "group_trace_merge" (work = records); the members' own
+ * timers are the single calls' ("link_packets", "link_trace_count",
+ * "link_trace_fill", "link_trace_sort"). */
+uint32_t sg_group_last_error_member(const sg_group* g);
+int32_t sg_group_link_load_packets(sg_group* g, sg_net** nets, sg_hosts** hosts,
+                                   const uint32_t* nodes, uint32_t n_nodes,
+                                   const uint32_t* row_begin, const uint32_t* row_end,
+                                   const uint32_t** pred, const sg_packets* packets,
+                                   const uint8_t** status, const uint32_t** weight,
+                                   uint32_t root,
+                                   uint64_t* out_link_load, uint64_t* out_node_load,
+                                   uint32_t** out_hops);
+int32_t sg_group_link_trace_packets(sg_group* g, sg_net** nets, sg_hosts** hosts,
+                                    const uint32_t* nodes, uint32_t n_nodes,
+                                    const uint32_t* row_begin, const uint32_t* row_end,
+                                    const uint32_t** pred, const uint64_t** latency_ns,
+                                    const sg_packets* packets, const uint8_t** status,
+                                    const uint8_t* watch, const uint32_t* packet_base,
+                                    uint32_t root,
+                                    uint64_t* out_link_off,
+                                    uint32_t* out_packet, uint8_t* out_member, uint32_t* out_hop,
+                                    uint64_t* out_enter_ns, uint64_t* out_exit_ns,
+                                    uint64_t cap, uint64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

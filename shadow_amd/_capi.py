@@ -63,6 +63,7 @@ EXPORTED = [
     "sg_routing_tree", "sg_routing_build_tree", "sg_tree_path",
     "sg_net_links", "sg_net_edge_links", "sg_link_load", "sg_link_load_packets",
     "sg_tree_paths", "sg_tree_paths_packets", "sg_link_trace_packets",
+    "sg_group_last_error_member", "sg_group_link_load_packets", "sg_group_link_trace_packets",
 ]
 
 
@@ -324,6 +325,11 @@ def load(path: str | None = None):
         "sg_group_routing_info_fill": (i32, [vp, vp, vp, u32, vp]),
         "sg_group_exchange_padded": (i32, [vp, vp, vp, u32, vp, vp]),
         "sg_group_alltoallv_records": (i32, [vp, vp, vp, vp]),
+        "sg_group_last_error_member": (u32, [vp]),
+        "sg_group_link_load_packets": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, C.POINTER(sg_packets), vp, vp, u32,
+                                             vp, vp, vp]),
+        "sg_group_link_trace_packets": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(sg_packets), vp, vp, vp,
+                                              u32, vp, vp, vp, vp, vp, vp, u64, u64p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

@@ -32,16 +32,11 @@
 
 #include "sg_internal.h"
 
-struct sg_group {
-  std::vector<sg_ctx*> ctxs;
-  std::vector<hipEvent_t> sent, pulled;  // one per member, created on the member's device
-  std::string last_error;
-  uint32_t err_row = 0, err_col = 0;
-};
+// (struct sg_group, group_guarded and set_device: sg_internal.h, shared with sg_group_trace.hip)
 
 namespace sg {
 
-constexpr uint32_t GROUP_MAX = 64;  // sg_round_ret::recv_cnt
+// (GROUP_MAX: sg_internal.h)
 constexpr int PULL_THREADS = 256;
 constexpr int PULL_UNROLL = 4;  // 16-byte loads in flight per thread
 
@@ -86,35 +81,6 @@ __global__ void __launch_bounds__(PULL_THREADS) k_group_pull(PullArgs a, uint32_
 }
 
 static thread_local std::string g_group_create_error;
-
-// Map exceptions to a status and the group's last error (sg::guarded, for a group).
-template <class F>
-static int32_t group_guarded(sg_group* g, F&& fn) {
-  if (!g) return SG_ERR_INVALID_ARG;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  int32_t rc = SG_OK;
-  try {
-    fn();
-    g->last_error.clear();
-    g->err_row = g->err_col = 0;
-  } catch (const Error& e) {
-    g->last_error = e.what();
-    g->err_row = e.row;
-    g->err_col = e.col;
-    rc = e.code;
-  } catch (const std::bad_alloc&) {
-    g->last_error = "host out of memory";
-    rc = SG_ERR_OOM;
-  } catch (const std::exception& e) {
-    g->last_error = e.what();
-    rc = SG_ERR_DEVICE;
-  }
-  (void)hipSetDevice(prev);  // the calls below walk over the members' devices
-  return rc;
-}
-
-static void set_device(const sg_ctx* c) { SG_HIP(hipSetDevice(c->device)); }
 
 // Steps 1 and 2's waits, then `work(r)` on every owner's stream, then steps 2's record and 3.
 template <class F>
@@ -248,6 +214,8 @@ void sg_group_last_error_pair(const sg_group* g, uint32_t* row, uint32_t* col) {
   if (row) *row = g ? g->err_row : 0;
   if (col) *col = g ? g->err_col : 0;
 }
+
+uint32_t sg_group_last_error_member(const sg_group* g) { return g ? g->err_member : 0xFFFFFFFFu; }
 
 int32_t sg_group_routing_info_fill(sg_group* g, sg_net** nets, const uint32_t* nodes, uint32_t flags,
                                    sg_routing_info* ri) {

@@ -277,7 +277,49 @@ struct sg_routing_info {
   ~sg_routing_info();
 };
 
+// A device group (sg_group.hip; sg_group_trace.hip holds its link loads and link trace).
+struct sg_group {
+  std::vector<sg_ctx*> ctxs;
+  std::vector<hipEvent_t> sent, pulled;  // one per member, created on the member's device
+  std::string last_error;
+  uint32_t err_row = 0, err_col = 0;
+  uint32_t err_member = 0xFFFFFFFFu;  // the member whose error the last call reported, or UINT32_MAX
+};
+
 namespace sg {
+
+constexpr uint32_t GROUP_MAX = 64;  // members of a group (sg_round_ret::recv_cnt)
+
+inline void set_device(const sg_ctx* c) { SG_HIP(hipSetDevice(c->device)); }
+
+// Map exceptions to a status and the group's last error (sg::guarded, for a group).  A call that
+// reports a member's error sets err_member before it throws.
+template <class F>
+int32_t group_guarded(sg_group* g, F&& fn) {
+  if (!g) return SG_ERR_INVALID_ARG;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  int32_t rc = SG_OK;
+  g->err_member = 0xFFFFFFFFu;
+  try {
+    fn();
+    g->last_error.clear();
+    g->err_row = g->err_col = 0;
+  } catch (const Error& e) {
+    g->last_error = e.what();
+    g->err_row = e.row;
+    g->err_col = e.col;
+    rc = e.code;
+  } catch (const std::bad_alloc&) {
+    g->last_error = "host out of memory";
+    rc = SG_ERR_OOM;
+  } catch (const std::exception& e) {
+    g->last_error = e.what();
+    rc = SG_ERR_DEVICE;
+  }
+  (void)hipSetDevice(prev);  // the calls walk over the members' devices
+  return rc;
+}
 
 // Run `fn` with the context's device current; map exceptions to status codes.
 template <class F>

@@ -56,6 +56,8 @@
 // resolved through the hosts' address map, then the tree path walked from the destination up to
 // the source, the packet's weight added to every link and node on the way.  Cost in proportion
 // to packets x hops; no per-row state, so no node limit and one path for every graph size.
+// Its host side is the halves of sg_walks.h (link_packets_check / _enqueue / _finish): the entry
+// point runs them back to back, a device group (sg_group_trace.hip) per member.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -66,6 +68,7 @@
 #include "sg_internal.h"
 #include "sg_knobs.h"
 #include "sg_links.h"
+#include "sg_walks.h"
 
 namespace sg {
 
@@ -288,17 +291,7 @@ enum { LP_PKT_SRC = 0, LP_PKT_ROW = 1, LP_PKT_DST = 2, LP_PKT_ROUTE = 3 };
 // wait; held back, LP_HOPS hops pay it once.  (The per-hop form was not measured.)
 constexpr int LP_HOPS = 4;
 
-struct LinkPacketArgs {
-  LinkArgs l;  // (counts, count_cols, scratch and vec unused; bad = LP_WORDS words)
-  HostMap map;
-  const uint32_t* route;  // host -> route index
-  uint32_t n_hosts, n_packets;
-  const uint32_t* src_host;
-  const uint32_t* dst_ipv4;
-  const uint8_t* status;   // or null: every packet counts
-  const uint32_t* weight;  // or null: 1
-  uint32_t* hops;          // or null
-};
+// (LinkPacketArgs: sg_walks.h)
 
 // One counted packet's walk: weight w from column j up row i's tree; returns its hops.
 __device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t i, uint32_t j, unsigned long long w) {
@@ -580,6 +573,98 @@ static void link_check_net(sg_ctx* ctx, sg_net* net) {
   if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
 }
 
+// ---- sg_link_load_packets' halves (sg_walks.h)
+void link_packets_check(const LinkPacketsCall& c, bool check_nodes) {
+  link_check_net(c.ctx, c.net);
+  if (!c.hosts || c.hosts->ctx != c.ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
+  if (c.n_nodes != c.net->n_nodes)
+    throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
+  if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
+  if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  if (check_nodes) check_node_list(c.net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
+  if (!c.packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
+  if (c.packets->n_packets && (!c.packets->src_host || !c.packets->dst_ipv4))
+    throw Error(SG_ERR_INVALID_ARG, "null packet arrays");
+  if (c.row_end > c.row_begin && !c.pred) throw Error(SG_ERR_INVALID_ARG, "null pred rows");
+}
+
+void link_packets_enqueue(const LinkPacketsCall& c) {
+  sg_ctx* ctx = c.ctx;
+  sg_net* net = c.net;
+  const sg_hosts* hosts = c.hosts;
+  hipStream_t st = ctx->stream;
+  const uint32_t n = c.n_nodes, np = c.packets->n_packets;
+  uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
+  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LP_WORDS);
+  SG_HIP(hipMemsetAsync(bad, 0xff, LP_COUNTED * 8, st));
+  SG_HIP(hipMemsetAsync(bad + LP_COUNTED, 0, 8, st));
+  LinkPacketArgs a;
+  a.l.lk_off = net->lk_off;
+  a.l.lk_tail = net->lk_tail;
+  a.l.nodes = d_idx;
+  a.l.pos = d_idx + n;
+  a.l.n = n;
+  a.l.row_begin = c.row_begin;
+  a.l.rows = c.row_end - c.row_begin;
+  a.l.count_cols = 0;
+  a.l.pred = c.pred;
+  a.l.counts = nullptr;
+  a.l.link_load = (unsigned long long*)c.link_load;
+  a.l.node_load = (unsigned long long*)c.node_load;
+  a.l.bad = bad;
+  a.l.scratch = nullptr;
+  a.l.vec = 0;
+  a.map = HostMap{hosts->ip_base, hosts->dense_span, hosts->n, hosts->dense, hosts->sorted_ip, hosts->sorted_host};
+  a.route = hosts->route;
+  a.n_hosts = hosts->n;
+  a.n_packets = np;
+  a.src_host = c.packets->src_host;
+  a.dst_ipv4 = c.packets->dst_ipv4;
+  a.status = c.status;
+  a.weight = c.weight;
+  a.hops = c.hops;
+  // (work = the packets walked, added by the finish once the count is read)
+  TimedLaunch tl(ctx, "link_packets", 0.0);
+  const dim3 grid(grid_for(np, 256, 16u * (unsigned)ctx->n_cu));
+  if (knob_int("SG_LINK_COMBINE", 1) != 0)
+    hipLaunchKernelGGL(k_link_packets<true>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_link_packets<false>, grid, dim3(256), 0, st, a);
+  SG_CHECK_LAUNCH();
+}
+
+void link_packets_finish(const LinkPacketsCall& c) {
+  sg_ctx* ctx = c.ctx;
+  unsigned long long h[LP_WORDS];
+  copy_to_host(ctx, h, ctx->l_flag.get<unsigned long long>(LP_WORDS), sizeof(h));
+  timer_add_work(ctx, "link_packets", (double)h[LP_COUNTED]);
+  // read_timer("link_packets_counted") = (0, the packets the last call counted, 0)
+  timer_set_counter(ctx, "link_packets_counted", 0.0, h[LP_COUNTED]);
+  if (h[LP_BAD_PACKET] != ~0ull) {
+    const uint64_t p = h[LP_BAD_PACKET] >> 2;
+    static const char* const why[4] = {
+        "has a source host past the host table", "has a source host whose route row lies outside the row block",
+        "counts and has a destination address that no host holds",
+        "resolves to a route index that is not below n_nodes"};
+    throw Error(SG_ERR_INVALID_ARG, "packet " + std::to_string(p) + " " + why[h[LP_BAD_PACKET] & 3], (uint32_t)p,
+                0xFFFFFFFFu);
+  }
+  int kind = -1;
+  for (int k = LP_BAD_RANGE; k <= LP_BAD_CYCLE; k++)
+    if (h[k] != ~0ull && (kind < 0 || h[k] < h[kind])) kind = k;
+  if (kind >= 0) {
+    const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
+    static const char* const why[LP_BAD_CYCLE + 1] = {
+        "", "holds a node index out of range at node ",
+        "names a predecessor that no link joins to the node (not a link) at node ",
+        "does not reach its source within n_nodes steps (a cycle) from node "};
+    throw Error(SG_ERR_INVALID_ARG,
+                "the pred row of source node " + node_name(c.net, c.nodes[i]) + " " + why[kind] +
+                    node_name(c.net, c.nodes[j]),
+                i, j);
+  }
+}
+
 }  // namespace sg
 
 extern "C" {
@@ -661,110 +746,35 @@ int32_t sg_link_load_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts, const ui
                              uint64_t* out_link_load, uint64_t* out_node_load, uint32_t* out_hops) {
   return sg::guarded(ctx, [&] {
     using namespace sg;
-    link_check_net(ctx, net);
-    if (!hosts || hosts->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
-    if (n_nodes != net->n_nodes)
-      throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
-    if (n_nodes && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-    if (row_begin > row_end || row_end > n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
-    check_node_list(net, nodes, n_nodes);  // in range and none twice: with n_nodes entries, a permutation
+    LinkPacketsCall c{ctx,     net,    hosts,  nodes,         n_nodes,       row_begin, row_end,
+                      pred,    packets, status, weight,        out_link_load, out_node_load, out_hops};
+    link_packets_check(c, true);
     if (!out_link_load && !out_node_load && !out_hops) throw Error(SG_ERR_INVALID_ARG, "null output");
-    if (!packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
     const uint32_t np = packets->n_packets;
-    if (np && (!packets->src_host || !packets->dst_ipv4)) throw Error(SG_ERR_INVALID_ARG, "null packet arrays");
-    if (row_end > row_begin && !pred) throw Error(SG_ERR_INVALID_ARG, "null pred rows");
     if (np == 0) return;
     ensure_links(ctx, net);
     hipStream_t st = ctx->stream;
     const uint32_t n = n_nodes, rows = row_end - row_begin, nl = net->n_links;
     const bool dev = (flags & SG_ROUTE_OUT_DEVICE) != 0;
     // host rows in, host sums out: the device sums start at zero and are added on the host
-    const uint32_t* d_pred = pred;
-    uint64_t* d_link = out_link_load;
-    uint64_t* d_node = out_node_load;
-    uint32_t* d_hops = out_hops;
     if (!dev) {
       uint32_t* up = ctx->l_pred.get<uint32_t>((size_t)rows * n);
       if (rows) SG_HIP(hipMemcpyAsync(up, pred, (size_t)rows * n * 4, hipMemcpyHostToDevice, st));
-      d_pred = up;
-      d_link = out_link_load ? ctx->l_link.get<uint64_t>(nl) : nullptr;
-      d_node = out_node_load ? ctx->l_node.get<uint64_t>(n) : nullptr;
-      d_hops = out_hops ? ctx->l_hops.get<uint32_t>(np) : nullptr;
-      if (d_link) SG_HIP(hipMemsetAsync(d_link, 0, std::max<size_t>((size_t)nl * 8, 8), st));
-      if (d_node) SG_HIP(hipMemsetAsync(d_node, 0, (size_t)n * 8, st));
+      c.pred = up;
+      c.link_load = out_link_load ? ctx->l_link.get<uint64_t>(nl) : nullptr;
+      c.node_load = out_node_load ? ctx->l_node.get<uint64_t>(n) : nullptr;
+      c.hops = out_hops ? ctx->l_hops.get<uint32_t>(np) : nullptr;
+      if (c.link_load) SG_HIP(hipMemsetAsync(c.link_load, 0, std::max<size_t>((size_t)nl * 8, 8), st));
+      if (c.node_load) SG_HIP(hipMemsetAsync(c.node_load, 0, (size_t)n * 8, st));
     }
-    uint32_t* d_idx = link_node_index(ctx, nodes, n);
-    unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LP_WORDS);
-    SG_HIP(hipMemsetAsync(bad, 0xff, LP_COUNTED * 8, st));
-    SG_HIP(hipMemsetAsync(bad + LP_COUNTED, 0, 8, st));
-    LinkPacketArgs a;
-    a.l.lk_off = net->lk_off;
-    a.l.lk_tail = net->lk_tail;
-    a.l.nodes = d_idx;
-    a.l.pos = d_idx + n;
-    a.l.n = n;
-    a.l.row_begin = row_begin;
-    a.l.rows = rows;
-    a.l.count_cols = 0;
-    a.l.pred = d_pred;
-    a.l.counts = nullptr;
-    a.l.link_load = (unsigned long long*)d_link;
-    a.l.node_load = (unsigned long long*)d_node;
-    a.l.bad = bad;
-    a.l.scratch = nullptr;
-    a.l.vec = 0;
-    a.map = HostMap{hosts->ip_base, hosts->dense_span, hosts->n, hosts->dense, hosts->sorted_ip, hosts->sorted_host};
-    a.route = hosts->route;
-    a.n_hosts = hosts->n;
-    a.n_packets = np;
-    a.src_host = packets->src_host;
-    a.dst_ipv4 = packets->dst_ipv4;
-    a.status = status;
-    a.weight = weight;
-    a.hops = d_hops;
-    {
-      // (work = the packets walked, added below once the count is read)
-      TimedLaunch tl(ctx, "link_packets", 0.0);
-      const dim3 grid(grid_for(np, 256, 16u * (unsigned)ctx->n_cu));
-      if (knob_int("SG_LINK_COMBINE", 1) != 0)
-        hipLaunchKernelGGL(k_link_packets<true>, grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL(k_link_packets<false>, grid, dim3(256), 0, st, a);
-      SG_CHECK_LAUNCH();
-    }
-    std::vector<uint64_t> h_link(!dev && d_link ? nl : 0), h_node(!dev && d_node ? n : 0);
+    link_packets_enqueue(c);
+    std::vector<uint64_t> h_link(!dev && c.link_load ? nl : 0), h_node(!dev && c.node_load ? n : 0);
     if (!dev) {
-      if (d_link && nl) SG_HIP(hipMemcpyAsync(h_link.data(), d_link, (size_t)nl * 8, hipMemcpyDeviceToHost, st));
-      if (d_node) SG_HIP(hipMemcpyAsync(h_node.data(), d_node, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-      if (d_hops) SG_HIP(hipMemcpyAsync(out_hops, d_hops, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+      if (c.link_load && nl) SG_HIP(hipMemcpyAsync(h_link.data(), c.link_load, (size_t)nl * 8, hipMemcpyDeviceToHost, st));
+      if (c.node_load) SG_HIP(hipMemcpyAsync(h_node.data(), c.node_load, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+      if (c.hops) SG_HIP(hipMemcpyAsync(out_hops, c.hops, (size_t)np * 4, hipMemcpyDeviceToHost, st));
     }
-    unsigned long long h[LP_WORDS];
-    copy_to_host(ctx, h, bad, sizeof(h));
-    timer_add_work(ctx, "link_packets", (double)h[LP_COUNTED]);
-    // read_timer("link_packets_counted") = (0, the packets the last call counted, 0)
-    timer_set_counter(ctx, "link_packets_counted", 0.0, h[LP_COUNTED]);
-    if (h[LP_BAD_PACKET] != ~0ull) {
-      const uint64_t p = h[LP_BAD_PACKET] >> 2;
-      static const char* const why[4] = {
-          "has a source host past the host table", "has a source host whose route row lies outside the row block",
-          "counts and has a destination address that no host holds",
-          "resolves to a route index that is not below n_nodes"};
-      throw Error(SG_ERR_INVALID_ARG, "packet " + std::to_string(p) + " " + why[h[LP_BAD_PACKET] & 3], (uint32_t)p,
-                  0xFFFFFFFFu);
-    }
-    int kind = -1;
-    for (int k = LP_BAD_RANGE; k <= LP_BAD_CYCLE; k++)
-      if (h[k] != ~0ull && (kind < 0 || h[k] < h[kind])) kind = k;
-    if (kind >= 0) {
-      const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
-      static const char* const why[LP_BAD_CYCLE + 1] = {
-          "", "holds a node index out of range at node ",
-          "names a predecessor that no link joins to the node (not a link) at node ",
-          "does not reach its source within n_nodes steps (a cycle) from node "};
-      throw Error(SG_ERR_INVALID_ARG,
-                  "the pred row of source node " + node_name(net, nodes[i]) + " " + why[kind] + node_name(net, nodes[j]), i,
-                  j);
-    }
+    link_packets_finish(c);
     for (uint32_t k = 0; k < (uint32_t)h_link.size(); k++) out_link_load[k] += h_link[k];
     for (uint32_t v = 0; v < (uint32_t)h_node.size(); v++) out_node_load[v] += h_node[v];
   });

@@ -36,7 +36,9 @@
 //                            keys below its own (a binary search).
 // The host reads the flag words and the total between 2 and 3 (total > cap: SG_ERR_CAPACITY, with
 // out_link_off and *total complete and no record written) and waits for the stream after 4: two
-// synchronisations.
+// synchronisations.  Steps 1-2 and 3-4 are the halves of sg_walks.h (trace_enqueue_count /
+// trace_finish_count / trace_enqueue_sort): sg_link_trace_packets runs them back to back, a
+// device group (sg_group_trace.hip) runs them per member and merges the members' sorted segments.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -46,6 +48,7 @@
 #include "sg_internal.h"
 #include "sg_knobs.h"
 #include "sg_links.h"
+#include "sg_walks.h"
 
 namespace sg {
 namespace {
@@ -60,37 +63,7 @@ constexpr uint32_t TR_SUMS_THREADS = 1024;
 constexpr uint32_t TR_RANK_MAX = 64;     // a segment up to one wave: rank sort in registers
 constexpr uint32_t TR_PIECE_MAX = 2048;  // keys of one piece in LDS: 16 bytes x 2048 = 32 KiB
 
-struct TraceArgs {
-  LinkArgs l;  // (counts, count_cols, link_load, node_load, scratch and vec unused; bad = TR_WORDS words)
-  HostMap map;
-  const uint32_t* route;  // host -> route index
-  uint32_t n_hosts;
-  const uint32_t* src_host;
-  const uint32_t* dst_ipv4;
-  const unsigned long long* send_time;
-  const uint8_t* status;  // or null: every packet counts
-  uint32_t n_items;       // packets
-  uint32_t* hops;         // per packet, from the count walk
-  const unsigned long long* lat;  // rows [row_begin, row_begin + rows) of the table
-  const uint8_t* watch;           // per link, or null: every link
-  uint32_t n_links;
-  uint32_t* cnt;  // records per link
-  uint32_t* cur;  // the fill's cursor per link
-  unsigned long long* sums;  // the scan's block sums, then their exclusive prefix
-  unsigned long long* off;   // out_link_off
-  unsigned long long* total;  // the mapped word
-  // staging: (enter lo, enter hi, packet, hop) and the exit time (or null)
-  uint4* key;
-  unsigned long long* exit;
-};
-
-// The four record arrays, any of them null.
-struct TraceOut {
-  uint32_t* packet;
-  uint32_t* hop;
-  unsigned long long* enter;
-  unsigned long long* exit;
-};
+// (TraceArgs, TraceOut: sg_walks.h)
 
 // Packet p's (row, column); returns whether it has records.  kind: TR_ITEM_* when the packet is in
 // error, else LINK_NONE.  sg_link_load_packets' rule, the resolve sg_hosts.h's.
@@ -464,28 +437,10 @@ __global__ void __launch_bounds__(TR_THREADS) k_trace_merge(const unsigned long 
   }
 }
 
-// ---- host
-struct TraceCall {
-  sg_ctx* ctx;
-  sg_net* net;
-  sg_hosts* hosts;
-  const uint32_t* nodes;
-  uint32_t n_nodes, row_begin, row_end, flags;
-  const uint32_t* pred;
-  const uint64_t* lat;
-  const sg_packets* packets;
-  const uint8_t* status;
-  const uint8_t* watch;
-  uint64_t* out_off;
-  uint32_t* out_packet;
-  uint32_t* out_hop;
-  uint64_t* out_enter;
-  uint64_t* out_exit;
-  uint64_t cap;
-  uint64_t* total;
-};
+}  // namespace
 
-void trace_run(const TraceCall& c) {
+// ---- host: the halves of sg_walks.h, and the single-context call that runs them back to back
+void trace_check(const TraceCall& c, bool check_nodes) {
   sg_ctx* ctx = c.ctx;
   sg_net* net = c.net;
   if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
@@ -493,53 +448,23 @@ void trace_run(const TraceCall& c) {
     throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
   if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
   if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
-  check_node_list(net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
-  if (!c.out_packet && !c.out_hop && !c.out_enter && !c.out_exit) throw Error(SG_ERR_INVALID_ARG, "no record output");
-  if (!c.out_off || !c.total) throw Error(SG_ERR_INVALID_ARG, "null out_link_off or total");
+  if (check_nodes) check_node_list(net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
   if (!c.hosts || c.hosts->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
   if (!c.packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
   const uint32_t ni = c.packets->n_packets;
   if (ni && (!c.packets->src_host || !c.packets->dst_ipv4 || !c.packets->send_time_ns))
     throw Error(SG_ERR_INVALID_ARG, "null packet arrays");
   if (c.row_end > c.row_begin && (!c.pred || !c.lat)) throw Error(SG_ERR_INVALID_ARG, "null pred or latency_ns rows");
+}
+
+void trace_enqueue_count(const TraceCall& c, TraceJob& j) {
+  sg_ctx* ctx = c.ctx;
+  sg_net* net = c.net;
   hipStream_t st = ctx->stream;
-  const bool dev = (c.flags & SG_ROUTE_OUT_DEVICE) != 0;
-  const uint32_t n = c.n_nodes, rows = c.row_end - c.row_begin;
+  const uint32_t n = c.n_nodes, rows = c.row_end - c.row_begin, ni = c.packets->n_packets;
   ensure_links(ctx, net);
   const uint32_t nl = net->n_links;
-  if (ni == 0) {
-    if (dev) {
-      SG_HIP(hipMemsetAsync(c.out_off, 0, ((size_t)nl + 1) * 8, st));
-      SG_HIP(hipStreamSynchronize(st));
-    } else {
-      std::fill(c.out_off, c.out_off + nl + 1, (uint64_t)0);
-    }
-    *c.total = 0;
-    return;
-  }
   if (!ctx->paths_ret) SG_HIP(hipHostMalloc(&ctx->paths_ret, 16, hipHostMallocMapped | hipHostMallocCoherent));
-  // host arrays in: device copies
-  const uint32_t* d_pred = c.pred;
-  const uint64_t* d_lat = c.lat;
-  const uint8_t* d_watch = c.watch;
-  uint64_t* d_off = c.out_off;
-  if (!dev) {
-    const size_t cells = (size_t)rows * n;
-    uint32_t* up = ctx->l_pred.get<uint32_t>(cells);
-    uint64_t* ul = ctx->p_lat.get<uint64_t>(cells);
-    if (cells) {
-      SG_HIP(hipMemcpyAsync(up, c.pred, cells * 4, hipMemcpyHostToDevice, st));
-      SG_HIP(hipMemcpyAsync(ul, c.lat, cells * 8, hipMemcpyHostToDevice, st));
-    }
-    d_pred = up;
-    d_lat = ul;
-    if (c.watch) {
-      uint8_t* uw = ctx->tr_watch.get<uint8_t>(nl);
-      if (nl) SG_HIP(hipMemcpyAsync(uw, c.watch, nl, hipMemcpyHostToDevice, st));
-      d_watch = uw;
-    }
-    d_off = ctx->p_off.get<uint64_t>((size_t)nl + 1);
-  }
   uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
   unsigned long long* bad = ctx->l_flag.get<unsigned long long>(TR_WORDS);
   SG_HIP(hipMemsetAsync(bad, 0xff, TR_WORDS * 8, st));
@@ -548,7 +473,7 @@ void trace_run(const TraceCall& c) {
   SG_HIP(hipMemsetAsync(ctr, 0, (2 * (size_t)nl + 1) * 4, st));
   const uint32_t n_blocks = std::max(1u, (uint32_t)(((size_t)nl + TR_SCAN_TILE - 1) / TR_SCAN_TILE));
   const sg_hosts* h = c.hosts;
-  TraceArgs a;
+  TraceArgs& a = j.a;
   a.l.lk_off = net->lk_off;
   a.l.lk_tail = net->lk_tail;
   a.l.nodes = d_idx;
@@ -557,7 +482,7 @@ void trace_run(const TraceCall& c) {
   a.l.row_begin = c.row_begin;
   a.l.rows = rows;
   a.l.count_cols = 0;
-  a.l.pred = d_pred;
+  a.l.pred = c.pred;
   a.l.counts = nullptr;
   a.l.link_load = nullptr;
   a.l.node_load = nullptr;
@@ -573,22 +498,23 @@ void trace_run(const TraceCall& c) {
   a.status = c.status;
   a.n_items = ni;
   a.hops = ctx->p_cnt.get<uint32_t>(ni);
-  a.lat = (const unsigned long long*)d_lat;
-  a.watch = d_watch;
+  a.lat = (const unsigned long long*)c.lat;
+  a.watch = c.watch;
   a.n_links = nl;
   a.cnt = ctr;
   a.cur = ctr + nl;
   a.sums = ctx->p_sums.get<unsigned long long>(n_blocks);
-  a.off = (unsigned long long*)d_off;
+  a.off = (unsigned long long*)c.off;
   a.total = ctx->paths_ret;
   a.key = nullptr;
   a.exit = nullptr;
-  uint32_t* n_work = ctr + 2 * (size_t)nl;
-  const dim3 grid(grid_for(ni, TR_THREADS, 16u * (unsigned)ctx->n_cu));
+  j.n_work = ctr + 2 * (size_t)nl;
+  j.grid = grid_for(ni, TR_THREADS, 16u * (unsigned)ctx->n_cu);
+  j.total = 0;
   {
-    // (work = the records, added below once the total is read)
+    // (work = the records, added once the total is read)
     TimedLaunch tl(ctx, "link_trace_count", 0.0);
-    hipLaunchKernelGGL(k_trace_count, grid, dim3(TR_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_trace_count, dim3(j.grid), dim3(TR_THREADS), 0, st, a);
     SG_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(k_trace_block_sums, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
@@ -597,9 +523,12 @@ void trace_run(const TraceCall& c) {
   SG_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_trace_scan_add, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
   SG_CHECK_LAUNCH();
-  if (!dev) SG_HIP(hipMemcpyAsync(c.out_off, d_off, ((size_t)nl + 1) * 8, hipMemcpyDeviceToHost, st));
+}
+
+void trace_finish_count(const TraceCall& c, TraceJob& j) {
+  sg_ctx* ctx = c.ctx;
   unsigned long long hw[TR_WORDS];
-  copy_to_host(ctx, hw, bad, sizeof(hw));
+  copy_to_host(ctx, hw, j.a.l.bad, sizeof(hw));
   const uint64_t tot = *ctx->paths_ret;
   timer_add_work(ctx, "link_trace_count", (double)tot);
   if (hw[TR_BAD_ITEM] != ~0ull) {
@@ -614,24 +543,28 @@ void trace_run(const TraceCall& c) {
                 "packet " + std::to_string(p) + " " + why[kind], (uint32_t)p, 0xFFFFFFFFu);
   }
   auto pred_error = [&](int kind) {
-    const uint32_t i = (uint32_t)(hw[kind] >> 32), j = (uint32_t)hw[kind];
+    const uint32_t i = (uint32_t)(hw[kind] >> 32), k = (uint32_t)hw[kind];
     static const char* const why[TR_WORDS] = {
         "", "holds a node index out of range at node ",
         "names a predecessor that no link joins to the node (not a link) at node ",
         "does not reach its source within n_nodes steps (a cycle) from node "};
     throw Error(SG_ERR_INVALID_ARG,
-                "the pred row of source node " + node_name(net, c.nodes[i]) + " " + why[kind] + node_name(net, c.nodes[j]),
-                i, j);
+                "the pred row of source node " + node_name(c.net, c.nodes[i]) + " " + why[kind] +
+                    node_name(c.net, c.nodes[k]),
+                i, k);
   };
   if (hw[TR_BAD_RANGE] != ~0ull || hw[TR_BAD_CYCLE] != ~0ull)
     pred_error(hw[TR_BAD_RANGE] <= hw[TR_BAD_CYCLE] ? TR_BAD_RANGE : TR_BAD_CYCLE);
   if (hw[TR_BAD_LINK] != ~0ull) pred_error(TR_BAD_LINK);
-  *c.total = tot;
-  if (tot > c.cap)
-    throw Error(SG_ERR_CAPACITY,
-                "the trace holds " + std::to_string(tot) + " records, the arrays " + std::to_string(c.cap));
-  if (tot == 0) return;
-  // staging, and the device copies of host outputs
+  j.total = tot;
+}
+
+void trace_enqueue_sort(const TraceCall& c, TraceJob& j, const TraceOut& out) {
+  sg_ctx* ctx = c.ctx;
+  hipStream_t st = ctx->stream;
+  TraceArgs& a = j.a;
+  const uint64_t tot = j.total;
+  const uint32_t nl = a.n_links;
   const uint32_t piece = (uint32_t)knob_int("SG_LINK_TRACE_PIECE", (int)TR_PIECE_MAX, (int)TR_RANK_MAX, (int)TR_PIECE_MAX);
   const uint64_t work_cap64 = tot / piece + tot / TR_RANK_MAX + 1;  // pieces of the segments past TR_RANK_MAX, at most
   if (work_cap64 > 0xFFFFFFFFull) throw Error(SG_ERR_CAPACITY, "the trace holds more records than one call sorts");
@@ -639,21 +572,14 @@ void trace_run(const TraceCall& c) {
   a.key = ctx->tr_key.get<uint4>(tot);
   uint4* key2 = ctx->tr_key2.get<uint4>(tot);
   unsigned long long* exit2 = nullptr;
-  if (c.out_exit) {
+  if (out.exit) {
     a.exit = ctx->tr_exit.get<unsigned long long>(tot);
     exit2 = ctx->tr_exit2.get<unsigned long long>(tot);
   }
   uint2* work = ctx->tr_work.get<uint2>(work_cap);
-  TraceOut out = {c.out_packet, c.out_hop, (unsigned long long*)c.out_enter, (unsigned long long*)c.out_exit};
-  if (!dev) {
-    if (c.out_packet) out.packet = ctx->p_node.get<uint32_t>(tot);
-    if (c.out_hop) out.hop = ctx->p_link.get<uint32_t>(tot);
-    if (c.out_enter) out.enter = ctx->p_olat.get<unsigned long long>(tot);
-    if (c.out_exit) out.exit = ctx->tr_oexit.get<unsigned long long>(tot);
-  }
   {
     TimedLaunch tl(ctx, "link_trace_fill", (double)tot);
-    hipLaunchKernelGGL(k_trace_fill, grid, dim3(TR_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_trace_fill, dim3(j.grid), dim3(TR_THREADS), 0, st, a);
     SG_CHECK_LAUNCH();
   }
   {
@@ -662,22 +588,96 @@ void trace_run(const TraceCall& c) {
     const dim3 g_small(grid_for((size_t)nl * 64, TR_THREADS, 16u * (unsigned)ctx->n_cu));
     const dim3 g_work(grid_for(work_cap, 1, 8u * (unsigned)ctx->n_cu));
     hipLaunchKernelGGL(k_trace_sort_small, g_small, dim3(TR_THREADS), 0, st, off, nl, (const uint4*)a.key,
-                       (const unsigned long long*)a.exit, out, piece, work, work_cap, n_work);
+                       (const unsigned long long*)a.exit, out, piece, work, work_cap, j.n_work);
     SG_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_trace_sort_lds, g_work, dim3(TR_THREADS), 0, st, off, (const uint4*)a.key,
                        (const unsigned long long*)a.exit, key2, exit2, out, piece, (const uint2*)work, work_cap,
-                       (const uint32_t*)n_work);
+                       (const uint32_t*)j.n_work);
     SG_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_trace_merge, g_work, dim3(TR_THREADS), 0, st, off, (const uint4*)key2,
                        (const unsigned long long*)exit2, out, piece, (const uint2*)work, work_cap,
-                       (const uint32_t*)n_work);
+                       (const uint32_t*)j.n_work);
     SG_CHECK_LAUNCH();
   }
+}
+
+namespace {
+
+// sg_link_trace_packets: host arrays staged around the halves; two synchronisations.
+struct TraceRun {
+  TraceCall c;  // (pred, lat, watch, off: the caller's, host or device by `flags`)
+  uint32_t flags;
+  uint32_t* out_packet;
+  uint32_t* out_hop;
+  uint64_t* out_enter;
+  uint64_t* out_exit;
+  uint64_t cap;
+  uint64_t* total;
+};
+
+void trace_run(const TraceRun& r) {
+  TraceCall c = r.c;
+  sg_ctx* ctx = c.ctx;
+  trace_check(c, true);
+  if (!r.out_packet && !r.out_hop && !r.out_enter && !r.out_exit) throw Error(SG_ERR_INVALID_ARG, "no record output");
+  if (!c.off || !r.total) throw Error(SG_ERR_INVALID_ARG, "null out_link_off or total");
+  hipStream_t st = ctx->stream;
+  const bool dev = (r.flags & SG_ROUTE_OUT_DEVICE) != 0;
+  const uint32_t n = c.n_nodes, rows = c.row_end - c.row_begin, ni = c.packets->n_packets;
+  ensure_links(ctx, c.net);
+  const uint32_t nl = c.net->n_links;
+  if (ni == 0) {
+    if (dev) {
+      SG_HIP(hipMemsetAsync(c.off, 0, ((size_t)nl + 1) * 8, st));
+      SG_HIP(hipStreamSynchronize(st));
+    } else {
+      std::fill(c.off, c.off + nl + 1, (uint64_t)0);
+    }
+    *r.total = 0;
+    return;
+  }
+  // host arrays in: device copies
   if (!dev) {
-    if (c.out_packet) SG_HIP(hipMemcpyAsync(c.out_packet, out.packet, tot * 4, hipMemcpyDeviceToHost, st));
-    if (c.out_hop) SG_HIP(hipMemcpyAsync(c.out_hop, out.hop, tot * 4, hipMemcpyDeviceToHost, st));
-    if (c.out_enter) SG_HIP(hipMemcpyAsync(c.out_enter, out.enter, tot * 8, hipMemcpyDeviceToHost, st));
-    if (c.out_exit) SG_HIP(hipMemcpyAsync(c.out_exit, out.exit, tot * 8, hipMemcpyDeviceToHost, st));
+    const size_t cells = (size_t)rows * n;
+    uint32_t* up = ctx->l_pred.get<uint32_t>(cells);
+    uint64_t* ul = ctx->p_lat.get<uint64_t>(cells);
+    if (cells) {
+      SG_HIP(hipMemcpyAsync(up, r.c.pred, cells * 4, hipMemcpyHostToDevice, st));
+      SG_HIP(hipMemcpyAsync(ul, r.c.lat, cells * 8, hipMemcpyHostToDevice, st));
+    }
+    c.pred = up;
+    c.lat = ul;
+    if (r.c.watch) {
+      uint8_t* uw = ctx->tr_watch.get<uint8_t>(nl);
+      if (nl) SG_HIP(hipMemcpyAsync(uw, r.c.watch, nl, hipMemcpyHostToDevice, st));
+      c.watch = uw;
+    }
+    c.off = ctx->p_off.get<uint64_t>((size_t)nl + 1);
+  }
+  TraceJob j;
+  trace_enqueue_count(c, j);
+  if (!dev) SG_HIP(hipMemcpyAsync(r.c.off, c.off, ((size_t)nl + 1) * 8, hipMemcpyDeviceToHost, st));
+  trace_finish_count(c, j);
+  const uint64_t tot = j.total;
+  *r.total = tot;
+  if (tot > r.cap)
+    throw Error(SG_ERR_CAPACITY,
+                "the trace holds " + std::to_string(tot) + " records, the arrays " + std::to_string(r.cap));
+  if (tot == 0) return;
+  // the device copies of host outputs
+  TraceOut out = {r.out_packet, r.out_hop, (unsigned long long*)r.out_enter, (unsigned long long*)r.out_exit};
+  if (!dev) {
+    if (r.out_packet) out.packet = ctx->p_node.get<uint32_t>(tot);
+    if (r.out_hop) out.hop = ctx->p_link.get<uint32_t>(tot);
+    if (r.out_enter) out.enter = ctx->p_olat.get<unsigned long long>(tot);
+    if (r.out_exit) out.exit = ctx->tr_oexit.get<unsigned long long>(tot);
+  }
+  trace_enqueue_sort(c, j, out);
+  if (!dev) {
+    if (r.out_packet) SG_HIP(hipMemcpyAsync(r.out_packet, out.packet, tot * 4, hipMemcpyDeviceToHost, st));
+    if (r.out_hop) SG_HIP(hipMemcpyAsync(r.out_hop, out.hop, tot * 4, hipMemcpyDeviceToHost, st));
+    if (r.out_enter) SG_HIP(hipMemcpyAsync(r.out_enter, out.enter, tot * 8, hipMemcpyDeviceToHost, st));
+    if (r.out_exit) SG_HIP(hipMemcpyAsync(r.out_exit, out.exit, tot * 8, hipMemcpyDeviceToHost, st));
   }
   SG_HIP(hipStreamSynchronize(st));
 }
@@ -693,9 +693,9 @@ int32_t sg_link_trace_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts, const u
                               const uint8_t* watch, uint64_t* out_link_off, uint32_t* out_packet, uint32_t* out_hop,
                               uint64_t* out_enter_ns, uint64_t* out_exit_ns, uint64_t cap, uint64_t* total) {
   return sg::guarded(ctx, [&] {
-    sg::trace_run(sg::TraceCall{ctx, net, hosts, nodes, n_nodes, row_begin, row_end, flags, pred, latency_ns, packets,
-                                status, watch, out_link_off, out_packet, out_hop, out_enter_ns, out_exit_ns, cap,
-                                total});
+    sg::trace_run(sg::TraceRun{sg::TraceCall{ctx, net, hosts, nodes, n_nodes, row_begin, row_end, pred, latency_ns,
+                                             packets, status, watch, out_link_off},
+                               flags, out_packet, out_hop, out_enter_ns, out_exit_ns, cap, total});
   });
 }
 

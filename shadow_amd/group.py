@@ -131,6 +131,163 @@ class Group:
                 raise ValueError(f"recv[{m}] holds fewer records than its counts")
         self._check(load().sg_group_alltoallv_records(self.handle, _ptrs(send), cnt.ctypes.data, _ptrs(recv)))
 
+    # -- a sharded round's link loads and link trace ------------------------------------------
+    def last_error_member(self) -> int | None:
+        """The member whose device-found error the last call reported (sg_group_last_error_member)."""
+        m = int(load().sg_group_last_error_member(self.handle))
+        return None if m == 0xFFFFFFFF else m
+
+    def _round_inputs(self, graphs, hosts, rows, packets, status, need_latency):
+        """The per-member arguments both calls share.  rows: a PathTree over all the group's
+        source rows (member m takes rows dist.row_range(tree.n_sources, n, m), uploaded to its
+        device), or (nodes, [(row_begin, row_end, pred, latency_ns or None), ...]) with one entry
+        per member of device tensors on that member's device.  Returns the C arguments and what
+        they point into."""
+        import torch
+
+        from .dist import row_range
+
+        n = len(self.contexts)
+        for name, lst in (("graphs", graphs), ("hosts", hosts), ("packets", packets)):
+            if len(lst) != n:
+                raise ValueError(f"{name}: {len(lst)} entries for {n} members")
+        devs = [torch.device("cuda", c.device) for c in self.contexts]
+        if isinstance(rows, (tuple, list)):
+            nodes, blocks = rows
+            if len(blocks) != n:
+                raise ValueError(f"rows: {len(blocks)} blocks for {n} members")
+            blocks = [(int(b[0]), int(b[1]), b[2], b[3] if len(b) > 3 else None) for b in blocks]
+        else:  # a PathTree
+            nodes, blocks = rows.nodes, []
+            for m in range(n):
+                r0, r1, _ = row_range(rows.n_sources, n, m)
+                pred = torch.from_numpy(np.ascontiguousarray(rows.pred[r0:r1], dtype=np.uint32).view(np.int32)).to(devs[m])
+                lat = None
+                if need_latency:
+                    lat = torch.from_numpy(np.ascontiguousarray(rows.latency_ns[r0:r1], dtype=np.uint64).view(np.int64)).to(devs[m])
+                blocks.append((r0, r1, pred, lat))
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        for m, (r0, r1, pred, lat) in enumerate(blocks):
+            cells = (r1 - r0) * len(nodes)
+            if r1 > r0 and (pred is None or pred.numel() < cells or (need_latency and (lat is None or lat.numel() < cells))):
+                raise ValueError(f"rows[{m}]: {r1 - r0} rows of {len(nodes)} cells")
+        st = [None] * n
+        if status is not None:
+            if len(status) != n:
+                raise ValueError(f"status: {len(status)} entries for {n} members")
+            for m, s in enumerate(status):
+                if s is None:
+                    continue
+                s = getattr(s, "status", s)
+                if not isinstance(s, torch.Tensor):
+                    s = torch.from_numpy(np.ascontiguousarray(s, dtype=np.uint8))
+                s = s.to(device=devs[m]).contiguous()
+                if s.element_size() != 1 or s.numel() < len(packets[m]):
+                    raise ValueError(f"status[{m}]: {len(packets[m])} u8 entries, one per packet")
+                st[m] = s
+        pk = (_capi.sg_packets * n)(*[p.c_struct() for p in packets])
+        u32s = lambda v: (C.c_uint32 * n)(*v)  # noqa: E731
+        args = dict(nets=(C.c_void_p * n)(*[g._ensure_net().value for g in graphs]),
+                    hosts=(C.c_void_p * n)(*[getattr(h.handle, "value", h.handle) for h in hosts]),
+                    nodes=nodes, row_begin=u32s([b[0] for b in blocks]), row_end=u32s([b[1] for b in blocks]),
+                    pred=_ptrs([b[2] for b in blocks]), lat=_ptrs([b[3] for b in blocks]), packets=pk,
+                    status=None if status is None else _ptrs(st))
+        for d in devs:  # what wrote the inputs on torch's streams
+            torch.cuda.synchronize(d)
+        return args, devs, (blocks, st)
+
+    def link_load_round(self, graphs, hosts, rows, packets, status=None, weight=None, root: int = 0):
+        """(link_load, node_load, hops) of one sharded round: PathTree.link_load_round over every
+        member's batch at once (sg_group_link_load_packets).  graphs[m], hosts[m], packets[m]
+        (a PacketBatch of member m's own sources) and status[m] (or None) live on member m's
+        context; rows as in _round_inputs; weight: None (1 per packet), "payload", or one u32
+        array per member.  link_load and node_load (u64, summed over the members on member
+        `root`'s device) equal the single call's on the concatenated batch; hops is one u32 array
+        per member."""
+        import torch
+
+        n = len(self.contexts)
+        a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, False)
+        wt = None
+        if weight is not None:
+            if isinstance(weight, str):
+                if weight != "payload":
+                    raise ValueError('weight: None, "payload" or one array per member')
+                weight = [p.payload_len for p in packets]
+            wt = []
+            for m, w in enumerate(weight):
+                if w is not None and not isinstance(w, torch.Tensor):
+                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
+                wt.append(None if w is None else w.to(device=devs[m]).contiguous())
+                if wt[m] is not None and (wt[m].element_size() != 4 or wt[m].numel() < len(packets[m])):
+                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
+            for d in devs:
+                torch.cuda.synchronize(d)
+        n_links = len(graphs[root].links()[0])
+        link = torch.zeros(max(n_links, 1), dtype=torch.int64, device=devs[root])
+        node = torch.zeros(max(len(a["nodes"]), 1), dtype=torch.int64, device=devs[root])
+        hops = [torch.zeros(max(len(p), 1), dtype=torch.int32, device=d) for p, d in zip(packets, devs)]
+        for d in devs:
+            torch.cuda.synchronize(d)
+        self._check(load().sg_group_link_load_packets(
+            self.handle, a["nets"], a["hosts"], a["nodes"].ctypes.data, len(a["nodes"]), a["row_begin"], a["row_end"],
+            a["pred"], a["packets"], a["status"], None if wt is None else _ptrs(wt), int(root), link.data_ptr(),
+            node.data_ptr(), _ptrs(hops)))
+        for c in self.contexts:
+            c.synchronize()
+        del keep
+        return (link.cpu().numpy().view(np.uint64)[:n_links], node.cpu().numpy().view(np.uint64)[:len(a["nodes"])],
+                [h.cpu().numpy().view(np.uint32)[:len(p)] for h, p in zip(hops, packets)])
+
+    def link_trace_round(self, graphs, hosts, rows, packets, status=None, watch=None, root: int = 0):
+        """The link trace of one sharded round, (link_off, packet, member, hop, enter_ns, exit_ns):
+        PathTree.link_trace_round over every member's batch, the members' records merged on member
+        `root`'s device (sg_group_link_trace_packets).  Link L owns records link_off[L] ..
+        link_off[L + 1] in ascending (enter_ns, member, member-local packet) order; packet is the
+        index in the members' batches concatenated in member order, member the batch it came from.
+        rows needs the latency rows; watch as in PathTree.link_trace_round.  A first call at a
+        guessed capacity, a second at the total the first reported when that was too small."""
+        import torch
+
+        a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, True)
+        n_links = len(graphs[root].links()[0])
+        if watch is not None:
+            w = np.asarray(watch)
+            if w.dtype == np.bool_ or (w.dtype == np.uint8 and w.shape == (n_links,)):
+                if w.shape != (n_links,):
+                    raise ValueError(f"watch: a mask of {n_links} entries, one per link")
+                mask = w.astype(np.uint8)
+            else:
+                idx = w.astype(np.int64).ravel()
+                if len(idx) and (idx.min() < 0 or idx.max() >= n_links):
+                    raise ValueError(f"watch: link numbers below {n_links}")
+                mask = np.zeros(n_links, np.uint8)
+                mask[idx] = 1
+            watch = np.ascontiguousarray(mask)
+        d = devs[root]
+        off = torch.zeros(n_links + 1, dtype=torch.int64, device=d)
+        total = C.c_uint64()
+        cap = 8 * sum(len(p) for p in packets) + 64
+        while True:
+            pkt, hop = torch.zeros(cap, dtype=torch.int32, device=d), torch.zeros(cap, dtype=torch.int32, device=d)
+            mem = torch.zeros(cap, dtype=torch.uint8, device=d)
+            enter, leave = torch.zeros(cap, dtype=torch.int64, device=d), torch.zeros(cap, dtype=torch.int64, device=d)
+            torch.cuda.synchronize(d)
+            rc = load().sg_group_link_trace_packets(
+                self.handle, a["nets"], a["hosts"], a["nodes"].ctypes.data, len(a["nodes"]), a["row_begin"], a["row_end"],
+                a["pred"], a["lat"], a["packets"], a["status"], None if watch is None else watch.ctypes.data, None,
+                int(root), off.data_ptr(), pkt.data_ptr(), mem.data_ptr(), hop.data_ptr(), enter.data_ptr(),
+                leave.data_ptr(), cap, C.byref(total))
+            if rc != _capi.SG_ERR_CAPACITY or total.value <= cap:
+                break
+            cap = total.value
+        self._check(rc)
+        del keep
+        t = total.value
+        return (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32), mem[:t].cpu().numpy(),
+                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
+                leave[:t].cpu().numpy().view(np.uint64))
+
 
 class GroupDelivery:
     """The single-process driver of a sharded delivery round: dist.ShardedDelivery.round for all

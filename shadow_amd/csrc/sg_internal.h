@@ -145,6 +145,9 @@ struct sg_ctx {
   // is pending.
   uint32_t* used_fill = nullptr;
   uint32_t used_fill_n = 0;
+  // ... and, copied or not, that the list of the build in progress is the identity (the LDS
+  // search then reads no column ids); false outside sg_routing_build, so in sg_routing_info_fill
+  bool used_ident = false;
   // Round control: round_err (device, zeroed at creation) collects the source
   // phase's error flags; the stats kernel hands them to the host and clears
   // them for the next round.  round_ret (pinned, mapped host memory) receives
@@ -462,12 +465,14 @@ struct SsspChainDesc {
 };
 
 // One launch of the LDS search on a net (the graph arrays come from it).
+constexpr int SSSP_DIAG_WORDS = 16;  // SG_SSSP_DIAG: u64 words per row (sg_sssp.hip writes, print_sssp_diag reads)
 struct SsspLdsLaunch {
   // the row block: rows [row_begin, row_end) of the table (out_* device, row-major from
   // row_begin); sat_row (row_end - row_begin u32) receives 1 for rows needing the wide kernel;
-  // delta the bucket width in ns; work / diag optional (relaxations; 8 words per row)
+  // delta the bucket width in ns; work / diag optional (relaxations; SSSP_DIAG_WORDS per row)
   const uint32_t* d_used = nullptr;
   uint32_t n_used = 0, row_begin = 0, row_end = 0;
+  bool ident = false;  // d_used[j] == j for every j: the kernel takes column j's node as j and does not load the list
   uint64_t* out_lat = nullptr;
   float* out_loss = nullptr;
   uint32_t* sat_row = nullptr;

@@ -444,30 +444,35 @@ static LdsKnobs lds_knobs(const sg_ctx* ctx, const sg_net* net, uint32_t n_used,
   return k;
 }
 
-// SG_SSSP_DIAG: the LDS search's per-row statistics (8 words per row) on stderr
+// SG_SSSP_DIAG: the LDS search's per-row statistics (SSSP_DIAG_WORDS per row) on stderr
 static void print_sssp_diag(sg_ctx* ctx, const sg_net* net, const unsigned long long* diag, uint32_t n_diag,
                             uint32_t delta) {
-  std::vector<unsigned long long> h((size_t)n_diag * 8);
+  constexpr int DW = SSSP_DIAG_WORDS;
+  std::vector<unsigned long long> h((size_t)n_diag * DW);
   copy_to_host(ctx, h.data(), diag, h.size() * 8);
-  double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double a[DW] = {};
   double setup = 0;
   // chained against unchained rows (word 3, bit 22): rows, setup cycles, search cycles (set-up included)
   double cn[2] = {0, 0}, cs[2] = {0, 0}, cq[2] = {0, 0};
   for (uint32_t r = 0; r < n_diag; r++) {
-    for (int k = 0; k < 8; k++) a[k] += (double)h[(size_t)r * 8 + k];
-    const unsigned long long w3 = h[(size_t)r * 8 + 3];
+    for (int k = 0; k < DW; k++) a[k] += (double)h[(size_t)r * DW + k];
+    const unsigned long long w3 = h[(size_t)r * DW + 3];
     setup += (double)(w3 >> 24);
     a[3] -= (double)(w3 >> 22 << 22);
-    if (h[(size_t)r * 8] == 0) continue;  // a row of the list past this launch's phase
+    if (h[(size_t)r * DW] == 0) continue;  // a row of the list past this launch's phase
     const int c = (int)((w3 >> 22) & 1);
     cn[c] += 1;
     cs[c] += (double)(w3 >> 24);
-    cq[c] += (double)h[(size_t)r * 8];
+    cq[c] += (double)h[(size_t)r * DW];
   }
   for (int c = 0; c < 2; c++)
     fprintf(stderr, "[sssp] %s rows: %.0f, mean setup %.0f cyc, mean search %.0f cyc\n", c ? "chained" : "unchained",
             cn[c], cs[c] / std::max(1.0, cn[c]), cq[c] / std::max(1.0, cn[c]));
   fprintf(stderr, "[sssp] mean setup (init + bound rows) %.0f cyc of the search\n", setup / n_diag);
+  // the set-up's parts, thread 0's stamps (words 8-12)
+  fprintf(stderr, "[sssp] setup parts: bound-row listing and load issue %.0f, LDS pass %.0f, barrier %.0f, first load "
+          "round %.0f, later rounds and closing barrier %.0f cyc\n", a[9] / n_diag, a[8] / n_diag, a[10] / n_diag,
+          a[11] / n_diag, a[12] / n_diag);
   fprintf(stderr, "[sssp] per-wave cycles summed over a row's 16 waves: claim+wait %.0f, pop %.0f, steps %.0f "
           "(per pop: %.0f, %.0f)\n", a[5] / n_diag, a[6] / n_diag, a[7] / n_diag, a[6] / std::max(1.0, a[2]),
           a[7] / std::max(1.0, a[2]));
@@ -499,8 +504,9 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   uint32_t* sat = ctx->r_flags.get<uint32_t>(2 * (size_t)rows);
   uint32_t* claim = k.chain ? sat + rows : nullptr;
   // the relaxation counters, then the chained rows' two: rows seeded in place, those with exact seeds
-  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS + 2) : nullptr;
-  if (work) SG_HIP(hipMemsetAsync(work, 0, (WORK_SHARDS + 2) * 8, st));
+  // ... then the ring invariant's two: ring slots a row's end found non-empty, rows looked at
+  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS + 4) : nullptr;
+  if (work) SG_HIP(hipMemsetAsync(work, 0, (WORK_SHARDS + 4) * 8, st));
   unsigned long long chained_seen[2] = {0, 0};
   unsigned long long phase_chained[SSSP_PHASES_MAX] = {};
   // counting mode: the rows this launch chained (kept per phase; SG_SSSP_DIAG prints them)
@@ -528,11 +534,13 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     }
   };
   const uint32_t n_diag = std::min<uint32_t>(rows, 4096);
-  unsigned long long* diag = work && k.diag ? ctx->r_misc.get<unsigned long long>((size_t)n_diag * 8) : nullptr;
-  if (diag) SG_HIP(hipMemsetAsync(diag, 0, (size_t)n_diag * 64, st));
+  unsigned long long* diag =
+      work && k.diag ? ctx->r_misc.get<unsigned long long>((size_t)n_diag * SSSP_DIAG_WORDS) : nullptr;
+  if (diag) SG_HIP(hipMemsetAsync(diag, 0, (size_t)n_diag * SSSP_DIAG_WORDS * 8, st));
   SsspLdsLaunch base;
   base.d_used = d_used;
   base.n_used = n_used;
+  base.ident = ctx->used_ident;
   base.row_begin = row_begin;
   base.row_end = row_end;
   base.out_lat = out_lat;
@@ -619,10 +627,15 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   std::vector<uint32_t> wide_rows = finish_rows(ctx, sat, row_begin, rows, told);
   ctx->side_busy = false;  // (the context stream waited for the side stream and was synchronised)
   if (work) {
-    unsigned long long w[WORK_SHARDS + 2];
-    timer_add_work(ctx, "sssp", read_work(ctx, work, w, 2));
+    unsigned long long w[WORK_SHARDS + 4];
+    timer_add_work(ctx, "sssp", read_work(ctx, work, w, 4));
     // read_timer("sssp_chained"): (0, rows with exact chain seeds, chained rows) of this build
     timer_set_counter(ctx, "sssp_chained", (double)w[WORK_SHARDS], w[WORK_SHARDS + 1]);
+    // read_timer("sssp_ring_left"): (0, rows whose ring was looked at, slots found non-empty: 0 by the invariant)
+    timer_set_counter(ctx, "sssp_ring_left", (double)w[WORK_SHARDS + 2], w[WORK_SHARDS + 3]);
+    if (k.diag)
+      fprintf(stderr, "[sssp] ring slots not empty at a row's end: %llu (%llu rows)\n", w[WORK_SHARDS + 2],
+              w[WORK_SHARDS + 3]);
   }
   if (!wide_rows.empty()) run_wide(ctx, net, d_used, n_used, wide_rows, row_begin, out_lat, out_loss);
 }
@@ -758,8 +771,12 @@ int32_t sg_routing_build(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32
     uint32_t* d_used = ctx->r_used.get<uint32_t>(n_used);
     struct NoFill {  // however the build ends, no later call finds this list's fill pending
       sg_ctx* c;
-      ~NoFill() { c->used_fill = nullptr; }
+      ~NoFill() {
+        c->used_fill = nullptr;
+        c->used_ident = false;
+      }
     } no_fill{ctx};
+    ctx->used_ident = identity;
     if (identity && build_fused()) {
       // every node used, in order (C3, C5, C2; Shadow whenever every graph node has a host): the
       // list is written by the first kernel that reads it (the plan's k_plan_rel, else flush_used)

@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(NT)
                const uint32_t* __restrict__ ub_row, const uint32_t* __restrict__ ub_w,
                uint32_t* __restrict__ item_ctr, uint32_t n_items, uint32_t spin_max,
                const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done,
-               const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag) {
+               const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag, int ident) {
   constexpr int NW = NT / 64;
   constexpr int AUX = FLAG ? SSSP_SC1 : 0;  // bound rows and the output: sc1 in the flagged launch
   // Chained rows: persistent workgroups, never the flagged launch.  The claim words and the maps
@@ -290,6 +290,13 @@ __global__ void __launch_bounds__(NT)
       if (atomicCAS(&claim_w[r - row_begin], 0u, 1u) == 0u) return b;
     }
   };
+  // The ring and own[] are reset here, once: a pop stores RING_EMPTY into its slot, and a search
+  // that ended normally is quiescent (head == tail, no wave busy), so every slot written was
+  // popped and the ring is all RING_EMPTY again; expand zeroes every own[] entry it reads, and
+  // it reads every entry it wrote; a workgroup that gave up takes no further row.  (The row
+  // loop's barriers order this ahead of the first search.)
+  for (uint32_t i = tid; i < cap; i += NT) ring[i] = RING_EMPTY;
+  for (int i = tid; i < NW * 64 * SSSP_K; i += NT) (&own[0][0])[i] = 0;
   if (item_ctr && tid == 0) {
     s_item = next_listed();
     s_chain = 0u;
@@ -318,37 +325,37 @@ __global__ void __launch_bounds__(NT)
     uint32_t n_adv = 0, n_pops = 0;
     unsigned long long cyc_claim = 0, cyc_pop = 0, cyc_steps = 0;  // per wave, COUNT diagnostics
     const uint32_t row = blk_rows ? blk_rows[bi] : row_begin + bi;
-    const uint32_t src = used[row];
-    // Setup: the LDS queue and keys (out_off is staged once, before the row loop)
-    if (chain) {
-      // Chained rows: key[] holds the finished row of a node this source has an arc to (latency
-      // chain_w); every key becomes this row's start in place -- see the header
-      const bool ex = (chain & 2u) != 0;
-      for (uint32_t v = tid; v < n; v += NT) {
-        const uint64_t kv = key[v];
-        const uint64_t l = (uint64_t)fkey_lat(kv) + chain_w;
-        uint64_t nk = FKEY_INF;
-        if (fkey_lat(kv) != LAT32_SAT && l < LAT32_SAT - 1)
-          nk = ex ? (l << 32) | ((uint32_t)kv & ~1u) : ((l + 1) << 32) | ((uint64_t)0x3F800000u << 1);
-        key[v] = nk;
-      }
-      if (COUNT && tid == 0) {
-        atomicAdd(&work[WORK_SHARDS], 1ull);
-        if (ex) atomicAdd(&work[WORK_SHARDS + 1], 1ull);
-      }
-    } else {
-      for (uint32_t v = tid; v < n; v += NT) key[v] = FKEY_INF;
-    }
-    for (uint32_t i = tid; i < cap; i += NT) ring[i] = RING_EMPTY;
-    for (int i = tid; i < NW * 64 * SSSP_K; i += NT) (&own[0][0])[i] = 0;
-    if (tid < 8) ctl[tid] = 0;
-    if (tid == 0) hb = 0;
-    if (ub_row && tid < 64) {
-      // wave 0 lists the row's usable bound rows in LDS while the others initialise: a
-      // row whose search gave up (sat_row 2) was never written, so it gives no bounds; a
-      // saturated one (1) holds real paths but not its optimum everywhere: bounds only
-      const uint32_t e = tid < SSSP_KB ? ub_row[(size_t)bi * SSSP_KB + tid] : ~0u;
-      const uint32_t w = tid < SSSP_KB ? ub_w[(size_t)bi * SSSP_KB + tid] : 0u;
+    const uint32_t src = ident ? row : used[row];  // (ident: the used list is the identity, column j is node j)
+    // Setup.  Every global load of it is issued before the LDS pass, so the row pays one memory
+    // round trip behind the bound-row listing instead of one per column group:
+    //   1. the row's usable bound rows are listed (ub_row / ub_w, then their flags): for a
+    //      persistent workgroup's later rows already at the claim, see list_bounds below;
+    //   2. each thread issues its columns' node ids and the first two bound rows' latency and loss
+    //      loads for its first GC columns (every column up to GC x NT = 10,240 of them);
+    //   3. the keys become this row's start (infinity, or the chained rewrite) and ctl / hb are
+    //      reset under those loads; a barrier, since with a used list other than the identity
+    //      column j's node is another thread's to rewrite;
+    //   4. the loads are merged into key[] with min, one bound row after the other (the map from a
+    //      bound to its start key is monotone, so the min of the keys is the key of the min);
+    //   5. columns past GC x NT and bound rows past the second (SG_SSSP_BOUNDS > 2, in pairs)
+    //      take a load round each: the same loop, without the LDS pass.
+    // The ring and own[] are not reset: see the invariant ahead of the row loop.
+    //
+    // The usable bound rows of list place b, written to s_ub / s_nub by one whole wave: a row
+    // whose search gave up (sat_row 2) was never written, so it gives no bounds; a saturated one
+    // (1) holds real paths but not its optimum everywhere: bounds only.
+    //   Phased launches: the flags are those of earlier launches, so they can be read at any
+    // time.  A persistent workgroup's later rows are listed by the wave that claims them, ahead
+    // of that wave's output stores (at the row's start the two dependent loads would wait behind
+    // every wave's stores of the row before); s_ub is read during a set-up only, and barriers
+    // separate that from the claim.  A workgroup's first row is listed here by every wave for
+    // itself (the same values into the same words), which waits for no other wave.
+    //   Flagged launch: wave 0 polls here, at set-up time (an earlier poll would miss rows
+    // published meanwhile), and alone: every column must see the same set of rows (the induction
+    // of "Exact seeds" follows one bound row along a path).
+    auto list_bounds = [&](uint32_t b) {
+      const uint32_t e = lane < SSSP_KB ? ub_row[(size_t)b * SSSP_KB + lane] : ~0u;
+      const uint32_t w = lane < SSSP_KB ? ub_w[(size_t)b * SSSP_KB + lane] : 0u;
       const uint32_t srow = e & ~SSSP_UB_EXACT;
       uint32_t sf;
       if constexpr (FLAG) {  // one sc1 poll per bound row, no wait: an unpublished row gives no bounds
@@ -362,81 +369,134 @@ __global__ void __launch_bounds__(NT)
       const bool on = sf != 2u;
       const uint64_t mk = __ballot(on);
       if (on) {
-        const int at = __popcll(mk & ((1ull << tid) - 1));
+        const int at = __popcll(mk & ((1ull << lane) - 1));
         s_ub[at][0] = srow;
         s_ub[at][1] = w;
         s_ub[at][2] = (e & SSSP_UB_EXACT) && sf == 0u;
       }
-      if (tid == 0) s_nub = (uint32_t)__popcll(mk);
+      if (lane == 0) s_nub = (uint32_t)__popcll(mk);
+    };
+    int nb = 0;
+    if (ub_row && (FLAG ? tid < 64 : it == 0)) list_bounds(bi);
+    if (ub_row) {
+      if constexpr (FLAG) {
+        __syncthreads();
+      } else {  // this wave's own writes (or another's, the same values)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+      nb = (int)s_nub;
     }
-    __syncthreads();
-    if (ub_row) {  // Bounds: keys start just above the shortest of up to SSSP_KB known paths (clean)
-      const int nb = (int)s_nub;
-      if (nb) {
-        const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)used, 0, (int)(n_used * 4u),
-                                                                            0x00020000);
-        constexpr int G = 6;  // columns per thread per group
-        for (uint32_t j0 = tid; j0 < n_used; j0 += G * NT) {
-          uint32_t vv[G];
-          uint64_t m[G], ex[G];
-#pragma unroll
-          for (int g = 0; g < G; g++) {
-            const uint32_t j = j0 + g * NT;
-            vv[g] = __builtin_amdgcn_raw_buffer_load_b32(ru, j < n_used ? j * 4u : OOB, 0, 0);
-            m[g] = ex[g] = ~0ull;
-          }
+    unsigned long long c_list = 0, c_init = 0, c_bar = 0, c_g0 = 0;
+    // the LDS pass: the keys become this row's start, ctl and hb are reset; then the barrier
+    auto lds_pass = [&]() {
+      if (dg) c_list = clock64();
+      if (chain) {
+        // Chained rows: key[] holds the finished row of a node this source has an arc to (latency
+        // chain_w); every key becomes this row's start in place -- see the header
+        const bool ex = (chain & 2u) != 0;
+        for (uint32_t v = tid; v < n; v += NT) {
+          const uint64_t kv = key[v];
+          const uint64_t lw = (uint64_t)fkey_lat(kv) + chain_w;
+          uint64_t nk = FKEY_INF;
+          if (fkey_lat(kv) != LAT32_SAT && lw < LAT32_SAT - 1)
+            nk = ex ? (lw << 32) | ((uint32_t)kv & ~1u) : ((lw + 1) << 32) | ((uint64_t)0x3F800000u << 1);
+          key[v] = nk;
+        }
+        if (COUNT && tid == 0) {
+          atomicAdd(&work[WORK_SHARDS], 1ull);
+          if (ex) atomicAdd(&work[WORK_SHARDS + 1], 1ull);
+        }
+      } else {
+        for (uint32_t v = tid; v < n; v += NT) key[v] = FKEY_INF;
+      }
+      if (tid < 8) ctl[tid] = 0;
+      if (tid == 0) hb = 0;
+      if (dg) c_init = clock64();
+      __syncthreads();
+      if (dg) c_bar = clock64();
+    };
+    if (!nb) {  // no bounds: the LDS pass alone
+      lds_pass();
+    } else {
+      constexpr int GC = 10;  // columns per thread in flight (x 2 bound rows x 12 B)
+      const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)used, 0, (int)(n_used * 4u),
+                                                                          0x00020000);
+      // load rounds: bound rows k, k + 1 for columns jb + tid + g NT, g < GC; the first round
+      // carries the LDS pass between its loads and their merge
+      int k = 0;
+      uint32_t jb = 0;
+      // (the column offsets come from an opaque copy of tid, per row: computed from tid itself they
+      // are hoisted out of the row loop and kept, or spilled, across the whole search)
+      uint32_t ts = (uint32_t)tid;
+      asm volatile("" : "+v"(ts));
 #pragma unroll 1
-          for (int k = 0; k < nb; k += 2) {  // two bound rows' loads in flight together
-            bool on[2], exact[2];
-            uint32_t sr[2], w[2];
-            __amdgpu_buffer_rsrc_t rl[2], rf[2];
+      do {
+        const uint32_t j0 = jb + ts;
+        uint32_t vv[GC];
+        uint64_t l[2][GC];
+        uint32_t f[2][GC];
+        bool on[2], exact[2];
+        uint32_t sr[2];
 #pragma unroll
-            for (int u = 0; u < 2; u++) {
-              on[u] = k + u < nb;
-              sr[u] = on[u] ? s_ub[k + u][0] : 0u;
-              w[u] = on[u] ? s_ub[k + u][1] : 0u;
-              exact[u] = on[u] && s_ub[k + u][2];
-              const size_t rb = on[u] ? (size_t)(sr[u] - out_row0) * n_used : 0;
-              rl[u] = __builtin_amdgcn_make_buffer_rsrc((void*)(out_lat + rb), 0, (int)(on[u] ? n_used * 8u : 0u),
-                                                        0x00020000);
-              rf[u] = __builtin_amdgcn_make_buffer_rsrc((void*)(out_loss + rb), 0, (int)(exact[u] ? n_used * 4u : 0u),
-                                                        0x00020000);
-            }
-            uint64_t l[2][G];
-            uint32_t f[2][G];
+        for (int u = 0; u < 2; u++) {
+          // (wave-uniform values: read into scalar registers, so the descriptors are scalar too)
+          on[u] = k + u < nb;
+          sr[u] = on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][0]) : 0u;
+          exact[u] = on[u] && __builtin_amdgcn_readfirstlane(s_ub[k + u][2]);
+          const size_t rb = on[u] ? (size_t)(sr[u] - out_row0) * n_used : 0;
+          const __amdgpu_buffer_rsrc_t rl =
+              __builtin_amdgcn_make_buffer_rsrc((void*)(out_lat + rb), 0, (int)(on[u] ? n_used * 8u : 0u), 0x00020000);
+          const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
+              (void*)(out_loss + rb), 0, (int)(exact[u] ? n_used * 4u : 0u), 0x00020000);
 #pragma unroll
-            for (int u = 0; u < 2; u++)
-#pragma unroll
-              for (int g = 0; g < G; g++) {
-                const uint32_t j = j0 + g * NT;
-                const auto x = __builtin_amdgcn_raw_buffer_load_b64(rl[u], j < n_used ? j * 8u : OOB, 0, AUX);
-                l[u][g] = ((uint64_t)x[1] << 32) | x[0];
-                f[u][g] = __builtin_amdgcn_raw_buffer_load_b32(rf[u], j < n_used ? j * 4u : OOB, 0, AUX);
-              }
-#pragma unroll
-            for (int u = 0; u < 2; u++)
-#pragma unroll
-              for (int g = 0; g < G; g++) {
-                const uint32_t j = j0 + g * NT;
-                const uint64_t ub = l[u][g] + w[u];  // w < 2^32: a wrap means >= 2^64
-                if (!on[u] || j >= n_used || ub < w[u]) continue;
-                m[g] = min(m[g], ub);
-                if (exact[u] && ub < LAT32_SAT && j != sr[u])  // exact: the path s -> s' then D[s'][v]
-                  ex[g] = min(ex[g], (ub << 32) | ((uint64_t)f[u][g] << 1));
-              }
-          }
-#pragma unroll
-          for (int g = 0; g < G; g++) {
-            uint64_t kv = m[g] < LAT32_SAT - 1 ? ((m[g] + 1) << 32) | ((uint64_t)0x3F800000u << 1) : FKEY_INF;
-            kv = min(kv, ex[g]);
-            // (a chained row's keys already hold its first bound row: the smaller start wins; one
-            // thread per column, so a plain read and write)
-            if (j0 + g * NT < n_used && kv != FKEY_INF) key[vv[g]] = chain ? min((uint64_t)key[vv[g]], kv) : kv;
+          for (int g = 0; g < GC; g++) {
+            const uint32_t j = j0 + g * NT;
+            const auto x = __builtin_amdgcn_raw_buffer_load_b64(rl, j < n_used ? j * 8u : OOB, 0, AUX);
+            l[u][g] = ((uint64_t)x[1] << 32) | x[0];
+            f[u][g] = __builtin_amdgcn_raw_buffer_load_b32(rf, j < n_used ? j * 4u : OOB, 0, AUX);
           }
         }
-      }
-      __syncthreads();
+        if (!ident) {
+#pragma unroll
+          for (int g = 0; g < GC; g++) {
+            const uint32_t j = j0 + g * NT;
+            vv[g] = __builtin_amdgcn_raw_buffer_load_b32(ru, j < n_used ? j * 4u : OOB, 0, 0);
+          }
+        }
+        if (k == 0 && jb == 0) lds_pass();
+        // one thread per column, so a plain read and write (a chained row's keys already hold its
+        // first bound row, an earlier pair's its bounds: the smaller start wins)
+        uint32_t w[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) w[u] = on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][1]) : 0u;
+#pragma unroll
+        for (int g = 0; g < GC; g++) {
+          const uint32_t j = j0 + g * NT;
+          if (j >= n_used) continue;
+          const uint32_t v = ident ? j : vv[g];
+          const uint64_t k0 = key[v];
+          uint64_t kv = k0;
+#pragma unroll
+          for (int u = 0; u < 2; u++) {
+            const uint64_t ub = l[u][g] + w[u];  // w < 2^32: a wrap means >= 2^64
+            if (!on[u] || ub < w[u]) continue;
+            if (ub < LAT32_SAT - 1) kv = min(kv, ((ub + 1) << 32) | ((uint64_t)0x3F800000u << 1));
+            if (exact[u] && ub < LAT32_SAT && j != sr[u])  // exact: the path s -> s' then D[s'][v]
+              kv = min(kv, (ub << 32) | ((uint64_t)f[u][g] << 1));
+          }
+          if (kv != k0) key[v] = kv;
+        }
+        if (dg && !c_g0) c_g0 = clock64();
+        jb += GC * NT;
+        if (jb >= n_used) {
+          jb = 0;
+          k += 2;
+        }
+      } while (k < nb);
     }
+    if (ub_row) __syncthreads();
     const unsigned long long c_setup = dg ? clock64() : 0;
     if (tid == 0) {
       key[src] = 1ull;  // PathProperties::default(), dirty and queued
@@ -704,18 +764,31 @@ __global__ void __launch_bounds__(NT)
     }
     if (COUNT && lane == 0 && n_rel) atomicAdd(&work[bi & 63], (unsigned long long)n_rel);
     if (COUNT && diag && bi < 4096 && lane == 0) {
-      if (n_rel) atomicAdd(&diag[bi * 8 + 4], (unsigned long long)n_rel);
-      if (n_pops) atomicAdd(&diag[bi * 8 + 2], (unsigned long long)n_pops);
-      atomicAdd(&diag[bi * 8 + 5], cyc_claim);
-      atomicAdd(&diag[bi * 8 + 6], cyc_pop);
-      atomicAdd(&diag[bi * 8 + 7], cyc_steps);
+      if (n_rel) atomicAdd(&diag[bi * SSSP_DIAG_WORDS + 4], (unsigned long long)n_rel);
+      if (n_pops) atomicAdd(&diag[bi * SSSP_DIAG_WORDS + 2], (unsigned long long)n_pops);
+      atomicAdd(&diag[bi * SSSP_DIAG_WORDS + 5], cyc_claim);
+      atomicAdd(&diag[bi * SSSP_DIAG_WORDS + 6], cyc_pop);
+      atomicAdd(&diag[bi * SSSP_DIAG_WORDS + 7], cyc_steps);
     }
     const unsigned long long c_search = dg ? clock64() : 0;
+    if (COUNT) {  // the ring invariant: slots a finished search left non-empty (0), rows looked at
+      uint32_t left = 0;
+      for (uint32_t i = tid; i < cap; i += NT) left += ring[i] != RING_EMPTY;
+      if (left) atomicAdd(&work[WORK_SHARDS + 2], (unsigned long long)left);
+      if (tid == 0) atomicAdd(&work[WORK_SHARDS + 3], 1ull);
+    }
 
     // ---- write the row: columns in used order, diagonal = the raw self-loop (graph/mod.rs:210-217)
     __syncthreads();  // every thread has read s_item (at the row's start) before it is written again
     if (item_ctr && !chain_on) {
-      if (tid == 0) s_item = atomicAdd(item_ctr, 1u);  // the next row (see the row loop)
+      if (wv == 0) {  // the next row (see the row loop), and its bound rows (see list_bounds)
+        uint32_t ni = 0;
+        if (lane == 0) s_item = ni = atomicAdd(item_ctr, 1u);
+        if (!FLAG && ub_row) {
+          ni = __builtin_amdgcn_readfirstlane(ni);
+          if (ni < n_items) list_bounds(ni);
+        }
+      }
     } else if (item_ctr && wv == NW - 1) {
       // Chained rows: one wave looks for the next row among the heads of this source's out-arcs
       // (up to 64, one per lane): a row of the block, of this launch's phase, not yet claimed;
@@ -772,10 +845,15 @@ __global__ void __launch_bounds__(NT)
         }
         if (ok && q == mq) sc = ~0ull;  // claimed by another workgroup: every arc to it drops out
       }
+      uint32_t ni = 0;
       if (lane == 0) {
-        s_item = got ? nb : next_listed();
+        s_item = ni = got ? nb : next_listed();
         s_chain = cf;
         s_cw = cw;
+      }
+      if (ub_row) {  // the claimed row's bound rows (see list_bounds)
+        ni = __builtin_amdgcn_readfirstlane(ni);
+        if (ni < n_items) list_bounds(ni);
       }
     }
     const size_t orow = (size_t)(row - out_row0) * n_used;
@@ -806,11 +884,11 @@ __global__ void __launch_bounds__(NT)
     };
     auto entry = [&](uint32_t j, uint64_t& l, float& f) {
       if (j == row) {
-        const uint32_t e = self_edge[used[j]];
+        const uint32_t e = self_edge[ident ? j : used[j]];
         l = e_lat[e];
         f = e_loss[e];
       } else {
-        const uint64_t kk = key[used[j]];
+        const uint64_t kk = key[ident ? j : used[j]];
         sat |= fkey_lat(kk) == LAT32_SAT;
         l = fkey_lat(kk);
         f = __uint_as_float(fkey_loss_bits(kk));
@@ -833,7 +911,8 @@ __global__ void __launch_bounds__(NT)
 #pragma unroll
       for (int k = 0; k < OU; k++) {
         const uint32_t j = (tt + (uint32_t)k * NT) * 4;
-        uv[k] = __builtin_amdgcn_raw_buffer_load_b128(ru, j < n_used ? j * 4u : OOB, 0, 0);
+        if (ident) uv[k] = (u32x4){j, j + 1, j + 2, j + 3};
+        else uv[k] = __builtin_amdgcn_raw_buffer_load_b128(ru, j < n_used ? j * 4u : OOB, 0, 0);
       }
       const uint32_t de = self_edge[src];
       const uint64_t d_lat = e_lat[de];
@@ -894,10 +973,17 @@ __global__ void __launch_bounds__(NT)
       if (chain_on) s_psat = 1u;
     }
     if (dg) {
-      diag[bi * 8 + 0] = c_search - c_start;
-      diag[bi * 8 + 1] = clock64() - c_search;
+      diag[bi * SSSP_DIAG_WORDS + 0] = c_search - c_start;
+      diag[bi * SSSP_DIAG_WORDS + 1] = clock64() - c_search;
       // bucket advances (< 2^22) | chained, exact (bits 22, 23) | setup cycles
-      diag[bi * 8 + 3] = n_adv | ((unsigned long long)chain << 22) | ((c_setup - c_start) << 24);
+      diag[bi * SSSP_DIAG_WORDS + 3] = n_adv | ((unsigned long long)chain << 22) | ((c_setup - c_start) << 24);
+      // the set-up's parts: the listing up to the loads' issue, the LDS pass, the barrier, the
+      // first load round's wait and merge, the later rounds with the closing barrier
+      diag[bi * SSSP_DIAG_WORDS + 8] = c_init - c_list;
+      diag[bi * SSSP_DIAG_WORDS + 9] = c_list - c_start;
+      diag[bi * SSSP_DIAG_WORDS + 10] = c_bar - c_list;
+      diag[bi * SSSP_DIAG_WORDS + 11] = c_g0 - c_bar;
+      diag[bi * SSSP_DIAG_WORDS + 12] = c_setup - c_g0;
     }
     if constexpr (FLAG) {
       // Flagged rows: every wave waits for its sc1 stores, then one lane publishes the row
@@ -978,7 +1064,7 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
                        l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
                        l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
                        k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
-                       l.done, chain, ctx->apsp_ret + 4);
+                       l.done, chain, ctx->apsp_ret + 4, (int)l.ident);
   };
   // <counting, threads, lane arcs, fill symbol, flagged>
   if (l.done) {  // the flagged one-launch plan

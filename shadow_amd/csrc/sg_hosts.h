@@ -1,5 +1,6 @@
 // sg_hosts.h -- the device-resident host table and its address map, shared by the translation
-// units that resolve a packet's destination on the device (sg_deliver.hip, sg_link.hip).
+// units that resolve a packet's destination on the device (sg_deliver.hip; packet_item of
+// sg_walks.h for sg_link.hip, sg_paths.hip and sg_trace.hip).
 #pragma once
 
 #include "sg_internal.h"

@@ -115,13 +115,15 @@ struct sg_ctx {
   // host inputs and outputs (l_hops: sg_link_load_packets' per-packet hops), and the global
   // path's per-workgroup rows
   sg::DevBuf l_idx, l_flag, l_pred, l_cnt, l_link, l_node, l_scratch, l_hops;
-  // tree paths (sg_paths.hip; it shares l_idx, l_flag and l_pred): the hop count per pair and the
-  // scan's block sums, the device copies of host inputs (table rows, pair arrays) and outputs,
-  // and the pinned, mapped word that receives the record total (allocated on first use)
+  // (l_idx, l_flag and l_pred serve every walk up the tree rows: sg_link.hip, sg_paths.hip,
+  // sg_trace.hip)
+  // tree paths (sg_paths.hip): the hop count per pair, the device copies of host inputs (table
+  // rows, pair arrays) and outputs, and the pinned, mapped word that receives the record total
+  // (allocated on first use); p_sums: the block sums of scan_counts (sg_scan.hip), whoever calls
   sg::DevBuf p_cnt, p_sums, p_lat, p_loss, p_pair, p_off, p_node, p_link, p_olat, p_oloss;
   unsigned long long* paths_ret = nullptr;
-  // link trace (sg_trace.hip; it shares l_idx, l_flag, l_pred, p_cnt, p_sums, p_lat, p_off, the
-  // p_* outputs and paths_ret): the link counters with the fill's cursors and the work counter,
+  // link trace (sg_trace.hip; it shares p_cnt, p_lat, p_off, the p_* outputs and paths_ret, and
+  // p_sums through scan_counts): the link counters with the fill's cursors and the work counter,
   // the two staging arrays (keys, exit times), the sort's work entries, the device copies of a
   // host watch array and of out_exit_ns
   sg::DevBuf tr_cnt, tr_key, tr_key2, tr_exit, tr_exit2, tr_work, tr_watch, tr_oexit;
@@ -381,6 +383,10 @@ inline unsigned grid_for(size_t n, unsigned block, unsigned cap = 1u << 20) {
 
 // Exclusive scan of n u32 values (device, in -> out, out has n+1 entries, out[n] = total).
 void exclusive_scan_u32(sg_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint32_t n);
+// sg_scan.hip: the exclusive u64 scan of n u32 counts (any n), three launches on the context
+// stream: off[0 .. n] (off[n] = the sum) and *total = the sum (device-visible memory).  The
+// block sums live in ctx->p_sums.
+void scan_counts(sg_ctx* ctx, const uint32_t* cnt, uint32_t n, unsigned long long* off, unsigned long long* total);
 
 // Group offsets of a key array grouped by ascending key (sg_deliver.hip's
 // k_host_off): off[g] = first index whose key >= g, g = 0..n_groups.  err bit

@@ -78,7 +78,16 @@ constexpr size_t LINK_SCRATCH_BYTES = 16;  // global path: sub u64 + child count
 // flag words: the first (row << 32) | col of each kind
 enum { LINK_BAD_RANGE = 0, LINK_BAD_ROOT = 1, LINK_BAD_LINK = 2, LINK_BAD_CYCLE = 3, LINK_BAD_KINDS = 4 };
 
-// (LinkArgs, link_find and link_node_index: sg_links.h, shared with sg_paths.hip)
+// (LinkArgs, link_find and link_node_index: sg_links.h, shared with the walks of sg_walks.h)
+// The tree rows and what the dense fold alone takes.
+struct LinkFoldArgs : LinkArgs {  // (bad: LINK_BAD_KINDS words)
+  uint32_t count_cols;
+  const unsigned long long* counts;
+  unsigned long long* link_load;  // or null
+  unsigned long long* node_load;  // or null
+  unsigned char* scratch;         // global path: LINK_SCRATCH_BYTES * n per workgroup
+  int vec;                        // 16-byte loads are aligned in every row
+};
 
 // The per-node state of one row: in LDS (relaxed workgroup-scope accesses) or in the workgroup's
 // scratch row (agent-scope accesses at the L2).
@@ -135,7 +144,7 @@ struct LinkState {
 };
 
 template <bool LDS>
-__global__ void __launch_bounds__(1024) k_link_load(const LinkArgs a) {
+__global__ void __launch_bounds__(1024) k_link_load(const LinkFoldArgs a) {
   extern __shared__ __align__(16) unsigned char link_smem[];
   __shared__ uint32_t s_bad[LINK_BAD_KINDS], s_count;
   const uint32_t tid = threadIdx.x, T = blockDim.x, n = a.n;
@@ -281,10 +290,7 @@ __global__ void __launch_bounds__(1024) k_link_load(const LinkArgs a) {
 }
 
 // ---- sg_link_load_packets: a lane per packet walks its tree path
-// Flag words: the smallest failing (packet << 2) | kind; the first (row << 32) | col of each
-// pred kind; the packets counted.
-enum { LP_BAD_PACKET = 0, LP_BAD_RANGE = 1, LP_BAD_LINK = 2, LP_BAD_CYCLE = 3, LP_COUNTED = 4, LP_WORDS = 5 };
-enum { LP_PKT_SRC = 0, LP_PKT_ROW = 1, LP_PKT_DST = 2, LP_PKT_ROUTE = 3 };
+// (the item rule and the flag words: sg_walks.h; WALK_COUNTED = the packets counted)
 // Hops walked between two flushes of the global adds.  A no-return atomic stays counted in vmcnt
 // for hundreds of cycles, and the next dependent load waits for everything issued before it (every
 // wait in the code object is vmcnt(0)): with the adds after every hop each hop would pay that
@@ -294,7 +300,9 @@ constexpr int LP_HOPS = 4;
 // (LinkPacketArgs: sg_walks.h)
 
 // One counted packet's walk: weight w from column j up row i's tree; returns its hops.
-__device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t i, uint32_t j, unsigned long long w) {
+__device__ __forceinline__ uint32_t link_packet_walk(const LinkPacketArgs& a, uint32_t i, uint32_t j,
+                                                     unsigned long long w) {
+  const LinkArgs& l = a.l;
   const uint32_t n = l.n;
   const uint32_t s = l.nodes[i], d = l.nodes[j];
   const uint32_t* __restrict__ row = l.pred + (size_t)(i - l.row_begin) * n;
@@ -302,9 +310,9 @@ __device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t
   if (d == s) {  // the self-loop (get_edge_weight's rule), one hop
     const uint32_t k = link_find(l, s, s);
     if (k == LINK_NONE)
-      atomicMin(&l.bad[LP_BAD_LINK], cell | j);
-    else if (l.link_load)
-      atomicAdd(&l.link_load[k], w);
+      atomicMin(&l.bad[WALK_BAD_LINK], cell | j);
+    else if (a.link_load)
+      atomicAdd(&a.link_load[k], w);
     return 1u;
   }
   // v climbs from d; cv its column; pv = pred_i[v], gathered one hop ahead
@@ -318,13 +326,13 @@ __device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t
       vs[q] = 0u;
       if (!go) continue;
       if (steps >= n) {  // n steps and not at s: a cycle
-        atomicMin(&l.bad[LP_BAD_CYCLE], cell | j);
+        atomicMin(&l.bad[WALK_BAD_CYCLE], cell | j);
         go = false;
         continue;
       }
       const uint32_t u = pv;
       if (u >= n) {
-        atomicMin(&l.bad[LP_BAD_RANGE], cell | cv);
+        atomicMin(&l.bad[WALK_BAD_RANGE], cell | cv);
         go = false;
         continue;
       }
@@ -336,7 +344,7 @@ __device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t
       }
       const uint32_t k = link_find(l, u, v);
       if (k == LINK_NONE) {
-        atomicMin(&l.bad[LP_BAD_LINK], cell | cv);
+        atomicMin(&l.bad[WALK_BAD_LINK], cell | cv);
         go = false;
         continue;
       }
@@ -350,8 +358,8 @@ __device__ __forceinline__ uint32_t link_packet_walk(const LinkArgs& l, uint32_t
 #pragma unroll
     for (int q = 0; q < LP_HOPS; q++) {
       if (ks[q] == LINK_NONE) continue;
-      if (l.link_load) atomicAdd(&l.link_load[ks[q]], w);
-      if (l.node_load) atomicAdd(&l.node_load[vs[q]], w);
+      if (a.link_load) atomicAdd(&a.link_load[ks[q]], w);
+      if (a.node_load) atomicAdd(&a.node_load[vs[q]], w);
     }
   }
   return steps;
@@ -376,29 +384,13 @@ __global__ void __launch_bounds__(256) k_link_packets(const LinkPacketArgs a) {
     unsigned long long w = 0ull;
     bool walk = false;
     if (p < a.n_packets) {
-      const uint32_t h = a.src_host[p];
-      const bool counts = !a.status || a.status[p] == SG_PKT_DELIVERED;
-      uint32_t bad_packet = LINK_NONE;
-      if (h >= a.n_hosts) {
-        bad_packet = LP_PKT_SRC;
-      } else {
-        i = a.route[h];
-        if (i < l.row_begin || i - l.row_begin >= l.rows) bad_packet = LP_PKT_ROW;
+      uint32_t kind;
+      walk = packet_item(a.pk, l, p, i, j, kind);
+      if (kind != LINK_NONE) flag_item(l, p, kind);
+      if (walk) {
+        counted++;
+        w = a.weight ? (unsigned long long)a.weight[p] : 1ull;
       }
-      if (bad_packet == LINK_NONE && counts) {
-        const uint2 r = a.map.resolve(a.dst_ipv4[p]);
-        j = r.y;
-        if (r.x == NONE) {
-          bad_packet = LP_PKT_DST;
-        } else if (j >= l.n) {
-          bad_packet = LP_PKT_ROUTE;
-        } else {
-          walk = true;
-          counted++;
-          w = a.weight ? (unsigned long long)a.weight[p] : 1ull;
-        }
-      }
-      if (bad_packet != LINK_NONE) atomicMin(&l.bad[LP_BAD_PACKET], ((unsigned long long)p << 2) | bad_packet);
     }
     if (COMBINE) {
       const uint32_t lane = threadIdx.x & 63u;
@@ -415,17 +407,17 @@ __global__ void __launch_bounds__(256) k_link_packets(const LinkPacketArgs a) {
           sum += ((unsigned long long)whi << 32) | wlo;
         }
       }
-      if (walk && first == lane) hops = link_packet_walk(l, i, j, sum);
+      if (walk && first == lane) hops = link_packet_walk(a, i, j, sum);
       const uint32_t got = __shfl(hops, first);
       if (walk) hops = got;
     } else if (walk) {
-      hops = link_packet_walk(l, i, j, w);
+      hops = link_packet_walk(a, i, j, w);
     }
     if (a.hops && p < a.n_packets) a.hops[p] = hops;
   }
   if (counted) atomicAdd(&s_counted, counted);
   __syncthreads();
-  if (threadIdx.x == 0 && s_counted) atomicAdd(&l.bad[LP_COUNTED], (unsigned long long)s_counted);
+  if (threadIdx.x == 0 && s_counted) atomicAdd(&l.bad[WALK_COUNTED], (unsigned long long)s_counted);
 }
 
 // The most nodes the LDS path takes on this device: 14 bytes a node in what a workgroup may
@@ -497,6 +489,10 @@ void ensure_links(sg_ctx* ctx, sg_net* net) {
   net->links = true;
 }
 
+// What a pred row's error says, in the dense fold's decode and the walks' (throw_pred_error).
+static const char WHY_RANGE[] = "holds a node index out of range";
+static const char WHY_LINK[] = "names a predecessor that no link joins to the node (not a link)";
+
 // Rows [row_begin, row_end) folded into the device outputs (d_* row-major from row_begin).
 // Queues everything and synchronises once, on the flag words; `after` runs between the kernel
 // and that synchronisation (the copies of host outputs).
@@ -509,20 +505,12 @@ static void link_rows(sg_ctx* ctx, sg_net* net, const uint32_t* h_nodes, uint32_
   uint32_t* d_idx = link_node_index(ctx, h_nodes, n);
   unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LINK_BAD_KINDS);
   SG_HIP(hipMemsetAsync(bad, 0xff, LINK_BAD_KINDS * 8, stq));
-  LinkArgs a;
-  a.lk_off = net->lk_off;
-  a.lk_tail = net->lk_tail;
-  a.nodes = d_idx;
-  a.pos = d_idx + n;
-  a.n = n;
-  a.row_begin = row_begin;
-  a.rows = rows;
+  LinkFoldArgs a;
+  static_cast<LinkArgs&>(a) = link_args(net, d_idx, n, row_begin, rows, d_pred, bad);
   a.count_cols = count_cols;
-  a.pred = d_pred;
   a.counts = (const unsigned long long*)d_counts;
   a.link_load = (unsigned long long*)d_link;
   a.node_load = (unsigned long long*)d_node;
-  a.bad = bad;
   a.scratch = nullptr;
   a.vec = n % 4 == 0 && count_cols % 4 == 0 && ((uintptr_t)d_pred & 15) == 0 && ((uintptr_t)d_counts & 15) == 0;
   size_t lds_bytes = 0;
@@ -559,8 +547,7 @@ static void link_rows(sg_ctx* ctx, sg_net* net, const uint32_t* h_nodes, uint32_
   if (kind >= 0) {
     const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
     static const char* const why[LINK_BAD_KINDS] = {
-        "holds a node index out of range", "does not have pred[source] == source",
-        "names a predecessor that no link joins to the node (not a link)",
+        WHY_RANGE, "does not have pred[source] == source", WHY_LINK,
         "is never released: the row has a cycle, it is not a tree"};
     throw Error(SG_ERR_INVALID_ARG,
                 "the pred row of source node " + node_name(net, h_nodes[i]) + " at node " +
@@ -573,14 +560,45 @@ static void link_check_net(sg_ctx* ctx, sg_net* net) {
   if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
 }
 
+// ---- the walks' host side (sg_walks.h)
+PacketArgs packet_args(const sg_hosts* h, const sg_packets* packets, const uint8_t* status) {
+  return PacketArgs{HostMap{h->ip_base, h->dense_span, h->n, h->dense, h->sorted_ip, h->sorted_host},
+                    h->route,
+                    h->n,
+                    packets->src_host,
+                    packets->dst_ipv4,
+                    status};
+}
+
+void throw_item_error(bool packets, unsigned long long word) {
+  const uint64_t p = word >> 3;
+  const uint32_t kind = (uint32_t)(word & 7);
+  static const char* const why_packet[ITEM_TIME + 1] = {
+      "has a source host past the host table", "has a source host whose route row lies outside the row block",
+      "counts and has a destination address that no host holds", "resolves to a route index that is not below n_nodes",
+      "counts and has a send time plus path latency past 2^64 - 1 ns"};
+  static const char* const why_pair[ITEM_TIME + 1] = {"", "has a row outside the row block", "",
+                                                      "has a column that is not below n_nodes", ""};
+  throw Error(kind == ITEM_TIME ? SG_ERR_TIME_OVERFLOW : SG_ERR_INVALID_ARG,
+              std::string(packets ? "packet " : "pair ") + std::to_string(p) + " " +
+                  (packets ? why_packet : why_pair)[kind],
+              (uint32_t)p, 0xFFFFFFFFu);
+}
+
+void throw_pred_error(const sg_net* net, const uint32_t* nodes, int kind, unsigned long long word) {
+  const uint32_t i = (uint32_t)(word >> 32), j = (uint32_t)word;
+  const std::string why = kind == WALK_BAD_RANGE  ? std::string(WHY_RANGE) + " at node "
+                          : kind == WALK_BAD_LINK ? std::string(WHY_LINK) + " at node "
+                                                  : "does not reach its source within n_nodes steps (a cycle) from node ";
+  throw Error(SG_ERR_INVALID_ARG,
+              "the pred row of source node " + node_name(net, nodes[i]) + " " + why + node_name(net, nodes[j]), i, j);
+}
+
 // ---- sg_link_load_packets' halves (sg_walks.h)
 void link_packets_check(const LinkPacketsCall& c, bool check_nodes) {
-  link_check_net(c.ctx, c.net);
+  link_check_net(c.ctx, c.net);  // (ahead of the host table's: the order of this call's errors)
   if (!c.hosts || c.hosts->ctx != c.ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
-  if (c.n_nodes != c.net->n_nodes)
-    throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
-  if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-  if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  check_rows_call(c.ctx, c.net, c.nodes, c.n_nodes, c.row_begin, c.row_end);
   if (check_nodes) check_node_list(c.net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
   if (!c.packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
   if (c.packets->n_packets && (!c.packets->src_host || !c.packets->dst_ipv4))
@@ -591,38 +609,19 @@ void link_packets_check(const LinkPacketsCall& c, bool check_nodes) {
 void link_packets_enqueue(const LinkPacketsCall& c) {
   sg_ctx* ctx = c.ctx;
   sg_net* net = c.net;
-  const sg_hosts* hosts = c.hosts;
   hipStream_t st = ctx->stream;
   const uint32_t n = c.n_nodes, np = c.packets->n_packets;
   uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
-  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(LP_WORDS);
-  SG_HIP(hipMemsetAsync(bad, 0xff, LP_COUNTED * 8, st));
-  SG_HIP(hipMemsetAsync(bad + LP_COUNTED, 0, 8, st));
-  LinkPacketArgs a;
-  a.l.lk_off = net->lk_off;
-  a.l.lk_tail = net->lk_tail;
-  a.l.nodes = d_idx;
-  a.l.pos = d_idx + n;
-  a.l.n = n;
-  a.l.row_begin = c.row_begin;
-  a.l.rows = c.row_end - c.row_begin;
-  a.l.count_cols = 0;
-  a.l.pred = c.pred;
-  a.l.counts = nullptr;
-  a.l.link_load = (unsigned long long*)c.link_load;
-  a.l.node_load = (unsigned long long*)c.node_load;
-  a.l.bad = bad;
-  a.l.scratch = nullptr;
-  a.l.vec = 0;
-  a.map = HostMap{hosts->ip_base, hosts->dense_span, hosts->n, hosts->dense, hosts->sorted_ip, hosts->sorted_host};
-  a.route = hosts->route;
-  a.n_hosts = hosts->n;
-  a.n_packets = np;
-  a.src_host = c.packets->src_host;
-  a.dst_ipv4 = c.packets->dst_ipv4;
-  a.status = c.status;
-  a.weight = c.weight;
-  a.hops = c.hops;
+  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(WALK_WORDS_COUNTED);
+  SG_HIP(hipMemsetAsync(bad, 0xff, WALK_WORDS * 8, st));
+  SG_HIP(hipMemsetAsync(bad + WALK_COUNTED, 0, 8, st));
+  const LinkPacketArgs a{link_args(net, d_idx, n, c.row_begin, c.row_end - c.row_begin, c.pred, bad),
+                         packet_args(c.hosts, c.packets, c.status),
+                         np,
+                         c.weight,
+                         (unsigned long long*)c.link_load,
+                         (unsigned long long*)c.node_load,
+                         c.hops};
   // (work = the packets walked, added by the finish once the count is read)
   TimedLaunch tl(ctx, "link_packets", 0.0);
   const dim3 grid(grid_for(np, 256, 16u * (unsigned)ctx->n_cu));
@@ -635,34 +634,16 @@ void link_packets_enqueue(const LinkPacketsCall& c) {
 
 void link_packets_finish(const LinkPacketsCall& c) {
   sg_ctx* ctx = c.ctx;
-  unsigned long long h[LP_WORDS];
-  copy_to_host(ctx, h, ctx->l_flag.get<unsigned long long>(LP_WORDS), sizeof(h));
-  timer_add_work(ctx, "link_packets", (double)h[LP_COUNTED]);
+  unsigned long long h[WALK_WORDS_COUNTED];
+  copy_to_host(ctx, h, ctx->l_flag.get<unsigned long long>(WALK_WORDS_COUNTED), sizeof(h));
+  timer_add_work(ctx, "link_packets", (double)h[WALK_COUNTED]);
   // read_timer("link_packets_counted") = (0, the packets the last call counted, 0)
-  timer_set_counter(ctx, "link_packets_counted", 0.0, h[LP_COUNTED]);
-  if (h[LP_BAD_PACKET] != ~0ull) {
-    const uint64_t p = h[LP_BAD_PACKET] >> 2;
-    static const char* const why[4] = {
-        "has a source host past the host table", "has a source host whose route row lies outside the row block",
-        "counts and has a destination address that no host holds",
-        "resolves to a route index that is not below n_nodes"};
-    throw Error(SG_ERR_INVALID_ARG, "packet " + std::to_string(p) + " " + why[h[LP_BAD_PACKET] & 3], (uint32_t)p,
-                0xFFFFFFFFu);
-  }
+  timer_set_counter(ctx, "link_packets_counted", 0.0, h[WALK_COUNTED]);
+  if (h[WALK_BAD_ITEM] != ~0ull) throw_item_error(true, h[WALK_BAD_ITEM]);
   int kind = -1;
-  for (int k = LP_BAD_RANGE; k <= LP_BAD_CYCLE; k++)
+  for (int k = WALK_BAD_RANGE; k <= WALK_BAD_CYCLE; k++)
     if (h[k] != ~0ull && (kind < 0 || h[k] < h[kind])) kind = k;
-  if (kind >= 0) {
-    const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
-    static const char* const why[LP_BAD_CYCLE + 1] = {
-        "", "holds a node index out of range at node ",
-        "names a predecessor that no link joins to the node (not a link) at node ",
-        "does not reach its source within n_nodes steps (a cycle) from node "};
-    throw Error(SG_ERR_INVALID_ARG,
-                "the pred row of source node " + node_name(c.net, c.nodes[i]) + " " + why[kind] +
-                    node_name(c.net, c.nodes[j]),
-                i, j);
-  }
+  if (kind >= 0) throw_pred_error(c.net, c.nodes, kind, h[kind]);
 }
 
 }  // namespace sg
@@ -704,11 +685,7 @@ int32_t sg_link_load(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n
                      uint32_t count_cols, uint64_t* out_link_load, uint64_t* out_node_load) {
   return sg::guarded(ctx, [&] {
     using namespace sg;
-    link_check_net(ctx, net);
-    if (n_nodes != net->n_nodes)
-      throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
-    if (n_nodes && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-    if (row_begin > row_end || row_end > n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+    check_rows_call(ctx, net, nodes, n_nodes, row_begin, row_end);
     if (count_cols > n_nodes) throw Error(SG_ERR_INVALID_ARG, "count_cols is larger than n_nodes");
     check_node_list(net, nodes, n_nodes);  // in range and none twice: with n_nodes entries, a permutation
     if (!out_link_load && !out_node_load) throw Error(SG_ERR_INVALID_ARG, "null output");

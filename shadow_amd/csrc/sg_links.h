@@ -1,5 +1,7 @@
-// sg_links.h -- the link lookup and the node index, shared by the translation units that turn a
-// (pred, node) pair into a link number on the device (sg_link.hip, sg_paths.hip).
+// sg_links.h -- the tree rows of a call (LinkArgs), the link lookup and the node index, shared by
+// the translation units that turn a (pred, node) pair into a link number on the device: the dense
+// fold and the packet walk of sg_link.hip, sg_paths.hip and sg_trace.hip (the latter three through
+// the walks of sg_walks.h).  check_rows_call also serves sg_tree.hip, which writes the rows.
 #pragma once
 
 #include <cstring>
@@ -10,6 +12,7 @@ namespace sg {
 
 constexpr uint32_t LINK_NONE = 0xFFFFFFFFu;
 
+// What link_find and every walk up a pred row need.
 struct LinkArgs {
   // the net's links by head (ensure_links)
   const uint32_t* lk_off;
@@ -17,15 +20,10 @@ struct LinkArgs {
   // nodes[j] = the node of column j; pos = its inverse
   const uint32_t* nodes;
   const uint32_t* pos;
-  uint32_t n, row_begin, rows, count_cols;
+  uint32_t n, row_begin, rows;
   // rows [row_begin, row_begin + rows), row-major from row_begin
   const uint32_t* pred;
-  const unsigned long long* counts;
-  unsigned long long* link_load;  // or null
-  unsigned long long* node_load;  // or null
-  unsigned long long* bad;        // LINK_BAD_KINDS words
-  unsigned char* scratch;         // global path: LINK_SCRATCH_BYTES * n per workgroup
-  int vec;                        // 16-byte loads are aligned in every row
+  unsigned long long* bad;  // the call's flag words
 };
 
 // The link (tail -> head): its index, or LINK_NONE.
@@ -53,6 +51,23 @@ static inline uint32_t* link_node_index(sg_ctx* ctx, const uint32_t* h_nodes, ui
   SG_HIP(hipMemcpyAsync(d_idx, hu, 2 * (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   stage_release(ctx, 1);
   return d_idx;
+}
+
+// d_idx: link_node_index's.
+static inline LinkArgs link_args(const sg_net* net, const uint32_t* d_idx, uint32_t n, uint32_t row_begin,
+                                 uint32_t rows, const uint32_t* pred, unsigned long long* bad) {
+  return LinkArgs{net->lk_off, net->lk_tail, d_idx, d_idx + n, n, row_begin, rows, pred, bad};
+}
+
+// The argument checks every call over tree rows starts with (`what` spans every graph node).
+static inline void check_rows_call(const sg_ctx* ctx, const sg_net* net, const uint32_t* nodes, uint32_t n_nodes,
+                                   uint32_t row_begin, uint32_t row_end, const char* what = "a pred row") {
+  if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
+  if (n_nodes != net->n_nodes)
+    throw Error(SG_ERR_INVALID_ARG,
+                std::string(what) + " spans every graph node: n_nodes must be the network's node count");
+  if (n_nodes && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
+  if (row_begin > row_end || row_end > n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
 }
 
 }  // namespace sg

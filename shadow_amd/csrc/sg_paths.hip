@@ -12,13 +12,11 @@
 //
 // The output is CSR and deterministic: out_off (n + 1 u64, out_off[0] = 0), pair or packet p owns
 // records [out_off[p], out_off[p + 1]).  Three steps on the context stream:
-//   1. count (k_paths_count): a lane per pair or packet, grid-stride; the walk of
-//      link_packet_walk without its link search and its atomics: per hop pos[u] and pred_row[.],
-//      two dependent loads.  A value >= n is caught before it forms an index, a walk ends after n
-//      steps (a cycle).  Writes the hop count, 0 for a packet that does not count.
-//   2. scan: an exclusive u64 scan of the counts into out_off, reduce-then-scan in three launches
-//      (block sums; one workgroup over the sums, which also writes out_off[n] and the total into a
-//      pinned, mapped word; the add).  No workgroup waits on another inside a launch.
+//   1. count (k_paths_count): a lane per pair or packet, grid-stride; the count walk of
+//      sg_walks.h without the link search: per hop pos[u] and pred_row[.], two dependent loads.
+//      Writes the hop count, 0 for a packet that does not count.
+//   2. scan (scan_counts, sg_scan.hip): the exclusive u64 scan of the counts into out_off, with
+//      out_off[n] and the total into a pinned, mapped word.
 //   3. fill (k_paths_fill): the walk again, records written backwards from out_off[p + 1], so the
 //      order comes out source to destination; the next hop's gather is issued ahead of this hop's
 //      link search (link_find, sg_links.h), which is skipped when out_link is NULL.
@@ -39,36 +37,25 @@
 #include "sg_internal.h"
 #include "sg_knobs.h"
 #include "sg_links.h"
+#include "sg_walks.h"
 
 namespace sg {
 
-// Flag words: the smallest failing (index << 2) | kind; the first (row << 32) | col of each pred kind.
-enum { PA_BAD_ITEM = 0, PA_BAD_RANGE = 1, PA_BAD_LINK = 2, PA_BAD_CYCLE = 3, PA_WORDS = 4 };
-enum { PA_ITEM_SRC = 0, PA_ITEM_ROW = 1, PA_ITEM_DST = 2, PA_ITEM_COL = 3 };
+// (the item rule, the flag words and the walks: sg_walks.h)
 constexpr uint32_t PA_THREADS = 256;
-constexpr uint32_t PA_SCAN_PER = 8;  // counts per thread of the scan
-constexpr uint32_t PA_SCAN_TILE = PA_THREADS * PA_SCAN_PER;
-constexpr uint32_t PA_SUMS_THREADS = 1024;
 constexpr int PA_STAGE_HOPS = 640;      // records a wave stages (the default: 10 hops a lane)
 constexpr int PA_STAGE_HOPS_MAX = 1536;  // 4 waves x 20 bytes x 1536 = 120 KiB of the CU's 160
 
 struct PathArgs {
-  LinkArgs l;  // (counts, count_cols, link_load, node_load, scratch and vec unused; bad = PA_WORDS words)
+  LinkArgs l;  // (bad: WALK_WORDS words)
   // the packet form: the hosts' address map and the batch
-  HostMap map;
-  const uint32_t* route;  // host -> route index
-  uint32_t n_hosts;
-  const uint32_t* src_host;
-  const uint32_t* dst_ipv4;
-  const uint8_t* status;  // or null: every packet counts
+  PacketArgs pk;
   // the pair form
   const uint32_t* pair_row;
   const uint32_t* pair_col;
   uint32_t n_items;  // pairs or packets
   uint32_t* cnt;     // hops per item
-  unsigned long long* sums;  // the scan's block sums, then their exclusive prefix
-  unsigned long long* off;   // out_off
-  unsigned long long* total;  // the mapped word
+  unsigned long long* off;  // out_off
   // rows [row_begin, row_begin + rows) of the table, or null
   const unsigned long long* lat;
   const float* loss;
@@ -79,169 +66,26 @@ struct PathArgs {
   uint32_t stage_hops;
 };
 
-// Item p's (row, column); returns whether it has records.  kind: PA_ITEM_* when the item is in
-// error, else LINK_NONE.  The packet form is sg_link_load_packets' rule, the resolve sg_hosts.h's.
 template <bool PACKETS>
 __device__ __forceinline__ bool path_item(const PathArgs& a, uint32_t p, uint32_t& i, uint32_t& j, uint32_t& kind) {
-  const LinkArgs& l = a.l;
-  kind = LINK_NONE;
-  i = j = 0;
-  if (PACKETS) {
-    const uint32_t h = a.src_host[p];
-    const bool counts = !a.status || a.status[p] == SG_PKT_DELIVERED;
-    if (h >= a.n_hosts) {
-      kind = PA_ITEM_SRC;
-      return false;
-    }
-    i = a.route[h];
-    if (i < l.row_begin || i - l.row_begin >= l.rows) {
-      kind = PA_ITEM_ROW;
-      return false;
-    }
-    if (!counts) return false;
-    const uint2 r = a.map.resolve(a.dst_ipv4[p]);
-    j = r.y;
-    if (r.x == NONE) {
-      kind = PA_ITEM_DST;
-      return false;
-    }
-  } else {
-    i = a.pair_row[p];
-    j = a.pair_col[p];
-    if (i < l.row_begin || i - l.row_begin >= l.rows) {
-      kind = PA_ITEM_ROW;
-      return false;
-    }
-  }
-  if (j >= l.n) {
-    kind = PA_ITEM_COL;
-    return false;
-  }
-  return true;
+  return PACKETS ? packet_item(a.pk, a.l, p, i, j, kind) : pair_item(a.pair_row, a.pair_col, a.l, p, i, j, kind);
 }
 
 // ---- 1. count
 template <bool PACKETS>
 __global__ void __launch_bounds__(PA_THREADS) k_paths_count(const PathArgs a) {
   const LinkArgs& l = a.l;
-  const uint32_t n = l.n;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_items; q += stride) {
     const uint32_t p = (uint32_t)q;
     uint32_t i, j, kind;
     const bool walk = path_item<PACKETS>(a, p, i, j, kind);
-    if (kind != LINK_NONE) atomicMin(&l.bad[PA_BAD_ITEM], ((unsigned long long)p << 2) | kind);
-    uint32_t hops = 0;
-    if (walk) {
-      const uint32_t s = l.nodes[i], d = l.nodes[j];
-      hops = 1u;  // the self-loop (get_edge_weight's rule), one hop
-      if (d != s) {
-        const uint32_t* __restrict__ row = l.pred + (size_t)(i - l.row_begin) * n;
-        const unsigned long long cell = (unsigned long long)i << 32;
-        // cv = the column of the node the walk stands on; pv = its predecessor
-        uint32_t cv = j, pv = row[j], steps = 0;
-        for (;;) {
-          if (steps >= n) {  // n steps and not at s: a cycle
-            atomicMin(&l.bad[PA_BAD_CYCLE], cell | j);
-            steps = 0;
-            break;
-          }
-          if (pv >= n) {
-            atomicMin(&l.bad[PA_BAD_RANGE], cell | cv);
-            steps = 0;
-            break;
-          }
-          steps++;
-          if (pv == s) break;
-          cv = l.pos[pv];
-          pv = row[cv];
-        }
-        hops = steps;
-      }
-    }
-    a.cnt[p] = hops;
+    if (kind != LINK_NONE) flag_item(l, p, kind);
+    a.cnt[p] = walk ? count_walk<false>(l, i, j, [] {}) : 0u;
   }
 }
 
-// ---- 2. scan
-__device__ __forceinline__ unsigned long long wave_inclusive(unsigned long long x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// The exclusive prefix of x over the workgroup's threads (blockDim.x a multiple of 64, at most
-// 1024); *total = the sum.  s_wave: 16 words of LDS; every thread calls.
-__device__ __forceinline__ unsigned long long block_exclusive(unsigned long long x, unsigned long long* s_wave,
-                                                              unsigned long long* total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const unsigned long long inc = wave_inclusive(x);
-  __syncthreads();  // (the last call's reads of s_wave)
-  if (lane == 63) s_wave[w] = inc;
-  __syncthreads();
-  unsigned long long before = 0ull, all = 0ull;
-  for (uint32_t k = 0; k < nw; k++) {
-    const unsigned long long t = s_wave[k];
-    if (k < w) before += t;
-    all += t;
-  }
-  *total = all;
-  return before + inc - x;
-}
-
-__global__ void __launch_bounds__(PA_THREADS) k_paths_block_sums(const PathArgs a) {
-  __shared__ unsigned long long s_wave[16];
-  const size_t base = (size_t)blockIdx.x * PA_SCAN_TILE + (size_t)threadIdx.x * PA_SCAN_PER;
-  unsigned long long x = 0ull;
-#pragma unroll
-  for (uint32_t k = 0; k < PA_SCAN_PER; k++)
-    if (base + k < a.n_items) x += a.cnt[base + k];
-  unsigned long long total;
-  block_exclusive(x, s_wave, &total);
-  if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
-}
-
-// One workgroup: the block sums to their exclusive prefix, in place; out_off[n] and the total.
-__global__ void __launch_bounds__(PA_SUMS_THREADS) k_paths_scan_sums(const PathArgs a, uint32_t n_blocks) {
-  __shared__ unsigned long long s_wave[16];
-  unsigned long long carry = 0ull;
-  for (uint32_t base = 0; base < n_blocks; base += blockDim.x) {
-    const uint32_t b = base + threadIdx.x;
-    const unsigned long long x = b < n_blocks ? a.sums[b] : 0ull;
-    unsigned long long total;
-    const unsigned long long ex = block_exclusive(x, s_wave, &total);
-    if (b < n_blocks) a.sums[b] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    a.off[a.n_items] = carry;
-    *a.total = carry;
-  }
-}
-
-__global__ void __launch_bounds__(PA_THREADS) k_paths_scan_add(const PathArgs a) {
-  __shared__ unsigned long long s_wave[16];
-  const size_t base = (size_t)blockIdx.x * PA_SCAN_TILE + (size_t)threadIdx.x * PA_SCAN_PER;
-  uint32_t c[PA_SCAN_PER];
-  unsigned long long x = 0ull;
-#pragma unroll
-  for (uint32_t k = 0; k < PA_SCAN_PER; k++) {
-    c[k] = base + k < a.n_items ? a.cnt[base + k] : 0u;
-    x += c[k];
-  }
-  unsigned long long total;
-  unsigned long long at = a.sums[blockIdx.x] + block_exclusive(x, s_wave, &total);
-#pragma unroll
-  for (uint32_t k = 0; k < PA_SCAN_PER; k++) {
-    if (base + k < a.n_items) a.off[base + k] = at;
-    at += c[k];
-  }
-}
-
+// ---- 2. scan: scan_counts (sg_scan.hip)
 // ---- 3. fill
 // The staged records of one wave: its part of the dynamic LDS, an array per requested output
 // (latency first: 8-byte aligned).
@@ -308,7 +152,7 @@ __global__ void __launch_bounds__(PA_THREADS) k_paths_fill(const PathArgs a) {
         while (k > begin) {  // (the count's own bound: a lane never leaves its region)
           k--;
           const uint32_t u = pv;
-          if (u >= n) break;  // (the count pass reported it)
+          if (u >= n) break;  // (the count walk reported it)
           // the next hop's gather ahead of this hop's search: the search's dependent loads overlap it
           uint32_t cu = 0u;
           if (u != s) {
@@ -318,7 +162,7 @@ __global__ void __launch_bounds__(PA_THREADS) k_paths_fill(const PathArgs a) {
           uint32_t link = LINK_NONE;
           if (a.out_link) {
             link = link_find(l, u, v);
-            if (link == LINK_NONE) atomicMin(&l.bad[PA_BAD_LINK], cell | cv);
+            if (link == LINK_NONE) atomicMin(&l.bad[WALK_BAD_LINK], cell | cv);
           }
           if (STAGE && staged) {
             const uint32_t t = (uint32_t)(k - span_b);
@@ -380,11 +224,7 @@ static void paths_run(const PathCall& c) {
   sg_ctx* ctx = c.ctx;
   sg_net* net = c.net;
   const bool packets = c.packet_form;
-  if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
-  if (c.n_nodes != net->n_nodes)
-    throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
-  if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-  if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  check_rows_call(ctx, net, c.nodes, c.n_nodes, c.row_begin, c.row_end);
   check_node_list(net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
   if (!c.out_node && !c.out_link && !c.out_lat && !c.out_loss) throw Error(SG_ERR_INVALID_ARG, "no record output");
   if (!c.out_off || !c.total) throw Error(SG_ERR_INVALID_ARG, "null out_off or total");
@@ -447,46 +287,16 @@ static void paths_run(const PathCall& c) {
     d_off = ctx->p_off.get<uint64_t>((size_t)ni + 1);
   }
   uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
-  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(PA_WORDS);
-  SG_HIP(hipMemsetAsync(bad, 0xff, PA_WORDS * 8, st));
-  const uint32_t n_blocks = (uint32_t)(((size_t)ni + PA_SCAN_TILE - 1) / PA_SCAN_TILE);
+  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(WALK_WORDS);
+  SG_HIP(hipMemsetAsync(bad, 0xff, WALK_WORDS * 8, st));
   PathArgs a;
-  a.l.lk_off = net->lk_off;
-  a.l.lk_tail = net->lk_tail;
-  a.l.nodes = d_idx;
-  a.l.pos = d_idx + n;
-  a.l.n = n;
-  a.l.row_begin = c.row_begin;
-  a.l.rows = rows;
-  a.l.count_cols = 0;
-  a.l.pred = d_pred;
-  a.l.counts = nullptr;
-  a.l.link_load = nullptr;
-  a.l.node_load = nullptr;
-  a.l.bad = bad;
-  a.l.scratch = nullptr;
-  a.l.vec = 0;
-  a.map = HostMap{0, 0, 0, nullptr, nullptr, nullptr};
-  a.route = nullptr;
-  a.n_hosts = 0;
-  a.src_host = a.dst_ipv4 = nullptr;
-  a.status = nullptr;
-  if (packets) {
-    const sg_hosts* h = c.hosts;
-    a.map = HostMap{h->ip_base, h->dense_span, h->n, h->dense, h->sorted_ip, h->sorted_host};
-    a.route = h->route;
-    a.n_hosts = h->n;
-    a.src_host = c.packets->src_host;
-    a.dst_ipv4 = c.packets->dst_ipv4;
-    a.status = c.status;
-  }
+  a.l = link_args(net, d_idx, n, c.row_begin, rows, d_pred, bad);
+  a.pk = packets ? packet_args(c.hosts, c.packets, c.status) : PacketArgs{};
   a.pair_row = d_prow;
   a.pair_col = d_pcol;
   a.n_items = ni;
   a.cnt = ctx->p_cnt.get<uint32_t>(ni);
-  a.sums = ctx->p_sums.get<unsigned long long>(n_blocks);
   a.off = (unsigned long long*)d_off;
-  a.total = ctx->paths_ret;
   a.lat = (const unsigned long long*)d_lat;
   a.loss = d_loss;
   a.out_node = nullptr;
@@ -506,43 +316,18 @@ static void paths_run(const PathCall& c) {
   }
   {
     TimedLaunch tl(ctx, "tree_paths_scan", (double)ni);
-    hipLaunchKernelGGL(k_paths_block_sums, dim3(n_blocks), dim3(PA_THREADS), 0, st, a);
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_paths_scan_sums, dim3(1), dim3(PA_SUMS_THREADS), 0, st, a, n_blocks);
-    SG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_paths_scan_add, dim3(n_blocks), dim3(PA_THREADS), 0, st, a);
-    SG_CHECK_LAUNCH();
+    scan_counts(ctx, a.cnt, ni, a.off, ctx->paths_ret);
   }
   if (!dev) SG_HIP(hipMemcpyAsync(c.out_off, d_off, ((size_t)ni + 1) * 8, hipMemcpyDeviceToHost, st));
-  unsigned long long h[PA_WORDS];
+  unsigned long long h[WALK_WORDS];
   copy_to_host(ctx, h, bad, sizeof(h));
   const uint64_t tot = *ctx->paths_ret;
   timer_add_work(ctx, "tree_paths_count", (double)tot);
-  if (h[PA_BAD_ITEM] != ~0ull) {
-    const uint64_t p = h[PA_BAD_ITEM] >> 2;
-    static const char* const why_packet[4] = {
-        "has a source host past the host table", "has a source host whose route row lies outside the row block",
-        "counts and has a destination address that no host holds",
-        "resolves to a route index that is not below n_nodes"};
-    static const char* const why_pair[4] = {"", "has a row outside the row block", "",
-                                            "has a column that is not below n_nodes"};
-    throw Error(SG_ERR_INVALID_ARG,
-                std::string(packets ? "packet " : "pair ") + std::to_string(p) + " " +
-                    (packets ? why_packet : why_pair)[h[PA_BAD_ITEM] & 3],
-                (uint32_t)p, 0xFFFFFFFFu);
+  if (h[WALK_BAD_ITEM] != ~0ull) throw_item_error(packets, h[WALK_BAD_ITEM]);
+  if (h[WALK_BAD_RANGE] != ~0ull || h[WALK_BAD_CYCLE] != ~0ull) {
+    const int kind = h[WALK_BAD_RANGE] <= h[WALK_BAD_CYCLE] ? WALK_BAD_RANGE : WALK_BAD_CYCLE;
+    throw_pred_error(net, c.nodes, kind, h[kind]);
   }
-  auto pred_error = [&](int kind) {
-    const uint32_t i = (uint32_t)(h[kind] >> 32), j = (uint32_t)h[kind];
-    static const char* const why[PA_WORDS] = {
-        "", "holds a node index out of range at node ",
-        "names a predecessor that no link joins to the node (not a link) at node ",
-        "does not reach its source within n_nodes steps (a cycle) from node "};
-    throw Error(SG_ERR_INVALID_ARG,
-                "the pred row of source node " + node_name(net, c.nodes[i]) + " " + why[kind] + node_name(net, c.nodes[j]),
-                i, j);
-  };
-  if (h[PA_BAD_RANGE] != ~0ull || h[PA_BAD_CYCLE] != ~0ull)
-    pred_error(h[PA_BAD_RANGE] <= h[PA_BAD_CYCLE] ? PA_BAD_RANGE : PA_BAD_CYCLE);
   *c.total = tot;
   if (tot > c.cap)
     throw Error(SG_ERR_CAPACITY, "the paths hold " + std::to_string(tot) + " hop records, the arrays " + std::to_string(c.cap));
@@ -585,7 +370,7 @@ static void paths_run(const PathCall& c) {
     if (c.out_loss) SG_HIP(hipMemcpyAsync(c.out_loss, a.out_loss, tot * 4, hipMemcpyDeviceToHost, st));
   }
   copy_to_host(ctx, h, bad, sizeof(h));
-  if (h[PA_BAD_LINK] != ~0ull) pred_error(PA_BAD_LINK);
+  if (h[WALK_BAD_LINK] != ~0ull) throw_pred_error(net, c.nodes, WALK_BAD_LINK, h[WALK_BAD_LINK]);
 }
 
 }  // namespace sg

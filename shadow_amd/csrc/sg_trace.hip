@@ -13,13 +13,11 @@
 // walked and validated all the same.
 //
 // Steps on the context stream:
-//   1. count (k_trace_count): a lane per packet, grid-stride; sg_paths.hip's count walk with the
-//      link search (link_find, sg_links.h) per hop and a u32 add into the link's counter.  Writes
-//      the packet's hop count and every flag word: the walk is validated here once, whole.
-//   2. scan: the exclusive u64 scan of the link counters into out_link_off, reduce-then-scan in
-//      three launches (block sums; one workgroup over the sums, which also writes
-//      out_link_off[n_links] and the total into a pinned, mapped word; the add).  No workgroup
-//      waits on another inside a launch.
+//   1. count (k_trace_count): a lane per packet, grid-stride; the count walk of sg_walks.h with
+//      the link search (link_find, sg_links.h) per hop and a u32 add into the link's counter.
+//      Writes the packet's hop count and every flag word: the walk is validated here once, whole.
+//   2. scan (scan_counts, sg_scan.hip): the exclusive u64 scan of the link counters into
+//      out_link_off, with out_link_off[n_links] and the total into a pinned, mapped word.
 //   3. fill (k_trace_fill): the walk again; a record reserves its slot with an add on the link's
 //      cursor and stores its staging record there: the key (enter, packet) with the hop in one
 //      16-byte word, the exit time beside it when out_exit_ns is wanted.  The order inside a
@@ -53,188 +51,37 @@
 namespace sg {
 namespace {
 
-// Flag words: the smallest failing (packet << 3) | kind; the first (row << 32) | col of each pred kind.
-enum { TR_BAD_ITEM = 0, TR_BAD_RANGE = 1, TR_BAD_LINK = 2, TR_BAD_CYCLE = 3, TR_WORDS = 4 };
-enum { TR_ITEM_SRC = 0, TR_ITEM_ROW = 1, TR_ITEM_DST = 2, TR_ITEM_COL = 3, TR_ITEM_TIME = 4 };
+// (the item rule, the flag words and the walks: sg_walks.h)
 constexpr uint32_t TR_THREADS = 256;
-constexpr uint32_t TR_SCAN_PER = 8;  // counters per thread of the scan
-constexpr uint32_t TR_SCAN_TILE = TR_THREADS * TR_SCAN_PER;
-constexpr uint32_t TR_SUMS_THREADS = 1024;
 constexpr uint32_t TR_RANK_MAX = 64;     // a segment up to one wave: rank sort in registers
 constexpr uint32_t TR_PIECE_MAX = 2048;  // keys of one piece in LDS: 16 bytes x 2048 = 32 KiB
 
 // (TraceArgs, TraceOut: sg_walks.h)
-
-// Packet p's (row, column); returns whether it has records.  kind: TR_ITEM_* when the packet is in
-// error, else LINK_NONE.  sg_link_load_packets' rule, the resolve sg_hosts.h's.
-__device__ __forceinline__ bool trace_item(const TraceArgs& a, uint32_t p, uint32_t& i, uint32_t& j, uint32_t& kind) {
-  const LinkArgs& l = a.l;
-  kind = LINK_NONE;
-  i = j = 0;
-  const uint32_t h = a.src_host[p];
-  const bool counts = !a.status || a.status[p] == SG_PKT_DELIVERED;
-  if (h >= a.n_hosts) {
-    kind = TR_ITEM_SRC;
-    return false;
-  }
-  i = a.route[h];
-  if (i < l.row_begin || i - l.row_begin >= l.rows) {
-    kind = TR_ITEM_ROW;
-    return false;
-  }
-  if (!counts) return false;
-  const uint2 r = a.map.resolve(a.dst_ipv4[p]);
-  j = r.y;
-  if (r.x == NONE) {
-    kind = TR_ITEM_DST;
-    return false;
-  }
-  if (j >= l.n) {
-    kind = TR_ITEM_COL;
-    return false;
-  }
-  return true;
-}
 
 __device__ __forceinline__ bool watched(const TraceArgs& a, uint32_t link) { return !a.watch || a.watch[link] != 0; }
 
 // ---- 1. count
 __global__ void __launch_bounds__(TR_THREADS) k_trace_count(const TraceArgs a) {
   const LinkArgs& l = a.l;
-  const uint32_t n = l.n;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_items; q += stride) {
     const uint32_t p = (uint32_t)q;
     uint32_t i, j, kind;
-    const bool walk = trace_item(a, p, i, j, kind);
-    if (kind != LINK_NONE) atomicMin(&l.bad[TR_BAD_ITEM], ((unsigned long long)p << 3) | kind);
+    const bool walk = packet_item(a.pk, l, p, i, j, kind);
+    if (kind != LINK_NONE) flag_item(l, p, kind);
     uint32_t hops = 0;
     if (walk) {
-      const size_t r = (size_t)(i - l.row_begin) * n;
-      const unsigned long long cell = (unsigned long long)i << 32;
       // the destination's time bounds every hop's: arc latency is at least 1 ns, cum rises along the path
-      if (a.send_time[p] + a.lat[r + j] < a.send_time[p])
-        atomicMin(&l.bad[TR_BAD_ITEM], ((unsigned long long)p << 3) | TR_ITEM_TIME);
-      const uint32_t s = l.nodes[i], d = l.nodes[j];
-      if (d == s) {  // the self-loop (get_edge_weight's rule), one hop
-        const uint32_t link = link_find(l, s, s);
-        if (link == LINK_NONE)
-          atomicMin(&l.bad[TR_BAD_LINK], cell | j);
-        else if (watched(a, link))
-          atomicAdd(&a.cnt[link], 1u);
-        hops = 1u;
-      } else {
-        const uint32_t* __restrict__ row = l.pred + r;
-        // v = the node the walk stands on, cv its column; pv = its predecessor
-        uint32_t v = d, cv = j, pv = row[j], steps = 0;
-        for (;;) {
-          if (steps >= n) {  // n steps and not at s: a cycle
-            atomicMin(&l.bad[TR_BAD_CYCLE], cell | j);
-            steps = 0;
-            break;
-          }
-          if (pv >= n) {
-            atomicMin(&l.bad[TR_BAD_RANGE], cell | cv);
-            steps = 0;
-            break;
-          }
-          steps++;
-          const uint32_t link = link_find(l, pv, v);
-          if (link == LINK_NONE)
-            atomicMin(&l.bad[TR_BAD_LINK], cell | cv);
-          else if (watched(a, link))
-            atomicAdd(&a.cnt[link], 1u);
-          if (pv == s) break;
-          v = pv;
-          cv = l.pos[pv];
-          pv = row[cv];
-        }
-        hops = steps;
-      }
+      if (a.send_time[p] + a.lat[(size_t)(i - l.row_begin) * l.n + j] < a.send_time[p]) flag_item(l, p, ITEM_TIME);
+      hops = count_walk<true>(l, i, j, [&](uint32_t link, uint32_t) {
+        if (watched(a, link)) atomicAdd(&a.cnt[link], 1u);
+      });
     }
     a.hops[p] = hops;
   }
 }
 
-// ---- 2. scan (sg_paths.hip's form over the link counters)
-__device__ __forceinline__ unsigned long long tr_wave_inclusive(unsigned long long x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// The exclusive prefix of x over the workgroup's threads (blockDim.x a multiple of 64, at most
-// 1024); *total = the sum.  s_wave: 16 words of LDS; every thread calls.
-__device__ __forceinline__ unsigned long long tr_block_exclusive(unsigned long long x, unsigned long long* s_wave,
-                                                                 unsigned long long* total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const unsigned long long inc = tr_wave_inclusive(x);
-  __syncthreads();  // (the last call's reads of s_wave)
-  if (lane == 63) s_wave[w] = inc;
-  __syncthreads();
-  unsigned long long before = 0ull, all = 0ull;
-  for (uint32_t k = 0; k < nw; k++) {
-    const unsigned long long t = s_wave[k];
-    if (k < w) before += t;
-    all += t;
-  }
-  *total = all;
-  return before + inc - x;
-}
-
-__global__ void __launch_bounds__(TR_THREADS) k_trace_block_sums(const TraceArgs a) {
-  __shared__ unsigned long long s_wave[16];
-  const size_t base = (size_t)blockIdx.x * TR_SCAN_TILE + (size_t)threadIdx.x * TR_SCAN_PER;
-  unsigned long long x = 0ull;
-#pragma unroll
-  for (uint32_t k = 0; k < TR_SCAN_PER; k++)
-    if (base + k < a.n_links) x += a.cnt[base + k];
-  unsigned long long total;
-  tr_block_exclusive(x, s_wave, &total);
-  if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
-}
-
-// One workgroup: the block sums to their exclusive prefix, in place; out_link_off[n_links] and the total.
-__global__ void __launch_bounds__(TR_SUMS_THREADS) k_trace_scan_sums(const TraceArgs a, uint32_t n_blocks) {
-  __shared__ unsigned long long s_wave[16];
-  unsigned long long carry = 0ull;
-  for (uint32_t base = 0; base < n_blocks; base += blockDim.x) {
-    const uint32_t b = base + threadIdx.x;
-    const unsigned long long x = b < n_blocks ? a.sums[b] : 0ull;
-    unsigned long long total;
-    const unsigned long long ex = tr_block_exclusive(x, s_wave, &total);
-    if (b < n_blocks) a.sums[b] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    a.off[a.n_links] = carry;
-    *a.total = carry;
-  }
-}
-
-__global__ void __launch_bounds__(TR_THREADS) k_trace_scan_add(const TraceArgs a) {
-  __shared__ unsigned long long s_wave[16];
-  const size_t base = (size_t)blockIdx.x * TR_SCAN_TILE + (size_t)threadIdx.x * TR_SCAN_PER;
-  uint32_t c[TR_SCAN_PER];
-  unsigned long long x = 0ull;
-#pragma unroll
-  for (uint32_t k = 0; k < TR_SCAN_PER; k++) {
-    c[k] = base + k < a.n_links ? a.cnt[base + k] : 0u;
-    x += c[k];
-  }
-  unsigned long long total;
-  unsigned long long at = a.sums[blockIdx.x] + tr_block_exclusive(x, s_wave, &total);
-#pragma unroll
-  for (uint32_t k = 0; k < TR_SCAN_PER; k++) {
-    if (base + k < a.n_links) a.off[base + k] = at;
-    at += c[k];
-  }
-}
-
+// ---- 2. scan: scan_counts (sg_scan.hip)
 // ---- 3. fill
 __global__ void __launch_bounds__(TR_THREADS) k_trace_fill(const TraceArgs a) {
   const LinkArgs& l = a.l;
@@ -244,19 +91,19 @@ __global__ void __launch_bounds__(TR_THREADS) k_trace_fill(const TraceArgs a) {
     const uint32_t p = (uint32_t)q;
     uint32_t k = a.hops[p];  // the hop number of the record at hand: the walk climbs from d
     uint32_t i, j, kind;
-    if (k == 0 || !trace_item(a, p, i, j, kind)) continue;
+    if (k == 0 || !packet_item(a.pk, l, p, i, j, kind)) continue;
     const uint32_t s = l.nodes[i];
     const size_t r = (size_t)(i - l.row_begin) * n;
     const uint32_t* __restrict__ row = l.pred + r;
     const unsigned long long send = a.send_time[p];
     // v climbs from d; cv its column; pv = pred_i[v] (s itself for the self-loop's record),
-    // gathered one hop ahead of the link search
+    // gathered one hop ahead of the link search, and the cell of the hop's tail with it
     uint32_t v = l.nodes[j], cv = j;
     uint32_t pv = v == s ? s : row[j];
     unsigned long long exit = send + a.lat[r + cv];
     while (k > 0) {  // (the count's own bound)
       const uint32_t u = pv;
-      if (u >= n) break;  // (the count pass reported it)
+      if (u >= n) break;  // (the count walk reported it)
       uint32_t cu = 0u;
       unsigned long long enter = send;
       if (u != s) {
@@ -443,11 +290,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_trace_merge(const unsigned long 
 void trace_check(const TraceCall& c, bool check_nodes) {
   sg_ctx* ctx = c.ctx;
   sg_net* net = c.net;
-  if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
-  if (c.n_nodes != net->n_nodes)
-    throw Error(SG_ERR_INVALID_ARG, "a pred row spans every graph node: n_nodes must be the network's node count");
-  if (c.n_nodes && !c.nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-  if (c.row_begin > c.row_end || c.row_end > c.n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  check_rows_call(ctx, net, c.nodes, c.n_nodes, c.row_begin, c.row_end);
   if (check_nodes) check_node_list(net, c.nodes, c.n_nodes);  // in range and none twice: with n_nodes entries, a permutation
   if (!c.hosts || c.hosts->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "host table belongs to another context");
   if (!c.packets) throw Error(SG_ERR_INVALID_ARG, "null packets");
@@ -466,36 +309,15 @@ void trace_enqueue_count(const TraceCall& c, TraceJob& j) {
   const uint32_t nl = net->n_links;
   if (!ctx->paths_ret) SG_HIP(hipHostMalloc(&ctx->paths_ret, 16, hipHostMallocMapped | hipHostMallocCoherent));
   uint32_t* d_idx = link_node_index(ctx, c.nodes, n);
-  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(TR_WORDS);
-  SG_HIP(hipMemsetAsync(bad, 0xff, TR_WORDS * 8, st));
+  unsigned long long* bad = ctx->l_flag.get<unsigned long long>(WALK_WORDS);
+  SG_HIP(hipMemsetAsync(bad, 0xff, WALK_WORDS * 8, st));
   // the link counters, the fill's cursors and the work counter: one block, zeroed
   uint32_t* ctr = ctx->tr_cnt.get<uint32_t>(2 * (size_t)nl + 1);
   SG_HIP(hipMemsetAsync(ctr, 0, (2 * (size_t)nl + 1) * 4, st));
-  const uint32_t n_blocks = std::max(1u, (uint32_t)(((size_t)nl + TR_SCAN_TILE - 1) / TR_SCAN_TILE));
-  const sg_hosts* h = c.hosts;
   TraceArgs& a = j.a;
-  a.l.lk_off = net->lk_off;
-  a.l.lk_tail = net->lk_tail;
-  a.l.nodes = d_idx;
-  a.l.pos = d_idx + n;
-  a.l.n = n;
-  a.l.row_begin = c.row_begin;
-  a.l.rows = rows;
-  a.l.count_cols = 0;
-  a.l.pred = c.pred;
-  a.l.counts = nullptr;
-  a.l.link_load = nullptr;
-  a.l.node_load = nullptr;
-  a.l.bad = bad;
-  a.l.scratch = nullptr;
-  a.l.vec = 0;
-  a.map = HostMap{h->ip_base, h->dense_span, h->n, h->dense, h->sorted_ip, h->sorted_host};
-  a.route = h->route;
-  a.n_hosts = h->n;
-  a.src_host = c.packets->src_host;
-  a.dst_ipv4 = c.packets->dst_ipv4;
+  a.l = link_args(net, d_idx, n, c.row_begin, rows, c.pred, bad);
+  a.pk = packet_args(c.hosts, c.packets, c.status);
   a.send_time = (const unsigned long long*)c.packets->send_time_ns;
-  a.status = c.status;
   a.n_items = ni;
   a.hops = ctx->p_cnt.get<uint32_t>(ni);
   a.lat = (const unsigned long long*)c.lat;
@@ -503,9 +325,7 @@ void trace_enqueue_count(const TraceCall& c, TraceJob& j) {
   a.n_links = nl;
   a.cnt = ctr;
   a.cur = ctr + nl;
-  a.sums = ctx->p_sums.get<unsigned long long>(n_blocks);
   a.off = (unsigned long long*)c.off;
-  a.total = ctx->paths_ret;
   a.key = nullptr;
   a.exit = nullptr;
   j.n_work = ctr + 2 * (size_t)nl;
@@ -517,45 +337,21 @@ void trace_enqueue_count(const TraceCall& c, TraceJob& j) {
     hipLaunchKernelGGL(k_trace_count, dim3(j.grid), dim3(TR_THREADS), 0, st, a);
     SG_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_trace_block_sums, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
-  SG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_trace_scan_sums, dim3(1), dim3(TR_SUMS_THREADS), 0, st, a, n_blocks);
-  SG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_trace_scan_add, dim3(n_blocks), dim3(TR_THREADS), 0, st, a);
-  SG_CHECK_LAUNCH();
+  scan_counts(ctx, a.cnt, nl, a.off, ctx->paths_ret);
 }
 
 void trace_finish_count(const TraceCall& c, TraceJob& j) {
   sg_ctx* ctx = c.ctx;
-  unsigned long long hw[TR_WORDS];
+  unsigned long long hw[WALK_WORDS];
   copy_to_host(ctx, hw, j.a.l.bad, sizeof(hw));
   const uint64_t tot = *ctx->paths_ret;
   timer_add_work(ctx, "link_trace_count", (double)tot);
-  if (hw[TR_BAD_ITEM] != ~0ull) {
-    const uint64_t p = hw[TR_BAD_ITEM] >> 3;
-    const uint32_t kind = (uint32_t)(hw[TR_BAD_ITEM] & 7);
-    static const char* const why[5] = {
-        "has a source host past the host table", "has a source host whose route row lies outside the row block",
-        "counts and has a destination address that no host holds",
-        "resolves to a route index that is not below n_nodes",
-        "counts and has a send time plus path latency past 2^64 - 1 ns"};
-    throw Error(kind == TR_ITEM_TIME ? SG_ERR_TIME_OVERFLOW : SG_ERR_INVALID_ARG,
-                "packet " + std::to_string(p) + " " + why[kind], (uint32_t)p, 0xFFFFFFFFu);
+  if (hw[WALK_BAD_ITEM] != ~0ull) throw_item_error(true, hw[WALK_BAD_ITEM]);
+  if (hw[WALK_BAD_RANGE] != ~0ull || hw[WALK_BAD_CYCLE] != ~0ull) {
+    const int kind = hw[WALK_BAD_RANGE] <= hw[WALK_BAD_CYCLE] ? WALK_BAD_RANGE : WALK_BAD_CYCLE;
+    throw_pred_error(c.net, c.nodes, kind, hw[kind]);
   }
-  auto pred_error = [&](int kind) {
-    const uint32_t i = (uint32_t)(hw[kind] >> 32), k = (uint32_t)hw[kind];
-    static const char* const why[TR_WORDS] = {
-        "", "holds a node index out of range at node ",
-        "names a predecessor that no link joins to the node (not a link) at node ",
-        "does not reach its source within n_nodes steps (a cycle) from node "};
-    throw Error(SG_ERR_INVALID_ARG,
-                "the pred row of source node " + node_name(c.net, c.nodes[i]) + " " + why[kind] +
-                    node_name(c.net, c.nodes[k]),
-                i, k);
-  };
-  if (hw[TR_BAD_RANGE] != ~0ull || hw[TR_BAD_CYCLE] != ~0ull)
-    pred_error(hw[TR_BAD_RANGE] <= hw[TR_BAD_CYCLE] ? TR_BAD_RANGE : TR_BAD_CYCLE);
-  if (hw[TR_BAD_LINK] != ~0ull) pred_error(TR_BAD_LINK);
+  if (hw[WALK_BAD_LINK] != ~0ull) throw_pred_error(c.net, c.nodes, WALK_BAD_LINK, hw[WALK_BAD_LINK]);
   j.total = tot;
 }
 

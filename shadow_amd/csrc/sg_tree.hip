@@ -54,6 +54,7 @@
 #include "sg_device.h"
 #include "sg_internal.h"
 #include "sg_knobs.h"
+#include "sg_links.h"
 
 namespace sg {
 
@@ -377,11 +378,7 @@ static void tree_rows(sg_ctx* ctx, sg_net* net, const uint32_t* h_nodes, uint32_
 // The checks sg_routing_tree and sg_routing_build_tree share; none touches an output.
 static void tree_check_args(sg_ctx* ctx, sg_net* net, const uint32_t* nodes, uint32_t n_nodes, uint32_t row_begin,
                             uint32_t row_end) {
-  if (!net || net->ctx != ctx) throw Error(SG_ERR_INVALID_ARG, "network belongs to another context");
-  if (n_nodes != net->n_nodes)
-    throw Error(SG_ERR_INVALID_ARG, "a tree spans every graph node: n_nodes must be the network's node count");
-  if (n_nodes && !nodes) throw Error(SG_ERR_INVALID_ARG, "null node list");
-  if (row_begin > row_end || row_end > n_nodes) throw Error(SG_ERR_INVALID_ARG, "bad row range");
+  check_rows_call(ctx, net, nodes, n_nodes, row_begin, row_end, "a tree");
   check_node_list(net, nodes, n_nodes);  // in range and none twice: with n_nodes entries, a permutation
 }
 

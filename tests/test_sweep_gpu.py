@@ -338,8 +338,9 @@ def scan(oracle):
 
 @pytest.mark.parametrize("stage", ["1", "0"])
 def test_scan_second_trip(ctx, monkeypatch, scan, stage):
-    """k_paths_scan_sums carries its total from the first 1,024 block sums into the 1,025th
-    tile, whose only item is the last pair (a same-node pair: one record)."""
+    """The scan's one-workgroup kernel over the block sums (k_scan_sums, sg_scan.hip; the link
+    trace's scan too) carries its total from the first 1,024 block sums into the 1,025th tile,
+    whose only item is the last pair (a same-node pair: one record)."""
     monkeypatch.setenv("SG_PATHS_STAGE", stage)
     off, node, link = scan["want"]
     total, n_pairs = int(off[-1]), len(scan["ri"])

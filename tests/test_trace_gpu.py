@@ -584,6 +584,23 @@ def test_c3_shape(ctx):
     assert ascends[inside].all()
 
 
+@pytest.mark.parametrize("n_links", sorted(XC.SCAN_EDGE))
+def test_link_offsets_at_scan_tile_edges(ctx, n_links):
+    """(m): one below, at and one past one scan tile (2,048) of link counters, the smallest sizes
+    at which the scan's block boundary can go wrong for out_link_off: a path with 500 packets from
+    sources spread along it.  The rows are the path's own (trace_cases.scan_edge_tables)."""
+    assert SC.SCAN_TILE == 2048
+    n, loops = XC.SCAN_EDGE[n_links]
+    g = XC.scan_edge_graph(n, loops)
+    assert len(LR.links(g)[0]) == n_links
+    nodes, hosts, pk = XC.scan_edge_round(n)
+    rows = (0, XC.SCAN_EDGE_ROWS)
+    tabs = XC.scan_edge_tables(nodes)
+    want = XR.trace(g, nodes, rows, tabs[0], tabs[1], hosts, pk)
+    assert len(want[0]) == n_links + 1
+    _check(_net(g, ctx), nodes, rows, tabs, want, ht=_host_table(hosts, ctx), pb=_batch(pk), dev=True)
+
+
 @pytest.mark.parametrize("name", SC.NAMES)
 def test_sweep(oracle, ctx, name):
     """(k): the 40 generated graphs, each row block's round with its mixed statuses."""

@@ -138,7 +138,8 @@ def test_conservation(tie):
 def test_case_conditions(tie, oracle):
     """(a): every record shares its enter time with another record of its link, under the mixed
     statuses and under none.  (b): the tier cases' segment lengths are the list, exactly.  (f):
-    latencies past 2^32 ns, and a link whose enter times lie on both sides of 2^32."""
+    latencies past 2^32 ns, and a link whose enter times lie on both sides of 2^32.  (m): the
+    paths with 2,047, 2,048 and 2,049 links."""
     g, pk, nodes = tie["g"], tie["pk"], tie["nodes"]
     assert len(pk["src"]) == 10000
     for status in (tie["mixed"], None):
@@ -169,6 +170,24 @@ def test_case_conditions(tie, oracle):
                 assert np.array_equal(packet[a:a + n], np.arange(n)) and len(np.unique(enter[a:a + n])) == 1
         seen.append(n)
     assert seen == [1, 63, 64, 65, 127, 128, 129, 257, 383, 2049, 4097, 6143]
+    # (m): the link counts, the written-out rows against the tree reference, no packet to its
+    # sender's own node, sources spread along the path, and links in use in the tile's last counters
+    for nl, (n, loops) in XC.SCAN_EDGE.items():
+        ge = XC.scan_edge_graph(n, loops)
+        assert XR.n_links(ge) == nl == 2 * (n - 1) + loops
+        nodes_e, hosts, epk = XC.scan_edge_round(n)
+        rows_e = (0, XC.SCAN_EDGE_ROWS)
+        assert sorted(nodes_e.tolist()) == list(range(n))
+        pred_e, lat_e = XC.scan_edge_tables(nodes_e)
+        ref_pred, _, bad = R.tree_ref(ge, nodes_e, rows_e, lat_e, np.zeros(lat_e.shape, np.float32))
+        assert bad is None and np.array_equal(ref_pred, pred_e)
+        _, ri, cj = RR.counted_pairs(hosts, epk, None)
+        assert len(ri) == 500 and (ri != cj).all() and int(ri.max()) < XC.SCAN_EDGE_ROWS
+        src_nodes = np.unique(nodes_e[ri])
+        assert int(src_nodes.min()) < n // 8 and int(src_nodes.max()) > n - n // 8 and len(src_nodes) == XC.SCAN_EDGE_ROWS
+        off = XR.trace(ge, nodes_e, rows_e, pred_e, lat_e, hosts, epk)[0]
+        cnt = np.diff(off.astype(np.int64))
+        assert cnt[:8].any() and cnt[2040:].any() and int(cnt.max()) > 64
     gw = XC.wide_graph()
     nodesw, rowsw, latw, _, predw = _table(oracle, gw)
     hosts, wpk = XC.wide_round()

@@ -67,3 +67,43 @@ def wide_round(n_packets=3000, seed=51):
 
 def wide_graph():
     return TC.wide_graph()
+
+
+# (m): link counts one below, at and one past one tile of the link counters' scan (sweep_cases
+# SCAN_TILE = 2048) -> (nodes, self-loops) of scan_edge_graph: 2 (n - 1) + k links
+SCAN_EDGE = {2047: (1024, 1), 2048: (1025, 0), 2049: (1025, 1)}
+SCAN_EDGE_ROWS = 32
+
+
+def scan_edge_graph(n, k):
+    """(m): the undirected path 0 - 1 - ... - n-1 with 1 ms arcs, self-loops on the first k nodes only."""
+    v = np.arange(n)
+    src = np.concatenate([v[:k], v[:-1]])
+    dst = np.concatenate([v[:k], v[1:]])
+    return LC._graph(n, src, dst, np.full(len(src), 1_000_000))
+
+
+def scan_edge_round(n, n_packets=500, seed=61):
+    """(m): the node order j -> 37 j mod n (a permutation: 37 divides neither 1024 nor 1025), so
+    rows [0, SCAN_EDGE_ROWS) are sources spread along the path; a host per route index; packets
+    from the hosts of those rows to hosts anywhere but the sender's own (no self-loop is crossed:
+    most nodes have none).  Returns (nodes, hosts, packets)."""
+    nodes = ((np.arange(n, dtype=np.int64) * 37) % n).astype(np.uint32)
+    hosts = synth.make_hosts(n, n)
+    rng = np.random.default_rng(seed)
+    src = np.sort(rng.integers(0, SCAN_EDGE_ROWS, n_packets))
+    dst = rng.integers(0, n - 1, n_packets)
+    dst += dst >= src
+    pk = dict(src=src.astype(np.uint32), dst_ip=hosts["ip"][dst].astype(np.uint32), payload=np.zeros(n_packets, np.uint32),
+              send_time=np.uint64(T0) + rng.integers(0, 1_000_000, n_packets).astype(np.uint64))
+    return nodes, hosts, pk
+
+
+def scan_edge_tables(nodes):
+    """(m): (pred, latency_ns) rows [0, SCAN_EDGE_ROWS) of the path, written out: the routing build
+    refuses a used node without a self-loop, and a path has one tree per source anyway -- a node's
+    predecessor is its neighbour towards the source, 1 ms a hop.  (The diagonal cell, a self-loop's
+    latency, is left 0: no packet of the round reads it.)"""
+    v = np.asarray(nodes, np.int64)[None, :]
+    s = np.asarray(nodes, np.int64)[:SCAN_EDGE_ROWS, None]
+    return (v + np.sign(s - v)).astype(np.uint32), (np.abs(s - v) * 1_000_000).astype(np.uint64)

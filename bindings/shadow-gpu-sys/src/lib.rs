@@ -363,6 +363,9 @@ pub const SG_ERR_TIME_OVERFLOW: i32 = 11;
 /// sg_comm_*: RCCL could not be opened; sg_group_create: a pair of devices without peer access
 pub const SG_ERR_UNSUPPORTED: i32 = 12;
 
+/// sg_link_series_packets' `at`: the time of a crossing that chooses its bin
+pub const SG_SERIES_AT_ENTER: u32 = 0;
+pub const SG_SERIES_AT_EXIT: u32 = 1;
 pub const SG_TIMERS_ON: u32 = 1;
 pub const SG_TIMERS_COUNT_WORK: u32 = 2;
 /// network.use_shortest_path (configuration.rs:315-326)
@@ -492,6 +495,15 @@ unsafe extern "C" {
                                  watch: *const u8, out_link_off: *mut u64, out_packet: *mut u32,
                                  out_hop: *mut u32, out_enter_ns: *mut u64, out_exit_ns: *mut u64, cap: u64,
                                  total: *mut u64) -> i32;
+    /// Link time series: every crossing of the trace adds its packet's weight to the cell
+    /// (link_slot[link], (t - t0_ns) / bin_ns) of out_series (n_slots x n_bins u64, ADDED to), t the
+    /// enter or the exit time by `at` (SG_SERIES_AT_*); crossings before t0_ns or past the last bin
+    /// go to out_outside[2 s] / [2 s + 1] (or NULL).  link_slot NULL: the identity.
+    pub fn sg_link_series_packets(ctx: *mut sg_ctx, net: *mut sg_net, hosts: *mut sg_hosts, nodes: *const u32,
+                                  n_nodes: u32, row_begin: u32, row_end: u32, flags: u32, pred: *const u32,
+                                  latency_ns: *const u64, packets: *const sg_packets, status: *const u8,
+                                  weight: *const u32, link_slot: *const u32, n_slots: u32, at: u32, t0_ns: u64,
+                                  bin_ns: u64, n_bins: u32, out_series: *mut u64, out_outside: *mut u64) -> i32;
 
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;
@@ -687,4 +699,13 @@ unsafe extern "C" {
                                        out_packet: *mut u32, out_member: *mut u8, out_hop: *mut u32,
                                        out_enter_ns: *mut u64, out_exit_ns: *mut u64, cap: u64,
                                        total: *mut u64) -> i32;
+    /// sg_link_series_packets on every member at once; `link_slot` is a HOST map.  The members'
+    /// sums are added into root's arrays by one kernel: any error leaves them untouched.
+    pub fn sg_group_link_series_packets(g: *mut sg_group, nets: *mut *mut sg_net, hosts: *mut *mut sg_hosts,
+                                        nodes: *const u32, n_nodes: u32, row_begin: *const u32, row_end: *const u32,
+                                        pred: *mut *const u32, latency_ns: *mut *const u64,
+                                        packets: *const sg_packets, status: *mut *const u8,
+                                        weight: *mut *const u32, link_slot: *const u32, n_slots: u32, at: u32,
+                                        t0_ns: u64, bin_ns: u64, n_bins: u32, root: u32, out_series: *mut u64,
+                                        out_outside: *mut u64) -> i32;
 }

@@ -699,6 +699,64 @@ int32_t sg_link_trace_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
                               uint64_t* out_enter_ns, uint64_t* out_exit_ns,
                               uint64_t cap, uint64_t* total);
 
+/* ---- link time series: bytes per link per time bin (additive to ABI 7) ---------
+ * How busy each link was over time: the crossings of sg_link_trace_packets, each
+ * adding its packet's weight into one (slot, time bin) cell of a matrix that stays
+ * on the device across rounds.  No record is kept and nothing is sorted.  Pairs,
+ * counting rule, `nodes`, `pred`, the latency_ns rows, the row block, address
+ * resolution, link numbering, the crossings and their enter_ns / exit_ns are exactly
+ * those of sg_link_trace_packets; `weight` is sg_link_load_packets' (device u32 per
+ * packet; NULL: 1).  For every crossing of a counted packet p (weight w) on link L:
+ *   slot  s = link_slot[L].  link_slot has n_links u32 entries; NULL is the
+ *         identity, and n_slots must then equal n_links.  UINT32_MAX: the link is
+ *         not watched; its crossing is walked and validated all the same.  Several
+ *         links may share a slot (both directions of an edge, a cut set).
+ *   time  t = enter_ns for at == SG_SERIES_AT_ENTER, exit_ns for SG_SERIES_AT_EXIT.
+ *   cell  t < t0_ns:  out_outside[2 s] += w.  Else q = (t - t0_ns) / bin_ns, the
+ *         exact u64 quotient (bins closed below, open above):
+ *         q < n_bins:  out_series[s * n_bins + q] += w;
+ *         otherwise:   out_outside[2 s + 1] += w.
+ *         q is compared as a 64-bit value, and the decision is by the quotient, not
+ *         by an end time: t0_ns + n_bins * bin_ns may pass 2^64.
+ * All sums are u64, WRAP, and are ADDED to what the arrays hold: row blocks, group
+ * members and successive rounds sum into one matrix.  out_series (n_slots * n_bins
+ * u64) is required; out_outside (2 * n_slots u64) may be NULL.
+ * IDENTITY: for every slot s, the sum over b of out_series[s][b], plus
+ * out_outside[2 s] + out_outside[2 s + 1], equals the sum of sg_link_load_packets'
+ * out_link_load[L] over the links L of that slot, for either value of `at`.
+ *
+ * SG_ROUTE_OUT_DEVICE applies to pred, latency_ns, link_slot and both outputs;
+ * without it they are host arrays, staged as sg_link_load_packets stages its own
+ * (the device sums start at zero and are added into the host arrays).  The packet
+ * arrays, status and weight are always device memory.  Synchronises once.
+ *
+ * SG_ERR_INVALID_ARG, every output untouched: the argument errors of
+ * sg_link_trace_packets; bin_ns, n_bins or n_slots zero; at > 1; NULL out_series;
+ * NULL link_slot with n_slots != n_links; in host mode a slot value >= n_slots
+ * other than UINT32_MAX, sg_ctx_last_error_pair = (link, UINT32_MAX).  Found on the
+ * device (the outputs then undefined, as in sg_link_load_packets; never a trap,
+ * never a loop, and no index is ever formed from a bad value): first a bad slot
+ * value in device mode, the smallest such link of the whole map as (link,
+ * UINT32_MAX), which the walk treats as not watched; then the packet kinds of
+ * sg_link_trace_packets, SG_ERR_TIME_OVERFLOW the last of them; then the pred kinds
+ * with sg_link_load_packets' precedence: the smallest (row, col) in row-major order
+ * among a value >= n_nodes, a non-link and a cycle.
+ * Timers: "link_series" (work = packets walked); read_timer("link_series_counted")
+ * gives the packets the last call counted, read_timer("link_series_lds") whether
+ * it summed in per-workgroup LDS matrices (1) or straight into memory (0), and
+ * n_slots * (n_bins + 2), the cells that choice is made by (SG_LINK_SERIES_LDS). */
+#define SG_SERIES_AT_ENTER 0
+#define SG_SERIES_AT_EXIT 1
+int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
+                               const uint32_t* nodes, uint32_t n_nodes,
+                               uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                               const uint32_t* pred, const uint64_t* latency_ns,
+                               const sg_packets* packets, const uint8_t* status,
+                               const uint32_t* weight,
+                               const uint32_t* link_slot, uint32_t n_slots, uint32_t at,
+                               uint64_t t0_ns, uint64_t bin_ns, uint32_t n_bins,
+                               uint64_t* out_series, uint64_t* out_outside);
+
 /* ---- sharded delivery with a fixed-split exchange (no host round trip) ----
  * The same round as sg_deliver_source / sg_deliver_bucket, with every rank's
  * records for rank r in a block of `cap` slots, so the exchange is one
@@ -1332,8 +1390,31 @@ int32_t sg_group_alltoallv_records(sg_group* g, const sg_record** send, const ui
  * Timers, on root's context: "group_link_reduce" (work = accumulator words read),
  * "group_trace_offsets" and "group_trace_merge" (work = records); the members' own
  * timers are the single calls' ("link_packets", "link_trace_count",
- * "link_trace_fill", "link_trace_sort"). */
+ * "link_trace_fill", "link_trace_sort").
+ *
+ * sg_group_link_series_packets: sg_link_series_packets for the same sharding, with
+ * sg_group_link_load_packets' argument shape.  latency_ns[m] as in the group trace;
+ * weight[m] as in the group link loads; link_slot is a HOST map of n_links u32, or
+ * NULL (the identity), uploaded to every member as `watch` is and validated on the
+ * host; n_slots, at, t0_ns, bin_ns and n_bins as in the single call.  out_series and
+ * out_outside (or NULL) lie on root's device and are ADDED to.  Each member sums into
+ * a zeroed accumulator of its own; after every member's flags have been read, one
+ * kernel on root's stream adds the accumulators into the caller's arrays.  ANY error
+ * leaves the caller's arrays untouched; the lowest-numbered failing member is
+ * reported.  The result equals the single call on all rows with the batches
+ * concatenated; with n = 1 it is that call's, bit for bit.  Timers: "link_series" on
+ * the members, "group_link_reduce" on root. */
 uint32_t sg_group_last_error_member(const sg_group* g);
+int32_t sg_group_link_series_packets(sg_group* g, sg_net** nets, sg_hosts** hosts,
+                                     const uint32_t* nodes, uint32_t n_nodes,
+                                     const uint32_t* row_begin, const uint32_t* row_end,
+                                     const uint32_t** pred, const uint64_t** latency_ns,
+                                     const sg_packets* packets, const uint8_t** status,
+                                     const uint32_t** weight,
+                                     const uint32_t* link_slot, uint32_t n_slots, uint32_t at,
+                                     uint64_t t0_ns, uint64_t bin_ns, uint32_t n_bins,
+                                     uint32_t root,
+                                     uint64_t* out_series, uint64_t* out_outside);
 int32_t sg_group_link_load_packets(sg_group* g, sg_net** nets, sg_hosts** hosts,
                                    const uint32_t* nodes, uint32_t n_nodes,
                                    const uint32_t* row_begin, const uint32_t* row_end,

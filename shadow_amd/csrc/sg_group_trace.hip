@@ -13,6 +13,10 @@
 //   3. k_group_link_reduce on root's stream adds the n accumulators into the caller's arrays.
 //      Because the add is deferred past 2, an error leaves the caller's arrays untouched.
 //
+// sg_group_link_series_packets: the same three steps with sg_link_series_packets' walk; the
+// accumulators are a member's series matrix and outside cells (sr_series, sr_outside), the host
+// slot map goes to every member (sr_slot), and k_group_flat_reduce adds on root.
+//
 // sg_group_link_trace_packets
 //   1. every member counts and scans on its own stream: off_m (p_off) and total_m;
 //   2. the host reads flags and totals;
@@ -71,6 +75,26 @@ __global__ void __launch_bounds__(GT_THREADS) k_group_link_reduce(const ReduceAr
       for (uint32_t m = 0; m < n; m++)
         if (a.node[m]) s += a.node[m][i];
       out_node[i] += s;
+    }
+}
+
+// The same sum over two flat arrays of any length (the series matrix and its outside cells).
+__global__ void __launch_bounds__(GT_THREADS) k_group_flat_reduce(const ReduceArgs a, uint32_t n, size_t len_a,
+                                                                 size_t len_b, unsigned long long* out_a,
+                                                                 unsigned long long* out_b) {
+  const size_t gtid = (size_t)blockIdx.x * GT_THREADS + threadIdx.x, gsize = (size_t)gridDim.x * GT_THREADS;
+  for (size_t i = gtid; i < len_a; i += gsize) {
+    unsigned long long s = 0ull;
+    for (uint32_t m = 0; m < n; m++)
+      if (a.link[m]) s += a.link[m][i];
+    if (s) out_a[i] += s;
+  }
+  if (out_b)
+    for (size_t i = gtid; i < len_b; i += gsize) {
+      unsigned long long s = 0ull;
+      for (uint32_t m = 0; m < n; m++)
+        if (a.node[m]) s += a.node[m][i];
+      if (s) out_b[i] += s;
     }
 }
 
@@ -298,6 +322,81 @@ int32_t sg_group_link_load_packets(sg_group* g, sg_net** nets, sg_hosts** hosts,
         const unsigned grid = grid_for(std::max<size_t>(nl, n_nodes), GT_THREADS, 4u * (unsigned)rc->n_cu);
         hipLaunchKernelGGL(k_group_link_reduce, dim3(grid), dim3(GT_THREADS), 0, rc->stream, ra, n, nl, n_nodes,
                            (unsigned long long*)out_link_load, (unsigned long long*)out_node_load);
+        SG_CHECK_LAUNCH();
+      }
+      SG_HIP(hipStreamSynchronize(rc->stream));
+    });
+  });
+}
+
+int32_t sg_group_link_series_packets(sg_group* g, sg_net** nets, sg_hosts** hosts, const uint32_t* nodes,
+                                     uint32_t n_nodes, const uint32_t* row_begin, const uint32_t* row_end,
+                                     const uint32_t** pred, const uint64_t** latency_ns, const sg_packets* packets,
+                                     const uint8_t** status, const uint32_t** weight, const uint32_t* link_slot,
+                                     uint32_t n_slots, uint32_t at, uint64_t t0_ns, uint64_t bin_ns, uint32_t n_bins,
+                                     uint32_t root, uint64_t* out_series, uint64_t* out_outside) {
+  return sg::group_guarded(g, [&] {
+    using namespace sg;
+    const uint32_t n = group_check_members(g, nets, hosts, nodes, n_nodes, row_begin, row_end,
+                                           (const void* const*)pred, packets, root);
+    if (!latency_ns) throw Error(SG_ERR_INVALID_ARG, "null argument");
+    std::vector<SeriesCall> c(n);
+    std::vector<uint8_t> active(n, 0);
+    for (uint32_t m = 0; m < n; m++) {
+      // (slot and series: the caller's, for the check alone, which reads neither; the member's
+      // own copy and accumulator below)
+      c[m] = SeriesCall{g->ctxs[m], nets[m],    hosts[m],   nodes,
+                        n_nodes,    row_begin[m], row_end[m], pred[m],
+                        latency_ns[m], &packets[m], status ? status[m] : nullptr, weight ? weight[m] : nullptr,
+                        link_slot,  n_slots,    at,         t0_ns,
+                        bin_ns,     n_bins,     out_series, nullptr};
+      member_check(m, [&] {
+        set_device(g->ctxs[m]);  // (the check builds the member's links)
+        series_check(c[m], false);
+      });
+      c[m].slot = nullptr;
+      active[m] = packets[m].n_packets != 0;
+    }
+    check_node_list(nets[0], nodes, n_nodes);  // in range and none twice: with n_nodes entries, a permutation
+    const uint32_t nl = group_links(g, nets);
+    if (link_slot)
+      for (uint32_t k = 0; k < nl; k++)
+        if (link_slot[k] >= n_slots && link_slot[k] != 0xFFFFFFFFu)
+          throw Error(SG_ERR_INVALID_ARG,
+                      "link_slot[" + std::to_string(k) + "] is neither below n_slots nor UINT32_MAX", k, 0xFFFFFFFFu);
+    if (std::find(active.begin(), active.end(), 1) == active.end()) return;
+    const size_t n_series = (size_t)n_slots * n_bins, n_out = out_outside ? 2 * (size_t)n_slots : 0;
+    ReduceArgs ra{};
+    drained_on_error(g, [&] {
+      for (uint32_t m = 0; m < n; m++) {
+        if (!active[m]) continue;
+        sg_ctx* ctx = g->ctxs[m];
+        set_device(ctx);
+        if (link_slot) {
+          uint32_t* us = ctx->sr_slot.get<uint32_t>(nl);
+          if (nl) SG_HIP(hipMemcpyAsync(us, link_slot, (size_t)nl * 4, hipMemcpyHostToDevice, ctx->stream));
+          c[m].slot = us;
+        }
+        c[m].series = ctx->sr_series.get<uint64_t>(n_series);
+        SG_HIP(hipMemsetAsync(c[m].series, 0, n_series * 8, ctx->stream));
+        if (out_outside) {
+          c[m].outside = ctx->sr_outside.get<uint64_t>(n_out);
+          SG_HIP(hipMemsetAsync(c[m].outside, 0, n_out * 8, ctx->stream));
+        }
+        ra.link[m] = (const unsigned long long*)c[m].series;
+        ra.node[m] = (const unsigned long long*)c[m].outside;
+        series_enqueue(c[m]);
+      }
+      finish_members(g, active, [&](uint32_t m) { series_finish(c[m]); });
+      root_waits(g, root, active);
+      sg_ctx* rc = g->ctxs[root];
+      {
+        // work = the accumulator words read
+        TimedLaunch tl(rc, "group_link_reduce",
+                       (double)std::count(active.begin(), active.end(), 1) * ((double)n_series + (double)n_out));
+        const unsigned grid = grid_for(std::max(n_series, n_out), GT_THREADS, 4u * (unsigned)rc->n_cu);
+        hipLaunchKernelGGL(k_group_flat_reduce, dim3(grid), dim3(GT_THREADS), 0, rc->stream, ra, n, n_series, n_out,
+                           (unsigned long long*)out_series, (unsigned long long*)out_outside);
         SG_CHECK_LAUNCH();
       }
       SG_HIP(hipStreamSynchronize(rc->stream));

@@ -127,6 +127,9 @@ struct sg_ctx {
   // the two staging arrays (keys, exit times), the sort's work entries, the device copies of a
   // host watch array and of out_exit_ns
   sg::DevBuf tr_cnt, tr_key, tr_key2, tr_exit, tr_exit2, tr_work, tr_watch, tr_oexit;
+  // link time series (sg_series.hip; it shares l_idx, l_flag, l_pred and p_lat): the device copy
+  // of a host slot map, and the zeroed sums of a host-mode call or of a group member
+  sg::DevBuf sr_slot, sr_series, sr_outside;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

@@ -1,11 +1,11 @@
 // sg_walks.h -- the walk up a row's predecessor tree, from a destination column to the row's
 // source, and what its users share: sg_link_load_packets (sg_link.hip), sg_tree_paths and
-// sg_tree_paths_packets (sg_paths.hip), sg_link_trace_packets (sg_trace.hip) and the two group
-// forms on top of them (sg_group_trace.hip).
+// sg_tree_paths_packets (sg_paths.hip), sg_link_trace_packets (sg_trace.hip),
+// sg_link_series_packets (sg_series.hip) and the group forms on top of them (sg_group_trace.hip).
 //   - the item rule: a packet or a pair to its (row, column), or the kind of its error;
 //   - the flag words a call's kernels report through, and the host's decode of them;
 //   - the count walk;
-//   - the per-packet walks of a round (link loads, link trace) as ENQUEUE and FINISH halves.  The
+//   - the per-packet walks of a round (link loads, link trace, link series) as ENQUEUE and FINISH halves.  The
 //     single-context entry points run the halves back to back; a device group enqueues every
 //     member's first half, then finishes them one by one, so that all members are in flight at once.
 //
@@ -238,5 +238,36 @@ void trace_enqueue_count(const TraceCall& c, TraceJob& j);
 void trace_finish_count(const TraceCall& c, TraceJob& j);
 // Fill and the three sort tiers into `out` (j.total > 0 records each; null arrays are skipped).
 void trace_enqueue_sort(const TraceCall& c, TraceJob& j, const TraceOut& out);
+
+// ---- link time series (sg_series.hip)
+// Flag words: the walks' four, the packets counted, and the smallest link whose slot value is
+// neither below n_slots nor UINT32_MAX.
+enum { SERIES_BAD_SLOT = 5, SERIES_WORDS = 6 };
+
+struct SeriesCall {
+  sg_ctx* ctx;
+  sg_net* net;
+  sg_hosts* hosts;
+  const uint32_t* nodes;
+  uint32_t n_nodes, row_begin, row_end;
+  const uint32_t* pred;
+  const uint64_t* lat;
+  const sg_packets* packets;
+  const uint8_t* status;
+  const uint32_t* weight;
+  const uint32_t* slot;  // n_links entries, or null: the identity
+  uint32_t n_slots, at;
+  uint64_t t0, bin;
+  uint32_t n_bins;
+  uint64_t* series;   // n_slots x n_bins, added to
+  uint64_t* outside;  // 2 n_slots, added to, or null
+};
+
+// The argument errors of sg_link_series_packets but those of the slot values; builds the net's
+// links (a null slot map needs their count).
+void series_check(const SeriesCall& c, bool check_nodes);
+// The walk of c.packets (n_packets > 0) on the context stream.
+void series_enqueue(const SeriesCall& c);
+void series_finish(const SeriesCall& c);
 
 }  // namespace sg

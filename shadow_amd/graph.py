@@ -180,6 +180,24 @@ class PathTable:
             yield k, self[k]
 
 
+def series_slots(slots, n_links: int) -> Tuple[Optional[np.ndarray], int]:
+    """(slot map or None, n_slots) of link_series_round's `slots`: None (the identity), a full map
+    (a u32 numpy array of one entry per link; n_slots = its largest slot + 1, 0xFFFFFFFF not
+    counted) or a list of link numbers (slot = position)."""
+    if slots is None:
+        return None, n_links
+    if isinstance(slots, np.ndarray) and slots.dtype == np.uint32 and slots.shape == (n_links,):
+        m = np.ascontiguousarray(slots)
+        watched = m[m != 0xFFFFFFFF]
+        return m, int(watched.max()) + 1 if len(watched) else 1
+    idx = np.asarray(slots).astype(np.int64).ravel()
+    if len(idx) == 0 or idx.min() < 0 or idx.max() >= n_links or len(np.unique(idx)) != len(idx):
+        raise ValueError(f"slots: distinct link numbers below {n_links}, at least one")
+    m = np.full(n_links, 0xFFFFFFFF, np.uint32)
+    m[idx] = np.arange(len(idx), dtype=np.uint32)
+    return m, len(idx)
+
+
 class PathTree:
     """Shortest-path trees beside their table rows (sg_routing_build_tree).
 
@@ -420,6 +438,67 @@ class PathTree:
         check(g.ctx.handle, rc)
         t = total.value
         return off, pkt[:t], hop[:t], enter[:t], leave[:t]
+
+    def link_series_round(self, hosts, packets, status=None, weight=None, *, t0_ns: int, bin_ns: int, n_bins: int,
+                          slots=None, at: str = "enter", out=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The link time series of one round's batch, (series, outside): series[s, b] (u64, n_slots
+        x n_bins) is the weight of the counted packets that crossed a link of slot s at a time t
+        with t0_ns + b bin_ns <= t < t0_ns + (b + 1) bin_ns, t the crossing's enter_ns (at =
+        "enter") or exit_ns ("exit") as link_trace_round gives them; outside[s] = (the weight
+        before t0_ns, the weight at or past the last bin's end).  hosts, packets and status as in
+        trace_round, weight as in link_load_round.  slots: None (a slot per link, in
+        NetworkGraph.links() order), a list of link numbers (slot = position in the list) or a
+        full u32 map of one entry per link (0xFFFFFFFF: not watched; links may share a slot).
+        out: a previous result to add into, so that a loop over rounds keeps one matrix
+        (sg_link_series_packets)."""
+        import torch
+
+        if at not in ("enter", "exit"):
+            raise ValueError('at: "enter" or "exit"')
+        npk = len(packets)
+        dev = packets.src_host.device
+
+        def to_dev(x, np_dtype, t_dtype, what):
+            if isinstance(x, torch.Tensor):
+                x = x.to(device=dev).contiguous()
+                if x.element_size() != np.dtype(np_dtype).itemsize or x.is_floating_point():
+                    raise ValueError(f"{what}: a {np.dtype(np_dtype).name} array")
+                x = x.view(t_dtype)
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).view(
+                    np.int32 if t_dtype == torch.int32 else np.uint8)).to(dev)
+            if x.numel() < npk:
+                raise ValueError(f"{what}: {npk} entries, one per packet")
+            return x
+
+        if status is not None:
+            status = to_dev(getattr(status, "status", status), np.uint8, torch.uint8, "status")
+        if isinstance(weight, str):
+            if weight != "payload":
+                raise ValueError('weight: None, "payload" or an array')
+            weight = packets.payload_len
+        if weight is not None:
+            weight = to_dev(weight, np.uint32, torch.int32, "weight")
+        g, n = self._graph, len(self.nodes)
+        n_links = len(g.links()[0])
+        slot_map, n_slots = series_slots(slots, n_links)
+        if out is None:
+            series, outside = np.zeros((n_slots, int(n_bins)), np.uint64), np.zeros((n_slots, 2), np.uint64)
+        else:
+            series, outside = out
+            if (series.dtype != np.uint64 or outside.dtype != np.uint64 or series.shape != (n_slots, int(n_bins))
+                    or outside.shape != (n_slots, 2) or not series.flags.c_contiguous or not outside.flags.c_contiguous):
+                raise ValueError(f"out: a previous result of this shape, u64 ({n_slots}, {int(n_bins)}) and ({n_slots}, 2)")
+        pred = np.ascontiguousarray(self.pred, dtype=np.uint32)
+        tlat = np.ascontiguousarray(self.latency_ns, dtype=np.uint64)
+        p = packets.c_struct()
+        check(g.ctx.handle, load().sg_link_series_packets(
+            g.ctx.handle, g._ensure_net(), hosts.handle, self.nodes.ctypes.data, n, 0, self.n_sources, 0,
+            pred.ctypes.data, tlat.ctypes.data, C.byref(p), None if status is None else C.c_void_p(status.data_ptr()),
+            None if weight is None else C.c_void_p(weight.data_ptr()),
+            None if slot_map is None else slot_map.ctypes.data, n_slots, 0 if at == "enter" else 1, int(t0_ns),
+            int(bin_ns), int(n_bins), series.ctypes.data, outside.ctypes.data))
+        return series, outside
 
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
@@ -769,6 +848,27 @@ class NetworkGraph:
         if rc != _capi.SG_ERR_CAPACITY:
             check(self.ctx.handle, rc)
         return rc, total.value
+
+    def link_series_packets_device(self, hosts, nodes: Sequence[int], row_begin: int, row_end: int, pred_ptr: int,
+                                   latency_ptr: int, packets, status_ptr: int, weight_ptr: int, slot_ptr: int,
+                                   n_slots: int, at: int, t0_ns: int, bin_ns: int, n_bins: int, series_ptr: int,
+                                   outside_ptr: int) -> None:
+        """One round's batch (a PacketBatch from hosts of `hosts`, a HostTable) added into a device
+        matrix of n_slots x n_bins u64 cells through device pred rows [row_begin, row_end) and the
+        same rows of the device latency table: every crossing of a counted packet adds the packet's
+        weight (device u32, 0: 1) to the cell (slot[link], (t - t0_ns) // bin_ns), t its enter
+        (at = 0) or exit (at = 1) time; crossings before t0_ns or past the last bin go to
+        outside[2 s] / outside[2 s + 1] (device u64, 2 n_slots, or 0).  slot: device u32 per link of
+        links(), 0xFFFFFFFF for a link not watched, or 0: the identity, with n_slots the link
+        count.  status as in link_load_packets_device (sg_link_series_packets)."""
+        used = np.ascontiguousarray(nodes, dtype=np.uint32)
+        p = packets.c_struct()
+        check(self.ctx.handle, load().sg_link_series_packets(
+            self.ctx.handle, self._ensure_net(), hosts.handle, used.ctypes.data, len(used), int(row_begin),
+            int(row_end), _capi.SG_ROUTE_OUT_DEVICE, C.c_void_p(pred_ptr), C.c_void_p(latency_ptr or None), C.byref(p),
+            C.c_void_p(status_ptr or None), C.c_void_p(weight_ptr or None), C.c_void_p(slot_ptr or None), int(n_slots),
+            int(at), int(t0_ns), int(bin_ns), int(n_bins), C.c_void_p(series_ptr or None),
+            C.c_void_p(outside_ptr or None)))
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

@@ -288,6 +288,62 @@ class Group:
                 hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
                 leave[:t].cpu().numpy().view(np.uint64))
 
+    def link_series_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, t0_ns: int, bin_ns: int,
+                          n_bins: int, slots=None, at: str = "enter", out=None, root: int = 0):
+        """The link time series of one sharded round, (series, outside): PathTree.link_series_round
+        over every member's batch at once, the members' sums added on member `root`'s device
+        (sg_group_link_series_packets).  graphs, hosts, rows (with the latency rows), packets and
+        status as in link_trace_round, weight as in link_load_round; t0_ns, bin_ns, n_bins, slots,
+        at and out as in PathTree.link_series_round.  Equals the single call on the concatenated
+        batch."""
+        import torch
+
+        from .graph import series_slots
+
+        if at not in ("enter", "exit"):
+            raise ValueError('at: "enter" or "exit"')
+        a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, True)
+        wt = None
+        if weight is not None:
+            if isinstance(weight, str):
+                if weight != "payload":
+                    raise ValueError('weight: None, "payload" or one array per member')
+                weight = [p.payload_len for p in packets]
+            wt = []
+            for m, w in enumerate(weight):
+                if w is not None and not isinstance(w, torch.Tensor):
+                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
+                wt.append(None if w is None else w.to(device=devs[m]).contiguous())
+                if wt[m] is not None and (wt[m].element_size() != 4 or wt[m].numel() < len(packets[m])):
+                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
+        n_links = len(graphs[root].links()[0])
+        slot_map, n_slots = series_slots(slots, n_links)
+        n_bins = int(n_bins)
+        if out is not None:
+            series, outside = out
+            if (series.dtype != np.uint64 or outside.dtype != np.uint64 or series.shape != (n_slots, n_bins)
+                    or outside.shape != (n_slots, 2)):
+                raise ValueError(f"out: a previous result of this shape, u64 ({n_slots}, {n_bins}) and ({n_slots}, 2)")
+            d_series = torch.from_numpy(np.ascontiguousarray(series).view(np.int64)).to(devs[root])
+            d_out = torch.from_numpy(np.ascontiguousarray(outside).view(np.int64)).to(devs[root])
+        else:
+            d_series = torch.zeros((n_slots, max(n_bins, 1)), dtype=torch.int64, device=devs[root])
+            d_out = torch.zeros((n_slots, 2), dtype=torch.int64, device=devs[root])
+        for d in devs:
+            torch.cuda.synchronize(d)
+        self._check(load().sg_group_link_series_packets(
+            self.handle, a["nets"], a["hosts"], a["nodes"].ctypes.data, len(a["nodes"]), a["row_begin"], a["row_end"],
+            a["pred"], a["lat"], a["packets"], a["status"], None if wt is None else _ptrs(wt),
+            None if slot_map is None else slot_map.ctypes.data, n_slots, 0 if at == "enter" else 1, int(t0_ns),
+            int(bin_ns), n_bins, int(root), d_series.data_ptr(), d_out.data_ptr()))
+        del keep
+        got = (d_series.cpu().numpy().view(np.uint64).reshape(n_slots, -1)[:, :n_bins],
+               d_out.cpu().numpy().view(np.uint64).reshape(n_slots, 2))
+        if out is None:
+            return got
+        series[...], outside[...] = got
+        return series, outside
+
 
 class GroupDelivery:
     """The single-process driver of a sharded delivery round: dist.ShardedDelivery.round for all

@@ -504,6 +504,17 @@ unsafe extern "C" {
                                   latency_ns: *const u64, packets: *const sg_packets, status: *const u8,
                                   weight: *const u32, link_slot: *const u32, n_slots: u32, at: u32, t0_ns: u64,
                                   bin_ns: u64, n_bins: u32, out_series: *mut u64, out_outside: *mut u64) -> i32;
+    /// Link queues: the FIFO wait of every record of a link trace (link_off, enter_ns, packet) under a
+    /// per-link service cost (cost_ps picoseconds per unit of weight[packet[i]], NULL weight: 1), the
+    /// server free from link_free_in[L] (NULL: 0).  Per record wait, done and the records ahead; per
+    /// link the new free time, the busy time, the largest and the summed wait, the deepest queue.
+    /// First order: a wait is not propagated to the packet's later hops.
+    pub fn sg_link_queue(ctx: *mut sg_ctx, flags: u32, n_links: u32, link_off: *const u64, n_records: u64,
+                         enter_ns: *const u64, packet: *const u32, weight: *const u32, n_weights: u32,
+                         cost_ps: *const u64, link_free_in: *const u64, out_wait_ns: *mut u64,
+                         out_done_ns: *mut u64, out_ahead: *mut u32, out_link_free: *mut u64,
+                         out_link_busy_ns: *mut u64, out_link_wait_max_ns: *mut u64,
+                         out_link_wait_sum_ns: *mut u64, out_link_ahead_max: *mut u32) -> i32;
 
     // ---- host-side dense RoutingInfo: generate_routing_info (sim_config.rs:411-448) ----
     pub fn sg_routing_info_create(n_used: u32, node_ids: *const u32, out: *mut *mut sg_routing_info) -> i32;

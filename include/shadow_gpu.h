@@ -757,6 +757,68 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
                                uint64_t t0_ns, uint64_t bin_ns, uint32_t n_bins,
                                uint64_t* out_series, uint64_t* out_outside);
 
+/* ---- link queues: FIFO wait per crossing under a link rate (additive to ABI 7) --
+ * What a link trace would look like if each link served only so many bytes a
+ * second: how long every crossing waits, when it is done, how deep the queue is
+ * when it arrives, and which links cannot keep up.  Input is a link trace in the
+ * format of sg_link_trace_packets and sg_group_link_trace_packets: link_off has
+ * n_links + 1 u64 entries, enter_ns n_records u64, packet n_records u32.  Further:
+ *   weight        u32, n_weights entries, indexed by packet[i]; NULL: 1 per record,
+ *                 and packet may then be NULL too.
+ *   cost_ps       u64, n_links entries: picoseconds of service per weight unit
+ *                 (with byte weights 1 Gbit/s is 8,000 and 100 Gbit/s is 80); 0: the
+ *                 link serves in no time.
+ *   link_free_in  u64, n_links entries, or NULL (all 0): the time each link's
+ *                 server becomes free.
+ * Link L owns records [link_off[L], link_off[L + 1]).  Taking them in the order
+ * given, with `done` starting at link_free_in[L]:
+ *   s_i     = min(ceil(w_i * cost_ps[L] / 1000), 2^64 - 1)   (the product exact)
+ *   start_i = max(enter_i, done)
+ *   done    = min(start_i + s_i, 2^64 - 1)                   -> done_i
+ *   wait_i  = start_i - enter_i
+ *   ahead_i = #{ j < i in the segment : done_j > enter_i }   (the records still in
+ *             the system when i arrives)
+ * The recurrence does not require a segment to be sorted: the result is a function
+ * of the arrays as given (a trace's segments are in ascending (enter_ns, packet)
+ * order, which is a FIFO queue's arrival order).
+ * Outputs, all optional, at least one required.  Per record: out_wait_ns u64,
+ * out_done_ns u64, out_ahead u32.  Per link, n_links entries each:
+ *   out_link_free         u64: done of the link's last record, link_free_in[L] for
+ *                         an empty segment; it must not alias link_free_in
+ *   out_link_busy_ns      u64: the sum of s_i
+ *   out_link_wait_max_ns  u64
+ *   out_link_wait_sum_ns  u64, wraps
+ *   out_link_ahead_max    u32
+ * An empty segment has 0 in the last four.  n_records == 0 is legal.
+ * FIRST ORDER: a wait is not propagated to the packet's later hops; enter_ns
+ * downstream is the trace's.  CHAINING out_link_free into a later call's
+ * link_free_in equals one call over both calls' records only when every record of
+ * the later call arrives after every record of the earlier one on its link.
+ *
+ * SG_ROUTE_OUT_DEVICE applies to every array argument alike; without it all
+ * arrays are host arrays, staged.  Synchronises once.
+ *
+ * SG_ERR_INVALID_ARG, every output untouched: NULL ctx, link_off, enter_ns or
+ * cost_ps; no output; weight without packet; out_link_free == link_free_in; in
+ * host mode a bad link_off, sg_ctx_last_error_pair = (link, UINT32_MAX), the
+ * smallest such link: link_off[0] != 0 is link 0, link_off[L + 1] < link_off[L]
+ * is link L, link_off[n_links] != n_records is link n_links.
+ * Found on the device (the outputs then undefined; never a trap, and no index is
+ * ever formed from a bad value), in this order: a bad link_off in device mode, as
+ * above; packet[i] >= n_weights, SG_ERR_INVALID_ARG with the pair (link, i -
+ * link_off[link]) of the smallest such i; done_i reaching 2^64 - 1,
+ * SG_ERR_TIME_OVERFLOW with the same kind of pair, the smallest i.
+ * Timers: "link_queue" (work = records), "link_queue_ahead". */
+int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
+                      const uint64_t* link_off, uint64_t n_records,
+                      const uint64_t* enter_ns, const uint32_t* packet,
+                      const uint32_t* weight, uint32_t n_weights,
+                      const uint64_t* cost_ps, const uint64_t* link_free_in,
+                      uint64_t* out_wait_ns, uint64_t* out_done_ns, uint32_t* out_ahead,
+                      uint64_t* out_link_free, uint64_t* out_link_busy_ns,
+                      uint64_t* out_link_wait_max_ns, uint64_t* out_link_wait_sum_ns,
+                      uint32_t* out_link_ahead_max);
+
 /* ---- sharded delivery with a fixed-split exchange (no host round trip) ----
  * The same round as sg_deliver_source / sg_deliver_bucket, with every rank's
  * records for rank r in a block of `cap` slots, so the exchange is one

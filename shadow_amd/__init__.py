@@ -6,7 +6,8 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 * routing-table build (NetworkGraph::compute_shortest_paths / get_direct_paths,
   src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`, with the paths' trees
   (`graph.PathTree`) and the traffic they carried per link (`PathTree.link_load` from per-pair
-  counters, `PathTree.link_load_round` from a round's packets, `NetworkGraph.links`);
+  counters, `PathTree.link_load_round` from a round's packets, `NetworkGraph.links`), and what
+  a link rate would make each crossing wait (`link_queue`, `PathTree.link_queue_round`);
 * per-round packet delivery (Worker::send_packet, src/main/core/worker.rs:322-397)
   -> `worker.deliver_round`;
 * the packets in flight between a delivery round and their arrival (the per-host
@@ -15,11 +16,13 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 There is no CPU fallback: if libshadow_gpu.so is missing, `load()` raises.
 """
 from ._capi import LIB_PATH, ShadowGpuError, ShadowGpuUnavailable, load  # noqa: F401
-from .graph import (Context, IpAssignment, NetworkGraph, PathProperties, PathTable, PathTree,  # noqa: F401
-                    RoutingInfo, default_context, generate_routing_info, ipv4_to_u32, u32_to_ipv4)
+from .graph import (Context, IpAssignment, LinkQueueResult, NetworkGraph, PathProperties, PathTable,  # noqa: F401
+                    PathTree, RoutingInfo, cost_ps_from_bandwidth, default_context, generate_routing_info,
+                    ipv4_to_u32, link_queue, u32_to_ipv4)
 from .wire import PacketWire  # noqa: F401
 from .group import Group, GroupDelivery  # noqa: F401
 
 __all__ = ["Context", "NetworkGraph", "PathProperties", "PathTable", "PathTree", "RoutingInfo", "IpAssignment",
            "generate_routing_info", "default_context", "load", "ShadowGpuError", "ShadowGpuUnavailable",
-           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire", "Group", "GroupDelivery"]
+           "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire", "Group", "GroupDelivery", "LinkQueueResult",
+           "link_queue", "cost_ps_from_bandwidth"]

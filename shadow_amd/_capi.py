@@ -64,7 +64,7 @@ EXPORTED = [
     "sg_net_links", "sg_net_edge_links", "sg_link_load", "sg_link_load_packets",
     "sg_tree_paths", "sg_tree_paths_packets", "sg_link_trace_packets",
     "sg_group_last_error_member", "sg_group_link_load_packets", "sg_group_link_trace_packets",
-    "sg_link_series_packets", "sg_group_link_series_packets",
+    "sg_link_series_packets", "sg_group_link_series_packets", "sg_link_queue",
 ]
 
 
@@ -335,6 +335,7 @@ def load(path: str | None = None):
                                          vp, u32, u32, u64, u64, u32, vp, vp]),
         "sg_group_link_series_packets": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(sg_packets), vp, vp,
                                                vp, u32, u32, u64, u64, u32, u32, vp, vp]),
+        "sg_link_queue": (i32, [vp, u32, u32, vp, u64, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

@@ -130,6 +130,9 @@ struct sg_ctx {
   // link time series (sg_series.hip; it shares l_idx, l_flag, l_pred and p_lat): the device copy
   // of a host slot map, and the zeroed sums of a host-mode call or of a group member
   sg::DevBuf sr_slot, sr_series, sr_outside;
+  // link queues (sg_queue.hip): the device copies of a host-mode call's six inputs and eight
+  // outputs, the tile aggregates, the done times when the caller takes none, the flag words
+  sg::DevBuf q_buf[14], q_agg, q_done, q_flag;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

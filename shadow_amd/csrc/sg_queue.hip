@@ -1,0 +1,575 @@
+// sg_queue.hip -- link queues: the FIFO wait of every crossing of a link trace under a link rate.
+//
+// Input is a link trace (sg_trace.hip, sg_group_trace.hip): link L owns records [off[L], off[L + 1])
+// in arrival order.  Per record, with `done` starting at the link's free_in value (include/
+// shadow_gpu.h has the definition):
+//   s = min(ceil(w cost / 1000), MAX);  start = max(enter, done);  done = min(start + s, MAX);
+//   wait = start - enter;  ahead = #{earlier records of the segment with done > enter}.
+//
+// The recurrence is a segmented scan in the (max, saturating +) algebra: record i is the element
+// (S, M) = (s, enter (+) s), the operator (S1, M1) o (S2, M2) = (S1 (+) S2, max(M1 (+) S2, M2)) with
+// (+) saturating at MAX = 2^64 - 1; a segment's first record takes max(enter, free_in) for enter,
+// so done_i is the M of its segment's prefix.  Saturating addition of non-negative values is
+// associative and max distributes over it: any bracketing gives the serial loop's value, and
+// done_i == MAX is the overflow test.
+//
+// Launches on the context stream, one flat scan over all records whatever the segment lengths:
+//   k_queue_links   a lane per link_off entry: validates link_off (every later kernel returns at
+//                   once when it is bad: no index is formed from a bad value), zeroes the per-link
+//                   sums and gives an empty link its free_in value;
+//   k_queue_agg     a tile of Q_TILE records per workgroup, Q_PER consecutive records per lane: the
+//                   tile's aggregate (head flag, S, M).  A lane finds the link of its first record
+//                   by binary search in link_off and advances through the offsets from there;
+//   k_queue_carry   one workgroup over the tile aggregates, looping past its 1024 threads: the
+//                   `done` that enters each tile;
+//   k_queue_rescan  the tile again with that carry: wait, done, out_link_free from a segment's
+//                   last record, and the per-link busy / wait sums.  A lane sums its own run of
+//                   equal links first; lanes whose records all lie on one link are then summed
+//                   across the wave by a segmented reduction keyed by the link, and only the
+//                   first lane of a run issues the atomics: a link of 100k records gets one add
+//                   per wave, not one per record;
+//   k_queue_ahead   a lane per record: done is non-decreasing within a segment, so ahead is one
+//                   binary search over the done values of the segment's prefix; the per-link
+//                   maximum by the same wave reduction.
+// No workgroup waits on another inside a launch.  SG_LINK_QUEUE_SERIAL = 1 replaces agg, carry
+// and rescan by k_queue_serial, a lane per link looping over its segment.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "sg_internal.h"
+#include "sg_knobs.h"
+#include "sg_scan.h"
+
+namespace sg {
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr uint32_t Q_THREADS = 256;
+constexpr uint32_t Q_PER = 8;  // consecutive records per lane
+constexpr uint32_t Q_TILE = Q_THREADS * Q_PER;
+constexpr uint32_t Q_CARRY_THREADS = 1024;
+constexpr u64 Q_MAX = ~0ull;
+constexpr uint32_t Q_NO_LINK = 0xFFFFFFFFu;
+
+// flag words (all ones: nothing found; the smallest value wins)
+enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_WORDS = 3 };
+
+struct QArgs {
+  const u64* off;
+  uint32_t n_links;
+  u64 n;
+  const u64* enter;
+  const uint32_t* packet;
+  const uint32_t* weight;
+  uint32_t n_weights;
+  const u64* cost;
+  const u64* free_in;
+  u64* wait;
+  u64* done;  // the caller's, or the scratch array k_queue_ahead reads, or null
+  uint32_t* ahead;
+  u64* link_free;
+  u64* busy;
+  u64* wmax;
+  u64* wsum;
+  uint32_t* amax;
+  u64* flag;
+  // the tile aggregates; agg_m becomes the `done` entering each tile
+  u64* agg_s;
+  u64* agg_m;
+  uint32_t* agg_h;
+};
+
+__device__ __forceinline__ u64 sat_add(u64 a, u64 b) {
+  const u64 r = a + b;
+  return r < a ? Q_MAX : r;
+}
+
+// min(ceil(w cost / 1000), MAX), the product taken exactly (96 bits)
+__device__ __forceinline__ u64 service_ns(uint32_t w, u64 cost) {
+  const u64 lo = (u64)w * cost, hi = __umul64hi((u64)w, cost);
+  u64 q, r;
+  if (hi == 0ull) {
+    q = lo / 1000ull;
+    r = lo - q * 1000ull;
+  } else {
+    // hi < 2^32: long division of the limbs (hi, lo >> 32, lo & 2^32 - 1) by 1000
+    if (hi >= 1000ull) return Q_MAX;  // the quotient is 2^64 or more
+    const u64 t1 = (hi << 32) | (lo >> 32), q1 = t1 / 1000ull, r1 = t1 - q1 * 1000ull;
+    const u64 t0 = (r1 << 32) | (lo & 0xFFFFFFFFull), q0 = t0 / 1000ull;
+    r = t0 - q0 * 1000ull;
+    if (q1 >> 32) return Q_MAX;
+    q = (q1 << 32) | q0;
+  }
+  return r != 0ull && q != Q_MAX ? q + 1ull : q;
+}
+
+// The link that owns record i < n of a valid link_off: the L with off[L] <= i < off[L + 1].
+__device__ __forceinline__ uint32_t link_of(const u64* __restrict__ off, uint32_t n_links, u64 i) {
+  uint32_t lo = 1, hi = n_links;  // the first L' in [1, n_links] with off[L'] > i (off[n_links] = n > i)
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (off[mid] > i)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo - 1;
+}
+
+// A lane's place in link_off while it steps through consecutive records.
+struct QCursor {
+  uint32_t link;
+  u64 end;  // off[link + 1]
+  __device__ __forceinline__ void seek(const QArgs& a, u64 i) {
+    link = link_of(a.off, a.n_links, i);
+    end = a.off[link + 1];
+  }
+  // to record i, one past the last; true when the link changed
+  __device__ __forceinline__ bool step(const QArgs& a, u64 i) {
+    if (i < end) return false;
+    link++;  // (i == end: a later link starts here, and link + 1 <= n_links while i < n)
+    end = a.off[link + 1];
+    if (i >= end) seek(a, i);  // empty links in between
+    return true;
+  }
+};
+
+// The weight of record i; a packet index past the weights is flagged and counts 0.
+__device__ __forceinline__ uint32_t record_weight(const QArgs& a, u64 i, bool flag) {
+  if (!a.weight) return 1u;
+  const uint32_t p = a.packet[i];
+  if (p >= a.n_weights) {
+    if (flag) atomicMin(&a.flag[Q_BAD_PACKET], i);
+    return 0u;
+  }
+  return a.weight[p];
+}
+
+// ---- the scan's element
+struct QElem {
+  u64 s, m;
+  uint32_t head;
+};
+
+__device__ __forceinline__ QElem scan_shfl_up(QElem x, uint32_t d) {
+  return QElem{__shfl_up(x.s, d, 64), __shfl_up(x.m, d, 64), __shfl_up(x.head, d, 64)};
+}
+
+struct QOp {
+  __device__ __forceinline__ QElem operator()(const QElem& a, const QElem& b) const {
+    if (b.head) return b;
+    return QElem{sat_add(a.s, b.s), max(sat_add(a.m, b.s), b.m), a.head};
+  }
+};
+
+// (every element has m >= s, so this is the identity on both sides)
+__device__ __forceinline__ QElem q_identity() { return QElem{0ull, 0ull, 0u}; }
+
+// A lane's Q_PER records: service, enter time, link, and which are a segment's first and last.
+struct QLane {
+  u64 s[Q_PER], e[Q_PER];
+  uint32_t link[Q_PER];
+  uint32_t head, last, count;  // bit masks; the records the lane has
+};
+
+template <bool FLAG>
+__device__ __forceinline__ QElem lane_load(const QArgs& a, u64 base, QLane& r) {
+  QElem acc = q_identity();
+  r.head = r.last = r.count = 0u;
+  if (base >= a.n) return acc;
+  QCursor c;
+  c.seek(a, base);
+  u64 cost = a.cost[c.link];
+  bool head = base == a.off[c.link];
+#pragma unroll
+  for (uint32_t k = 0; k < Q_PER; k++) {
+    const u64 i = base + k;
+    r.s[k] = r.e[k] = 0ull;
+    r.link[k] = Q_NO_LINK;
+    if (i >= a.n) continue;
+    if (k > 0 && c.step(a, i)) {
+      head = true;
+      cost = a.cost[c.link];
+    }
+    const u64 s = service_ns(record_weight(a, i, FLAG), cost), e = a.enter[i];
+    r.s[k] = s;
+    r.e[k] = e;
+    r.link[k] = c.link;
+    r.count = k + 1;
+    if (head) {
+      r.head |= 1u << k;
+      const u64 x0 = a.free_in ? a.free_in[c.link] : 0ull;
+      acc = QElem{s, sat_add(max(e, x0), s), 1u};
+    } else {
+      acc = QElem{sat_add(acc.s, s), sat_add(max(acc.m, e), s), acc.head};
+    }
+    if (i + 1 == c.end) r.last |= 1u << k;
+    head = false;
+  }
+  return acc;
+}
+
+// ---- link_off's check, the per-link sums' zeroes, the empty links
+__global__ void __launch_bounds__(Q_THREADS) k_queue_links(const QArgs a) {
+  const u64 q = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (q > a.n_links) return;
+  const uint32_t lk = (uint32_t)q;
+  const u64 o = a.off[lk];
+  if (lk == 0 && o != 0ull) atomicMin(&a.flag[Q_BAD_OFF], 0ull);
+  if (lk == a.n_links) {
+    if (o != a.n) atomicMin(&a.flag[Q_BAD_OFF], (u64)lk);
+    return;
+  }
+  const u64 o1 = a.off[lk + 1];
+  if (o1 < o) atomicMin(&a.flag[Q_BAD_OFF], (u64)lk);
+  if (a.busy) a.busy[lk] = 0ull;
+  if (a.wmax) a.wmax[lk] = 0ull;
+  if (a.wsum) a.wsum[lk] = 0ull;
+  if (a.amax) a.amax[lk] = 0u;
+  if (a.link_free && o1 == o) a.link_free[lk] = a.free_in ? a.free_in[lk] : 0ull;
+}
+
+// ---- 1. the tile aggregates
+__global__ void __launch_bounds__(Q_THREADS) k_queue_agg(const QArgs a) {
+  __shared__ QElem s_wave[16];
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  QLane r;
+  const QElem x = lane_load<true>(a, (u64)blockIdx.x * Q_TILE + (u64)threadIdx.x * Q_PER, r);
+  QElem total;
+  block_exclusive_op(x, q_identity(), s_wave, &total, QOp());
+  if (threadIdx.x == 0) {
+    a.agg_s[blockIdx.x] = total.s;
+    a.agg_m[blockIdx.x] = total.m;
+    a.agg_h[blockIdx.x] = total.head;
+  }
+}
+
+// ---- 2. one workgroup: agg_m[t] = the M of everything before tile t (the `done` entering it)
+__global__ void __launch_bounds__(Q_CARRY_THREADS) k_queue_carry(const QArgs a, uint32_t n_tiles) {
+  __shared__ QElem s_wave[16];
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const QOp op;
+  QElem carry = q_identity();
+  for (uint32_t base = 0; base < n_tiles; base += Q_CARRY_THREADS) {
+    const uint32_t b = base + threadIdx.x;
+    const QElem x = b < n_tiles ? QElem{a.agg_s[b], a.agg_m[b], a.agg_h[b]} : q_identity();
+    QElem total;
+    const QElem ex = block_exclusive_op(x, q_identity(), s_wave, &total, op);
+    if (b < n_tiles) a.agg_m[b] = op(carry, ex).m;
+    carry = op(carry, total);
+  }
+}
+
+// The segmented reduction of a wave's (key, busy, wait max, wait sum): equal keys sit in
+// consecutive lanes (links rise with the record index); afterwards the first lane of a run of
+// equal keys holds the run's sums.  Every lane calls.
+struct QSums {
+  u64 busy, wmax, wsum;
+};
+
+__device__ __forceinline__ bool wave_run_sums(uint32_t key, QSums& x) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t k2 = __shfl_down(key, d, 64);
+    const u64 b = __shfl_down(x.busy, d, 64), m = __shfl_down(x.wmax, d, 64), s = __shfl_down(x.wsum, d, 64);
+    if (lane + d < 64 && k2 == key) {
+      x.busy += b;
+      x.wmax = max(x.wmax, m);
+      x.wsum += s;
+    }
+  }
+  const uint32_t below = __shfl_up(key, 1, 64);
+  return key != Q_NO_LINK && (lane == 0 || below != key);
+}
+
+__device__ __forceinline__ void link_sums_add(const QArgs& a, uint32_t link, const QSums& x) {
+  if (a.busy && x.busy) atomicAdd(&a.busy[link], x.busy);
+  if (a.wmax && x.wmax) atomicMax(&a.wmax[link], x.wmax);
+  if (a.wsum && x.wsum) atomicAdd(&a.wsum[link], x.wsum);
+}
+
+// ---- 3. the tile again, with its carry
+__global__ void __launch_bounds__(Q_THREADS) k_queue_rescan(const QArgs a) {
+  __shared__ QElem s_wave[16];
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const u64 base = (u64)blockIdx.x * Q_TILE + (u64)threadIdx.x * Q_PER;
+  QLane r;
+  const QElem x = lane_load<false>(a, base, r);
+  QElem total;
+  const QElem ex = block_exclusive_op(x, q_identity(), s_wave, &total, QOp());
+  // (ex.head: a segment starts in the tile below this lane, the carry does not reach it)
+  u64 done = ex.head ? ex.m : max(sat_add(a.agg_m[blockIdx.x], ex.s), ex.m);
+  const bool sums = a.busy || a.wmax || a.wsum;
+  QSums run = {0ull, 0ull, 0ull};
+  uint32_t run_link = Q_NO_LINK;
+#pragma unroll
+  for (uint32_t k = 0; k < Q_PER; k++) {
+    if (k >= r.count) continue;
+    const uint32_t lk = r.link[k];
+    if ((r.head >> k) & 1u) done = a.free_in ? a.free_in[lk] : 0ull;
+    const u64 start = max(r.e[k], done), wait = start - r.e[k];
+    done = sat_add(start, r.s[k]);
+    if (done == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], base + k);
+    if (a.wait) a.wait[base + k] = wait;
+    if (a.done) a.done[base + k] = done;
+    if (a.link_free && ((r.last >> k) & 1u)) a.link_free[lk] = done;
+    if (sums) {
+      if (lk != run_link) {
+        if (run_link != Q_NO_LINK) link_sums_add(a, run_link, run);
+        run_link = lk;
+        run = QSums{0ull, 0ull, 0ull};
+      }
+      run.busy += r.s[k];
+      run.wmax = max(run.wmax, wait);
+      run.wsum += wait;
+    }
+  }
+  if (sums) {  // (the same for every lane of the launch)
+    // a lane whose records lie on one link joins the wave's reduction; any other adds its last run itself
+    uint32_t key = Q_NO_LINK;
+    if (r.count && r.link[0] == run_link) {
+      key = run_link;
+    } else if (run_link != Q_NO_LINK) {
+      link_sums_add(a, run_link, run);
+    }
+    if (wave_run_sums(key, run)) link_sums_add(a, key, run);
+  }
+}
+
+// ---- the lane-per-link form
+__global__ void __launch_bounds__(Q_THREADS) k_queue_serial(const QArgs a) {
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const u64 stride = (u64)gridDim.x * Q_THREADS;
+  for (u64 q = (u64)blockIdx.x * Q_THREADS + threadIdx.x; q < a.n_links; q += stride) {
+    const uint32_t lk = (uint32_t)q;
+    const u64 i0 = a.off[lk], i1 = a.off[lk + 1];
+    if (i0 == i1) continue;  // (k_queue_links wrote an empty link's outputs)
+    const u64 cost = a.cost[lk];
+    u64 done = a.free_in ? a.free_in[lk] : 0ull;
+    QSums run = {0ull, 0ull, 0ull};
+    for (u64 i = i0; i < i1; i++) {
+      const u64 s = service_ns(record_weight(a, i, true), cost), e = a.enter[i];
+      const u64 start = max(e, done), wait = start - e;
+      done = sat_add(start, s);
+      if (done == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], i);
+      if (a.wait) a.wait[i] = wait;
+      if (a.done) a.done[i] = done;
+      run.busy += s;
+      run.wmax = max(run.wmax, wait);
+      run.wsum += wait;
+    }
+    if (a.link_free) a.link_free[lk] = done;
+    if (a.busy) a.busy[lk] = run.busy;
+    if (a.wmax) a.wmax[lk] = run.wmax;
+    if (a.wsum) a.wsum[lk] = run.wsum;
+  }
+}
+
+// ---- ahead: the records of the segment's prefix still in the system when record i arrives
+__global__ void __launch_bounds__(Q_THREADS) k_queue_ahead(const QArgs a) {
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  uint32_t key = Q_NO_LINK, ahead = 0u;
+  if (i < a.n) {
+    key = link_of(a.off, a.n_links, i);
+    const u64 e = a.enter[i];
+    u64 lo = a.off[key], hi = i;  // the first j of the prefix with done[j] > e
+    while (lo < hi) {
+      const u64 mid = lo + (hi - lo) / 2;
+      if (a.done[mid] > e)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    ahead = (uint32_t)min(i - lo, (u64)0xFFFFFFFFull);
+    if (a.ahead) a.ahead[i] = ahead;
+  }
+  if (!a.amax) return;  // (the same for every lane)
+  uint32_t m = ahead;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t k2 = __shfl_down(key, d, 64), m2 = __shfl_down(m, d, 64);
+    if (lane + d < 64 && k2 == key) m = max(m, m2);
+  }
+  const uint32_t below = __shfl_up(key, 1, 64);
+  if (key != Q_NO_LINK && (lane == 0 || below != key) && m) atomicMax(&a.amax[key], m);
+}
+
+// the first bad link of a host link_off; all ones when it is good
+u64 bad_link_off(const uint64_t* off, uint32_t n_links, uint64_t n) {
+  if (off[0] != 0) return 0;
+  for (uint32_t k = 0; k < n_links; k++)
+    if (off[k + 1] < off[k]) return k;
+  return off[n_links] != n ? (u64)n_links : Q_MAX;
+}
+
+[[noreturn]] void throw_bad_off(u64 link) {
+  throw Error(SG_ERR_INVALID_ARG,
+              "link_off is not an offset array of the records at link " + std::to_string(link) +
+                  " (it starts at 0, never falls and ends at n_records)",
+              (uint32_t)link, 0xFFFFFFFFu);
+}
+
+struct QueueCall {
+  sg_ctx* ctx;
+  uint32_t flags, n_links;
+  const uint64_t* link_off;
+  uint64_t n;
+  const uint64_t* enter;
+  const uint32_t* packet;
+  const uint32_t* weight;
+  uint32_t n_weights;
+  const uint64_t* cost;
+  const uint64_t* free_in;
+  uint64_t* wait;
+  uint64_t* done;
+  uint32_t* ahead;
+  uint64_t* link_free;
+  uint64_t* busy;
+  uint64_t* wmax;
+  uint64_t* wsum;
+  uint32_t* amax;
+};
+
+void queue_run(const QueueCall& c) {
+  sg_ctx* ctx = c.ctx;
+  if (!c.link_off || !c.enter || !c.cost) throw Error(SG_ERR_INVALID_ARG, "null link_off, enter_ns or cost_ps");
+  if (!c.wait && !c.done && !c.ahead && !c.link_free && !c.busy && !c.wmax && !c.wsum && !c.amax)
+    throw Error(SG_ERR_INVALID_ARG, "no output");
+  if (c.weight && !c.packet) throw Error(SG_ERR_INVALID_ARG, "weight without packet");
+  if (c.link_free && c.link_free == c.free_in) throw Error(SG_ERR_INVALID_ARG, "out_link_free is link_free_in");
+  const bool dev = (c.flags & SG_ROUTE_OUT_DEVICE) != 0;
+  const uint32_t nl = c.n_links;
+  const uint64_t n = c.n;
+  if (!dev) {
+    const u64 bad = bad_link_off(c.link_off, nl, n);
+    if (bad != Q_MAX) throw_bad_off(bad);
+  }
+  const uint64_t n_tiles64 = (n + Q_TILE - 1) / Q_TILE;
+  if (n_tiles64 > 0x7FFFFFFFull) throw Error(SG_ERR_CAPACITY, "more records than one call scans");
+  const uint32_t n_tiles = (uint32_t)n_tiles64;
+  hipStream_t st = ctx->stream;
+
+  QArgs a = {};
+  a.n_links = nl;
+  a.n = n;
+  a.n_weights = c.n_weights;
+  // host arrays in: device copies; host outputs: device arrays copied back at the end
+  struct Back {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  std::vector<Back> back;
+  int slot = 0;
+  auto in = [&](const void* p, size_t bytes) -> const void* {
+    sg::DevBuf& b = ctx->q_buf[slot++];
+    if (!p || dev) return p;
+    char* d = b.get<char>(bytes);
+    if (bytes) SG_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, st));
+    return d;
+  };
+  auto out = [&](void* p, size_t bytes) -> void* {
+    sg::DevBuf& b = ctx->q_buf[slot++];
+    if (!p || dev) return p;
+    char* d = b.get<char>(bytes);
+    back.push_back(Back{p, d, bytes});
+    return d;
+  };
+  a.off = (const u64*)in(c.link_off, ((size_t)nl + 1) * 8);
+  a.enter = (const u64*)in(c.enter, n * 8);
+  a.packet = (const uint32_t*)in(c.packet, n * 4);
+  a.weight = (const uint32_t*)in(c.weight, (size_t)c.n_weights * 4);
+  a.cost = (const u64*)in(c.cost, (size_t)nl * 8);
+  a.free_in = (const u64*)in(c.free_in, (size_t)nl * 8);
+  a.wait = (u64*)out(c.wait, n * 8);
+  a.done = (u64*)out(c.done, n * 8);
+  a.ahead = (uint32_t*)out(c.ahead, n * 4);
+  a.link_free = (u64*)out(c.link_free, (size_t)nl * 8);
+  a.busy = (u64*)out(c.busy, (size_t)nl * 8);
+  a.wmax = (u64*)out(c.wmax, (size_t)nl * 8);
+  a.wsum = (u64*)out(c.wsum, (size_t)nl * 8);
+  a.amax = (uint32_t*)out(c.amax, (size_t)nl * 4);
+  const bool want_ahead = (a.ahead || a.amax);
+  if (want_ahead && !a.done) a.done = ctx->q_done.get<u64>(n);
+  a.flag = ctx->q_flag.get<u64>(Q_WORDS);
+  SG_HIP(hipMemsetAsync(a.flag, 0xff, Q_WORDS * 8, st));
+
+  const bool serial = knob_int("SG_LINK_QUEUE_SERIAL", 0) != 0;
+  hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), dim3(Q_THREADS), 0, st, a);
+  SG_CHECK_LAUNCH();
+  if (n) {
+    TimedLaunch tl(ctx, "link_queue", (double)n);
+    if (serial) {
+      hipLaunchKernelGGL(k_queue_serial, dim3(grid_for(nl, Q_THREADS, 16u * (unsigned)ctx->n_cu)), dim3(Q_THREADS), 0,
+                         st, a);
+      SG_CHECK_LAUNCH();
+    } else {
+      u64* agg = ctx->q_agg.get<u64>(3 * (size_t)n_tiles);
+      a.agg_s = agg;
+      a.agg_m = agg + n_tiles;
+      a.agg_h = (uint32_t*)(agg + 2 * (size_t)n_tiles);
+      hipLaunchKernelGGL(k_queue_agg, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
+      SG_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_queue_carry, dim3(1), dim3(Q_CARRY_THREADS), 0, st, a, n_tiles);
+      SG_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_queue_rescan, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
+      SG_CHECK_LAUNCH();
+    }
+  }
+  if (n && want_ahead) {
+    TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+    hipLaunchKernelGGL(k_queue_ahead, dim3(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), dim3(Q_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+  }
+  // read_timer("link_queue_serial") = (0, 1 when the last call took the lane-per-link form, its records)
+  timer_set_counter(ctx, "link_queue_serial", (double)n, serial ? 1u : 0u);
+  u64 h[Q_WORDS];
+  copy_to_host(ctx, h, a.flag, sizeof(h));
+  if (h[Q_BAD_OFF] != Q_MAX) throw_bad_off(h[Q_BAD_OFF]);
+  if (h[Q_BAD_PACKET] != Q_MAX || h[Q_OVERFLOW] != Q_MAX) {
+    const bool pk = h[Q_BAD_PACKET] != Q_MAX;
+    const u64 i = pk ? h[Q_BAD_PACKET] : h[Q_OVERFLOW];
+    // the record's link: link_off is valid, the host's or a copy of the device's
+    std::vector<uint64_t> hoff;
+    const uint64_t* off = c.link_off;
+    if (dev) {
+      hoff.resize((size_t)nl + 1);
+      SG_HIP(hipMemcpy(hoff.data(), c.link_off, hoff.size() * 8, hipMemcpyDeviceToHost));
+      off = hoff.data();
+    }
+    const uint32_t lk = (uint32_t)(std::upper_bound(off + 1, off + nl + 1, (uint64_t)i) - off - 1);
+    const uint32_t at = (uint32_t)std::min<uint64_t>(i - off[lk], 0xFFFFFFFFull);
+    if (pk)
+      throw Error(SG_ERR_INVALID_ARG,
+                  "packet[" + std::to_string(i) + "] is not below n_weights (link " + std::to_string(lk) + ")", lk, at);
+    throw Error(SG_ERR_TIME_OVERFLOW,
+                "record " + std::to_string(i) + " of link " + std::to_string(lk) + " is served past 2^64 - 1 ns", lk, at);
+  }
+  for (const Back& b : back)
+    if (b.bytes) SG_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+  if (!back.empty()) SG_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+}  // namespace sg
+
+extern "C" {
+
+int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links, const uint64_t* link_off, uint64_t n_records,
+                      const uint64_t* enter_ns, const uint32_t* packet, const uint32_t* weight, uint32_t n_weights,
+                      const uint64_t* cost_ps, const uint64_t* link_free_in, uint64_t* out_wait_ns,
+                      uint64_t* out_done_ns, uint32_t* out_ahead, uint64_t* out_link_free, uint64_t* out_link_busy_ns,
+                      uint64_t* out_link_wait_max_ns, uint64_t* out_link_wait_sum_ns, uint32_t* out_link_ahead_max) {
+  return sg::guarded(ctx, [&] {
+    sg::queue_run(sg::QueueCall{ctx, flags, n_links, link_off, n_records, enter_ns, packet, weight, n_weights, cost_ps,
+                                link_free_in, out_wait_ns, out_done_ns, out_ahead, out_link_free, out_link_busy_ns,
+                                out_link_wait_max_ns, out_link_wait_sum_ns, out_link_ahead_max});
+  });
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "sg_internal.h"
+#include "sg_scan.h"
 
 namespace sg {
 namespace {
@@ -15,34 +16,7 @@ constexpr uint32_t SCAN_PER = 8;  // counts per thread
 constexpr uint32_t SCAN_TILE = SCAN_THREADS * SCAN_PER;
 constexpr uint32_t SCAN_SUMS_THREADS = 1024;
 
-__device__ __forceinline__ unsigned long long wave_inclusive(unsigned long long x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const unsigned long long y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// The exclusive prefix of x over the workgroup's threads (blockDim.x a multiple of 64, at most
-// 1024); *total = the sum.  s_wave: 16 words of LDS; every thread calls.
-__device__ __forceinline__ unsigned long long block_exclusive(unsigned long long x, unsigned long long* s_wave,
-                                                              unsigned long long* total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const unsigned long long inc = wave_inclusive(x);
-  __syncthreads();  // (the last call's reads of s_wave)
-  if (lane == 63) s_wave[w] = inc;
-  __syncthreads();
-  unsigned long long before = 0ull, all = 0ull;
-  for (uint32_t k = 0; k < nw; k++) {
-    const unsigned long long t = s_wave[k];
-    if (k < w) before += t;
-    all += t;
-  }
-  *total = all;
-  return before + inc - x;
-}
+// (wave_inclusive, block_exclusive: sg_scan.h)
 
 __global__ void __launch_bounds__(SCAN_THREADS) k_scan_block_sums(const uint32_t* cnt, uint32_t n,
                                                                   unsigned long long* sums) {

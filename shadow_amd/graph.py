@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -196,6 +196,99 @@ def series_slots(slots, n_links: int) -> Tuple[Optional[np.ndarray], int]:
     m = np.full(n_links, 0xFFFFFFFF, np.uint32)
     m[idx] = np.arange(len(idx), dtype=np.uint32)
     return m, len(idx)
+
+
+class LinkQueueResult(NamedTuple):
+    """What sg_link_queue gives: per record wait_ns, done_ns (u64) and ahead (u32, the records of
+    the link still in the system on arrival); per link link_free (u64, when its server is free
+    after the last record), link_busy_ns (the summed service), link_wait_max_ns, link_wait_sum_ns
+    (u64) and link_ahead_max (u32)."""
+    wait_ns: np.ndarray
+    done_ns: np.ndarray
+    ahead: np.ndarray
+    link_free: np.ndarray
+    link_busy_ns: np.ndarray
+    link_wait_max_ns: np.ndarray
+    link_wait_sum_ns: np.ndarray
+    link_ahead_max: np.ndarray
+
+
+def cost_ps_from_bandwidth(bits_per_second, unit_bytes: int = 1):
+    """sg_link_queue's cost_ps of a link rate: the picoseconds one weight unit of unit_bytes bytes
+    takes at bits_per_second, rounded up (1e9 gives 8,000, 100e9 gives 80).  A sequence of rates
+    gives a u64 array, one cost per link."""
+    def one(bps) -> int:
+        bps = int(bps)
+        if bps <= 0:
+            raise ValueError("bits_per_second: a positive rate")
+        return -((-8 * int(unit_bytes) * 10**12) // bps)
+    if np.ndim(bits_per_second) == 0:
+        return one(bits_per_second)
+    return np.array([one(b) for b in np.asarray(bits_per_second).ravel()], dtype=np.uint64)
+
+
+def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
+    """One u64 per link from a scalar or an array of n_links entries."""
+    if np.ndim(x) == 0:
+        return np.full(n_links, int(x), np.uint64)
+    a = np.ascontiguousarray(x, dtype=np.uint64)
+    if a.shape != (n_links,):
+        raise ValueError(f"{what}: one value, or {n_links} entries, one per link")
+    return a
+
+
+def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None) -> LinkQueueResult:
+    """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
+    records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
+    arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
+    cost_ps: picoseconds of service per weight unit, one value or one per link
+    (cost_ps_from_bandwidth); free_ns: when each link's server is free (None: 0).  A record starts
+    at max(enter, the link's previous done), takes ceil(weight cost_ps / 1000) ns and waits start -
+    enter.  First order: a wait is not carried to the packet's later hops (sg_link_queue)."""
+    off = np.ascontiguousarray(link_off, dtype=np.uint64)
+    n_links = len(off) - 1
+    if n_links < 0:
+        raise ValueError("link_off: n_links + 1 entries")
+    enter = np.ascontiguousarray(enter_ns, dtype=np.uint64)
+    n = len(enter)
+    pkt = None if packet is None else np.ascontiguousarray(packet, dtype=np.uint32)
+    if pkt is not None and len(pkt) != n:
+        raise ValueError(f"packet: {n} entries, one per record")
+    wt = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint32)
+    cost = _per_link_u64(cost_ps, n_links, "cost_ps")
+    free = None if free_ns is None else _per_link_u64(free_ns, n_links, "free_ns")
+    res = LinkQueueResult(np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32),
+                          np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64),
+                          np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint32))
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(ctx.handle, load().sg_link_queue(
+        ctx.handle, 0, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)), ptr(pkt), ptr(wt), 0 if wt is None else len(wt), ptr(cost),
+        ptr(free), *[ptr(a) for a in res]))
+    return res
+
+
+def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
+                        free_ns) -> LinkQueueResult:
+    """sg_link_queue on a device trace (torch tensors on `dev`: off, enter, packet; weight or
+    None), every output taken and copied to the host."""
+    import torch
+
+    up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)  # noqa: E731
+    cost = up(_per_link_u64(cost_ps, n_links, "cost_ps"))
+    free = None if free_ns is None else up(_per_link_u64(free_ns, n_links, "free_ns"))
+    rec = lambda dt: torch.zeros(max(n_records, 1), dtype=dt, device=dev)  # noqa: E731
+    lnk = lambda dt: torch.zeros(max(n_links, 1), dtype=dt, device=dev)  # noqa: E731
+    outs = [rec(torch.int64), rec(torch.int64), rec(torch.int32), lnk(torch.int64), lnk(torch.int64), lnk(torch.int64),
+            lnk(torch.int64), lnk(torch.int32)]
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    torch.cuda.synchronize(dev)
+    check(ctx.handle, load().sg_link_queue(
+        ctx.handle, _capi.SG_ROUTE_OUT_DEVICE, n_links, ptr(off), n_records, ptr(enter),
+        None if weight is None else ptr(packet), ptr(weight), 0 if weight is None else weight.numel(), ptr(cost),
+        ptr(free), *[ptr(t) for t in outs]))
+    lens = [n_records] * 3 + [n_links] * 5
+    dts = [np.uint64, np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32]
+    return LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
 
 
 class PathTree:
@@ -499,6 +592,75 @@ class PathTree:
             None if slot_map is None else slot_map.ctypes.data, n_slots, 0 if at == "enter" else 1, int(t0_ns),
             int(bin_ns), int(n_bins), series.ctypes.data, outside.ctypes.data))
         return series, outside
+
+    def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None):
+        """The link trace of one round's batch and the FIFO queue of every link under a link rate,
+        (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
+        gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
+        between the two calls (sg_link_trace_packets, then sg_link_queue).  weight as in
+        link_load_round: None (every crossing weighs 1), "payload" or a u32 array per packet;
+        cost_ps and free_ns as in shadow_amd.link_queue; hosts, packets, status and watch as in
+        link_trace_round.  First order: a crossing's wait is not added to the packet's later hops."""
+        import torch
+
+        npk = len(packets)
+        dev = packets.src_host.device
+
+        def to_dev(x, np_dtype, t_dtype, what):
+            if isinstance(x, torch.Tensor):
+                x = x.to(device=dev).contiguous()
+                if x.element_size() != np.dtype(np_dtype).itemsize or x.is_floating_point():
+                    raise ValueError(f"{what}: a {np.dtype(np_dtype).name} array")
+                x = x.view(t_dtype)
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).view(
+                    np.int32 if t_dtype == torch.int32 else np.uint8)).to(dev)
+            if x.numel() < npk:
+                raise ValueError(f"{what}: {npk} entries, one per packet")
+            return x
+
+        if status is not None:
+            status = to_dev(getattr(status, "status", status), np.uint8, torch.uint8, "status")
+        if isinstance(weight, str):
+            if weight != "payload":
+                raise ValueError('weight: None, "payload" or an array')
+            weight = packets.payload_len
+        if weight is not None:
+            weight = to_dev(weight, np.uint32, torch.int32, "weight")
+        g, n = self._graph, len(self.nodes)
+        n_links = len(g.links()[0])
+        if watch is not None:
+            w = np.asarray(watch)
+            if w.dtype == np.bool_ or (w.dtype == np.uint8 and w.shape == (n_links,)):
+                if w.shape != (n_links,):
+                    raise ValueError(f"watch: a mask of {n_links} entries, one per link")
+                mask = w.astype(np.uint8)
+            else:
+                idx = w.astype(np.int64).ravel()
+                if len(idx) and (idx.min() < 0 or idx.max() >= n_links):
+                    raise ValueError(f"watch: link numbers below {n_links}")
+                mask = np.zeros(n_links, np.uint8)
+                mask[idx] = 1
+            watch = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
+        pred = torch.from_numpy(np.ascontiguousarray(self.pred, dtype=np.uint32).view(np.int32)).to(dev)
+        tlat = torch.from_numpy(np.ascontiguousarray(self.latency_ns, dtype=np.uint64).view(np.int64)).to(dev)
+        off = torch.zeros(n_links + 1, dtype=torch.int64, device=dev)
+        cap = 8 * npk + 64
+        while True:  # a first call at a guessed capacity, a second at the total the first reported
+            pkt, hop = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(2))
+            enter, leave = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(2))
+            torch.cuda.synchronize(dev)
+            rc, t = g.link_trace_packets_device(
+                hosts, self.nodes, 0, self.n_sources, pred.data_ptr(), tlat.data_ptr(), packets,
+                0 if status is None else status.data_ptr(), 0 if watch is None else watch.data_ptr(), off.data_ptr(),
+                pkt.data_ptr(), hop.data_ptr(), enter.data_ptr(), leave.data_ptr(), cap)
+            if rc != _capi.SG_ERR_CAPACITY or t <= cap:
+                break
+            cap = t
+        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns)
+        return (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32),
+                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
+                leave[:t].cpu().numpy().view(np.uint64), queue)
 
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
@@ -869,6 +1031,25 @@ class NetworkGraph:
             C.c_void_p(status_ptr or None), C.c_void_p(weight_ptr or None), C.c_void_p(slot_ptr or None), int(n_slots),
             int(at), int(t0_ns), int(bin_ns), int(n_bins), C.c_void_p(series_ptr or None),
             C.c_void_p(outside_ptr or None)))
+
+    def link_queue_device(self, link_off_ptr: int, n_records: int, enter_ptr: int, packet_ptr: int, weight_ptr: int,
+                          n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
+                          ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
+                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0) -> None:
+        """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
+        device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
+        packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
+        u32, n_weights entries indexed by packet; 0: every record weighs 1, packet may be 0 too);
+        cost (device u64 per link, picoseconds per weight unit); free_in (device u64 per link, 0:
+        all zero).  Outputs, any of them 0 but not all: per record wait u64, done u64, ahead u32;
+        per link link_free u64 (not free_in's array), busy u64, wait_max u64, wait_sum u64,
+        ahead_max u32 (sg_link_queue)."""
+        vp = lambda x: C.c_void_p(x or None)  # noqa: E731
+        check(self.ctx.handle, load().sg_link_queue(
+            self.ctx.handle, _capi.SG_ROUTE_OUT_DEVICE, len(self.links()[0]), vp(link_off_ptr), int(n_records),
+            vp(enter_ptr), vp(packet_ptr), vp(weight_ptr), int(n_weights), vp(cost_ptr), vp(free_in_ptr), vp(wait_ptr),
+            vp(done_ptr), vp(ahead_ptr), vp(link_free_ptr), vp(busy_ptr), vp(wait_max_ptr), vp(wait_sum_ptr),
+            vp(ahead_max_ptr)))
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

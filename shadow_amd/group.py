@@ -247,6 +247,16 @@ class Group:
         index in the members' batches concatenated in member order, member the batch it came from.
         rows needs the latency rows; watch as in PathTree.link_trace_round.  A first call at a
         guessed capacity, a second at the total the first reported when that was too small."""
+        return self._trace_to_host(*self._link_trace_tensors(graphs, hosts, rows, packets, status, watch, root))
+
+    @staticmethod
+    def _trace_to_host(off, pkt, mem, hop, enter, leave, t):
+        return (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32), mem[:t].cpu().numpy(),
+                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
+                leave[:t].cpu().numpy().view(np.uint64))
+
+    def _link_trace_tensors(self, graphs, hosts, rows, packets, status, watch, root):
+        """link_trace_round's arrays as they lie on root's device, and the record total."""
         import torch
 
         a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, True)
@@ -283,10 +293,44 @@ class Group:
             cap = total.value
         self._check(rc)
         del keep
-        t = total.value
-        return (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32), mem[:t].cpu().numpy(),
-                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
-                leave[:t].cpu().numpy().view(np.uint64))
+        return off, pkt, mem, hop, enter, leave, total.value
+
+    def link_queue_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, cost_ps, watch=None,
+                         free_ns=None, root: int = 0):
+        """The link trace of one sharded round and the FIFO queue of every link under a link rate,
+        (link_off, packet, member, hop, enter_ns, exit_ns, queue): the first six as
+        link_trace_round gives them, queue a graph.LinkQueueResult over the same records
+        (PathTree.link_queue_round for a group).  The merged trace stays on member `root`'s device,
+        where sg_link_queue runs on root's context with the members' weights concatenated in
+        member order, as the trace's packet numbers are.  weight: None, "payload" or one u32
+        array per member (as in link_load_round); cost_ps, free_ns as in shadow_amd.link_queue."""
+        import torch
+
+        from .graph import _link_queue_tensors
+
+        tr = self._link_trace_tensors(graphs, hosts, rows, packets, status, watch, root)
+        off, pkt, _, _, enter, _, t = tr
+        dev = off.device
+        wt = None
+        if weight is not None:
+            if isinstance(weight, str):
+                if weight != "payload":
+                    raise ValueError('weight: None, "payload" or one array per member')
+                weight = [p.payload_len for p in packets]
+            if len(weight) != len(packets):
+                raise ValueError(f"weight: {len(weight)} entries for {len(packets)} members")
+            parts = []
+            for m, w in enumerate(weight):
+                if w is None:
+                    w = torch.ones(len(packets[m]), dtype=torch.int32)
+                elif not isinstance(w, torch.Tensor):
+                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
+                if w.element_size() != 4 or w.numel() < len(packets[m]):
+                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
+                parts.append(w.reshape(-1)[:len(packets[m])].view(torch.int32).to(dev))
+            wt = torch.cat(parts).contiguous() if parts else None
+        queue = _link_queue_tensors(self.contexts[root], dev, off.numel() - 1, off, t, enter, pkt, wt, cost_ps, free_ns)
+        return self._trace_to_host(*tr) + (queue,)
 
     def link_series_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, t0_ns: int, bin_ns: int,
                           n_bins: int, slots=None, at: str = "enter", out=None, root: int = 0):

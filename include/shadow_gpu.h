@@ -70,7 +70,12 @@ void sg_ctx_destroy(sg_ctx* ctx);
  * stream, a blocking stream (ordered with work on the legacy default stream, which is
  * torch's default stream).  Every entry point launches on this stream and reads
  * device inputs in stream order: inputs written on some other non-blocking stream
- * must be complete (or waited for) before the call. */
+ * must be complete (or waited for) before the call.
+ * tests/test_stream_gpu.py holds every single-context entry point to this on a
+ * caller's non-blocking stream: behind a delay kernel on that stream the inputs are
+ * overwritten with a second valid set and the outputs with a poison byte, then the
+ * call runs and its results must be the second set's, bit for bit; the calls marked
+ * "does not synchronise" below must return while the delay still runs. */
 int32_t sg_ctx_set_stream(sg_ctx* ctx, void* hip_stream);
 void* sg_ctx_stream(const sg_ctx* ctx);
 int32_t sg_ctx_synchronize(sg_ctx* ctx);
@@ -470,7 +475,9 @@ typedef struct sg_round_stats {
 } sg_round_stats;
 
 /* Run one round.  Updates the hosts' RNG streams and event counters on the
- * device.  `stats` (host) may be NULL for a fully asynchronous call.
+ * device.  `stats` (host) may be NULL.  The call synchronises once either way: it
+ * reads the round's error flags and whether a destination overfilled its region
+ * (then it sorts again and synchronises a second time).
  * A batch that is not grouped by ascending source host (SG_ERR_UNSORTED), names
  * a host out of range, or comes from a host whose route row is outside the
  * table shard (SG_ERR_INVALID_ARG) is rejected whole: no host's RNG stream or

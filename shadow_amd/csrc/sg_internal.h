@@ -478,6 +478,11 @@ struct SsspChainDesc {
 
 // One launch of the LDS search on a net (the graph arrays come from it).
 constexpr int SSSP_DIAG_WORDS = 16;  // SG_SSSP_DIAG: u64 words per row (sg_sssp.hip writes, print_sssp_diag reads)
+// SG_SSSP_DIAG, counting build: a launch's pops by class of S = ceil(arcs / 64): 0, 1, 2, 3-4, 5-8, > 8;
+// (pops, arcs, step cycles) per class, then the pops that took the lane path and the pops every wave
+// counted (u64 words)
+constexpr int SSSP_POP_CLASSES = 6;
+constexpr int SSSP_POP_WORDS = 3 * SSSP_POP_CLASSES + 2;
 struct SsspLdsLaunch {
   // the row block: rows [row_begin, row_end) of the table (out_* device, row-major from
   // row_begin); sat_row (row_end - row_begin u32) receives 1 for rows needing the wide kernel;
@@ -491,6 +496,7 @@ struct SsspLdsLaunch {
   uint32_t delta = 0;
   unsigned long long* work = nullptr;
   unsigned long long* diag = nullptr;
+  unsigned long long* pops = nullptr;  // with work: SSSP_POP_WORDS counters the launch adds to (see above)
   // the plan (optional): the rows to run (blk_rows, n_blk) and their bound rows (ub_row, ub_w),
   // as described above; plan_ctl / plan_ph: the device plan's phase to run (n_blk then bounds
   // its row count, which only the device knows); plan_ctr: the launch's claim counters, zeroed

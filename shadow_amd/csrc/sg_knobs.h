@@ -37,6 +37,7 @@
 //   SG_SSSP_CLAIM | 64 | 1 .. 64 | tune | LDS search: queue entries a wave claims at once
 //   SG_SSSP_SLEEP | 0 | >= 0 | tune | LDS search: idle back-off, units of ~512 cycles
 //   SG_SSSP_LANE_DEG | 64 | >= 0 | tune | LDS search: out-degree up to which a wave takes the lane path
+//   SG_SSSP_STEP_ARCS | 256 | >= 0 | tune | LDS search: arcs up to which a pop takes the arc-parallel step sized to them (0: never)
 //   SG_SSSP_PERSIST | 1 | 0, 1 | test | LDS search: 0 launches a workgroup per row
 //   SG_SSSP_CHAIN | 1 | 0, 1 | tune | LDS search: 0 takes rows in list order, none seeded from the row the workgroup just finished
 //   SG_SSSP_SPIN_MAX | 4194304 | >= 1 | test | LDS and bucketed searches: spin budget per wave; small values make searches give up

@@ -505,8 +505,25 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   uint32_t* claim = k.chain ? sat + rows : nullptr;
   // the relaxation counters, then the chained rows' two: rows seeded in place, those with exact seeds
   // ... then the ring invariant's two: ring slots a row's end found non-empty, rows looked at
-  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_SHARDS + 4) : nullptr;
-  if (work) SG_HIP(hipMemsetAsync(work, 0, (WORK_SHARDS + 4) * 8, st));
+  // ... then, with SG_SSSP_DIAG, the pops by class (SSSP_POP_WORDS)
+  constexpr int WORK_WORDS = WORK_SHARDS + 4 + SSSP_POP_WORDS;
+  unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_WORDS) : nullptr;
+  if (work) SG_HIP(hipMemsetAsync(work, 0, WORK_WORDS * 8, st));
+  // counting mode with SG_SSSP_DIAG: the pops of the launch just issued, by class (the counters run on)
+  unsigned long long pops_seen[SSSP_POP_WORDS] = {};
+  auto diag_pops = [&](const char* what, int ph) {
+    if (!work || !k.diag) return;
+    unsigned long long c[SSSP_POP_WORDS];
+    copy_to_host(ctx, c, work + WORK_SHARDS + 4, sizeof(c));
+    static const char* const cls[SSSP_POP_CLASSES] = {"0", "1", "2", "3-4", "5-8", ">8"};
+    for (int i = 0; i < SSSP_POP_CLASSES; i++) {
+      const unsigned long long p = c[3 * i] - pops_seen[3 * i], a = c[3 * i + 1] - pops_seen[3 * i + 1],
+                               cy = c[3 * i + 2] - pops_seen[3 * i + 2];
+      fprintf(stderr, "[sssp] %s %d pops of S %s: %llu pops, %llu arcs, %llu step cycles (%.0f per pop)\n", what, ph,
+              cls[i], p, a, cy, (double)cy / (double)std::max(1ull, p));
+    }
+    for (int i = 0; i < SSSP_POP_WORDS; i++) pops_seen[i] = c[i];
+  };
   unsigned long long chained_seen[2] = {0, 0};
   unsigned long long phase_chained[SSSP_PHASES_MAX] = {};
   // counting mode: the rows this launch chained (kept per phase; SG_SSSP_DIAG prints them)
@@ -549,6 +566,7 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   base.delta = k.delta;
   base.work = work;
   base.diag = diag;
+  base.pops = work && k.diag ? work + WORK_SHARDS + 4 : nullptr;
   if (k.flagged) {
     uint32_t* done = ctx->r_done.get<uint32_t>(std::max(rows, 1u));
     const SsspDevPlan plan = sssp_device_plan(ctx, net, d_used, n_used, row_begin, row_end, k.n_phase, k.kb, k.exact,
@@ -564,6 +582,7 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
       TimedLaunch tl(ctx, "sssp", 0.0);
       launch_sssp_lds(ctx, net, l);
     }
+    diag_pops("launch", 0);
     publish_phases(plan);  // (the one launch chains no rows)
   } else if (k.phased) {
     // the plan's bound rows beside phase 0 (sssp_plan_bounds_side) -- not with timers on, where
@@ -589,6 +608,7 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
         launch_sssp_lds(ctx, net, l);
       }
       diag_chained("phase", ph);
+      diag_pops("phase", ph);
       if (ph == 0 && plan.bounds_deferred) {
         sssp_plan_bounds_side(ctx, net, plan, d_used, row_begin, row_end, k.kb, k.exact, k.hops);
         // the build's self-loop check rides along; the bounded phases wait for both
@@ -622,13 +642,30 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
       launch_sssp_lds(ctx, net, l);
     }
     diag_chained("launch", 0);
+    diag_pops("launch", 0);
   }
   if (diag) print_sssp_diag(ctx, net, diag, n_diag, k.delta);
   std::vector<uint32_t> wide_rows = finish_rows(ctx, sat, row_begin, rows, told);
   ctx->side_busy = false;  // (the context stream waited for the side stream and was synchronised)
   if (work) {
-    unsigned long long w[WORK_SHARDS + 4];
-    timer_add_work(ctx, "sssp", read_work(ctx, work, w, 4));
+    unsigned long long w[WORK_WORDS];
+    timer_add_work(ctx, "sssp", read_work(ctx, work, w, WORK_WORDS - WORK_SHARDS));
+    // with SG_SSSP_DIAG, read_timer("sssp_pop_s<class>") = (0, pops, arcs) and ("sssp_pop_s<class>_cyc") =
+    // (0, pops, step cycles) of this build's pops of S = ceil(arcs / 64) slots per lane, the classes named
+    // by their largest S (0, 1, 2, 4, 8, and "gt8"); ("sssp_pops") = (0, pops counted by the waves, those of
+    // them that took the lane path)
+    if (k.diag) {
+      static const char* const cls[SSSP_POP_CLASSES] = {"0", "1", "2", "4", "8", "gt8"};
+      const unsigned long long* pc = w + WORK_SHARDS + 4;
+      for (int i = 0; i < SSSP_POP_CLASSES; i++) {
+        char name[32];
+        snprintf(name, sizeof(name), "sssp_pop_s%s", cls[i]);
+        timer_set_counter(ctx, name, (double)pc[3 * i + 1], pc[3 * i]);
+        snprintf(name, sizeof(name), "sssp_pop_s%s_cyc", cls[i]);
+        timer_set_counter(ctx, name, (double)pc[3 * i + 2], pc[3 * i]);
+      }
+      timer_set_counter(ctx, "sssp_pops", (double)pc[3 * SSSP_POP_CLASSES], pc[SSSP_POP_WORDS - 1]);
+    }
     // read_timer("sssp_chained"): (0, rows with exact chain seeds, chained rows) of this build
     timer_set_counter(ctx, "sssp_chained", (double)w[WORK_SHARDS], w[WORK_SHARDS + 1]);
     // read_timer("sssp_ring_left"): (0, rows whose ring was looked at, slots found non-empty: 0 by the invariant)

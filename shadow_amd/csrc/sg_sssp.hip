@@ -49,11 +49,12 @@
 //     the dirty nodes left are those at or beyond `split`.  split = (smallest
 //     dirty latency) + delta, the dirty nodes below it are queued, and the
 //     waves go on.  No dirty node left: the search is done.
-//   * Relaxing a popped node: when the largest out-degree among the wave's
-//     entries is at most LANE_DEG_MAX, each lane walks its own node's arcs, eight
-//     loads in flight (no cross-lane bookkeeping on the dependent chain);
-//     otherwise the wave expands the entries' arcs into consecutive slots
-//     (owner by scatter + max-scan) and relaxes SSSP_K chunks of 64 at once.
+//   * Relaxing a popped node: a pop of at most step_arcs arcs (SG_SSSP_STEP_ARCS) is
+//     expanded into consecutive slots (owner by scatter + max-scan) and relaxed in as
+//     many chunks of 64 as it holds: one, two, or rounds of SSSP_K.  A larger pop: when
+//     the largest out-degree among the wave's entries is at most LANE_DEG_MAX, each lane
+//     walks its own node's arcs, eight loads in flight (no cross-lane bookkeeping on the
+//     dependent chain); otherwise the expansion, SSSP_K chunks of 64 at once.
 //
 // Bounds (ub_row / ub_w).  For an arc s -> s' whose row D[s'] is already in the
 // table, w(s, s') + D[s'][v] is the latency of a real path from s, so it bounds
@@ -207,7 +208,8 @@ __global__ void __launch_bounds__(NT)
                const uint32_t* __restrict__ ub_row, const uint32_t* __restrict__ ub_w,
                uint32_t* __restrict__ item_ctr, uint32_t n_items, uint32_t spin_max,
                const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done,
-               const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag, int ident) {
+               const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag, int ident, uint32_t step_arcs,
+               unsigned long long* __restrict__ popc) {
   constexpr int NW = NT / 64;
   constexpr int AUX = FLAG ? SSSP_SC1 : 0;  // bound rows and the output: sc1 in the flagged launch
   // Chained rows: persistent workgroups, never the flagged launch.  The claim words and the maps
@@ -235,6 +237,10 @@ __global__ void __launch_bounds__(NT)
   unsigned long long* key = (unsigned long long*)smem;
   uint32_t* off = (uint32_t*)(key + n);  // out_off staged in LDS (n + 1)
   uint16_t* ring = (uint16_t*)(smem + (size_t)n * 8 + (((size_t)n + 1) * 4 + 7) / 8 * 8);
+  // counting build with SG_SSSP_DIAG (popc set): the workgroup's pops by class, behind the ring (cap is a
+  // multiple of 64, so 8-byte aligned; the launch asks for SSSP_POP_WORDS more words of LDS)
+  unsigned long long* s_popc = (unsigned long long*)(ring + cap);
+  const bool pop_diag = COUNT && popc;
   __shared__ uint32_t ctl[8];  // TAIL
   constexpr int TAIL = 1;
   // (head << 32) | busy in one word: a claim advances head and counts its wave
@@ -297,6 +303,7 @@ __global__ void __launch_bounds__(NT)
   // loop's barriers order this ahead of the first search.)
   for (uint32_t i = tid; i < cap; i += NT) ring[i] = RING_EMPTY;
   for (int i = tid; i < NW * 64 * SSSP_K; i += NT) (&own[0][0])[i] = 0;
+  if (pop_diag && tid < SSSP_POP_WORDS) s_popc[tid] = 0ull;
   if (item_ctr && tid == 0) {
     s_item = next_listed();
     s_chain = 0u;
@@ -656,12 +663,16 @@ __global__ void __launch_bounds__(NT)
       uint64_t ku = 0;
       bool stuck = false;
       if (on) {
-        volatile uint16_t* slot = &ring[slot_of(h + lane)];
+        // (relaxed workgroup-scope accesses, so the slot is read and written as LDS: through a
+        // volatile pointer both were flat operations, the store with a wait for it behind it)
+        uint16_t* slot = &ring[slot_of(h + lane)];
         uint16_t x;
         uint32_t sp = 0;
-        while ((x = *slot) == RING_EMPTY && ++sp < spin_max) __builtin_amdgcn_s_sleep(0);
+        while ((x = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == RING_EMPTY &&
+               ++sp < spin_max)
+          __builtin_amdgcn_s_sleep(0);
         stuck = x == RING_EMPTY;
-        *slot = RING_EMPTY;
+        __hip_atomic_store(slot, RING_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         u = stuck ? src : x;
         a0 = off[u];
         a1 = off[u + 1];
@@ -673,13 +684,15 @@ __global__ void __launch_bounds__(NT)
         goto wave_exit;
       }
       const uint32_t deg = a1 - a0;
-      const uint32_t dmax = __builtin_amdgcn_readlane(wave_incl_max(deg), 63);
-      const unsigned long long tc2 = (COUNT && diag) ? clock64() : 0;
+      // the pop's arcs: the scan the arc-parallel step needs anyway, taken once
+      const uint32_t deg_incl = wave_incl_sum(deg);
+      const uint32_t T = __builtin_amdgcn_readlane(deg_incl, 63);
+      const unsigned long long tc2 = (COUNT && (diag || pop_diag)) ? clock64() : 0;
       // arcs [ea0, ea0 + edeg) of each lane's node, arc-parallel: the wave's arcs in consecutive
       // slots, KX chunks of 64 at once (owner lane by scatter + max-scan)
-      auto expand = [&](auto kx, uint32_t ea0, uint32_t edeg) {
+      // (incl: the inclusive scan of edeg over the wave)
+      auto expand = [&](auto kx, uint32_t ea0, uint32_t edeg, uint32_t incl) {
         constexpr int KX = decltype(kx)::value;
-        const uint32_t incl = wave_incl_sum(edeg);
         const uint32_t base = incl - edeg;
         const uint32_t T = __builtin_amdgcn_readlane(incl, 63);
         if (COUNT) n_rel += T;
@@ -721,12 +734,26 @@ __global__ void __launch_bounds__(NT)
           append_q<KX>(app, v, ring, &ctl[TAIL], slot_of, lane);
         }
       };
-      if (dmax <= lane_deg_max) {
+      // ---- the step follows the arcs: a pop of at most step_arcs arcs goes arc-parallel whatever its
+      // entries' degrees, in ceil(T / 64) slots per lane (1, 2, or rounds of SSSP_K) where the lane path
+      // issues LA slots and its overflow round for every pop.  (A pop without arcs relaxes nothing.)
+      const bool small = T <= step_arcs;
+      // (the largest degree is only ever compared: a ballot each, no second scan)
+      if (small && T <= 64u) {
+        expand(std::integral_constant<int, 1>(), a0, deg, deg_incl);
+      } else if (small && T <= 128u) {
+        expand(std::integral_constant<int, 2>(), a0, deg, deg_incl);
+      } else if (small || __builtin_amdgcn_ballot_w64(deg > lane_deg_max)) {
+        // ---- expansion path (a small pop past 128 arcs, or a high out-degree): arcs of the 64 entries in
+        // consecutive slots
+        expand(std::integral_constant<int, SSSP_K>(), a0, deg, deg_incl);
+      } else {
         // ---- lane path: each lane walks its node's first LA arcs (LA loads in flight); the arcs
         // past them (nodes of degree > LA only) go arc-parallel like the expansion path.  At C3
         // (mean degree 8, a wave's largest ~14) a second round of LA slots per lane was mostly
         // idle lanes: 3.10 -> 2.83 ms (profiles/r05/ab_sssp_hybrid_r6x.txt)
         if (COUNT) n_rel += __builtin_amdgcn_readlane(wave_incl_sum(min(deg, (uint32_t)LA)), 63);
+        if (pop_diag && lane == 0) atomicAdd(&s_popc[3 * SSSP_POP_CLASSES], 1ull);
         {
           constexpr uint32_t j0 = 0;
           uint32_t v[LA], lat[LA], om[LA];
@@ -747,19 +774,27 @@ __global__ void __launch_bounds__(NT)
           offer_all(std::integral_constant<int, LA>(), valid, v, cand, app);
           append_q<LA>(app, v, ring, &ctl[TAIL], slot_of, lane);
         }
-        if (dmax > (uint32_t)LA)  // the arcs past each node's first LA, arc-parallel
-          expand(std::integral_constant<int, 1>(), a0 + LA, deg > (uint32_t)LA ? deg - LA : 0u);
-      } else {
-        // ---- expansion path (high out-degree): arcs of the 64 entries in consecutive slots
-        expand(std::integral_constant<int, SSSP_K>(), a0, deg);
+        if (__builtin_amdgcn_ballot_w64(deg > (uint32_t)LA)) {  // the arcs past each node's first LA, arc-parallel
+          const uint32_t rest = deg > (uint32_t)LA ? deg - LA : 0u;
+          expand(std::integral_constant<int, 1>(), a0 + LA, rest, wave_incl_sum(rest));
+        }
       }
       // release the claim after this wave's appends (LDS keeps a wave's operations in order)
       if (lane == 0) atomicSub(&hb, 1ull);
-      if (COUNT && diag) {
+      if (COUNT && (diag || pop_diag)) {
         const unsigned long long tc3 = clock64();
-        cyc_claim += tc1 - tc0;
-        cyc_pop += tc2 - tc1;
-        cyc_steps += tc3 - tc2;
+        if (diag) {
+          cyc_claim += tc1 - tc0;
+          cyc_pop += tc2 - tc1;
+          cyc_steps += tc3 - tc2;
+        }
+        if (pop_diag && lane == 0) {  // the pop's class by S = ceil(T / 64): pops, arcs, step cycles
+          const uint32_t S = (T + 63u) / 64u;
+          const int cls = S <= 2u ? (int)S : S <= 4u ? 3 : S <= 8u ? 4 : 5;
+          atomicAdd(&s_popc[3 * cls], 1ull);
+          atomicAdd(&s_popc[3 * cls + 1], (unsigned long long)T);
+          atomicAdd(&s_popc[3 * cls + 2], tc3 - tc2);
+        }
       }
     }
     if (COUNT && lane == 0 && n_rel) atomicAdd(&work[bi & 63], (unsigned long long)n_rel);
@@ -780,6 +815,13 @@ __global__ void __launch_bounds__(NT)
 
     // ---- write the row: columns in used order, diagonal = the raw self-loop (graph/mod.rs:210-217)
     __syncthreads();  // every thread has read s_item (at the row's start) before it is written again
+    if (pop_diag) {  // (no wave is in a step: the row's classes move to the launch's counters)
+      if (tid < SSSP_POP_WORDS - 1 && s_popc[tid]) {
+        atomicAdd(&popc[tid], s_popc[tid]);
+        s_popc[tid] = 0ull;
+      }
+      if (lane == 0 && n_pops) atomicAdd(&popc[SSSP_POP_WORDS - 1], (unsigned long long)n_pops);
+    }
     if (item_ctr && !chain_on) {
       if (wv == 0) {  // the next row (see the row loop), and its bound rows (see list_bounds)
         uint32_t ni = 0;
@@ -1023,6 +1065,9 @@ struct SsspKnobs {
   // bug, never reached by a correct search; SG_SSSP_SPIN_MAX (tests) lowers it so
   // that searches give up and their rows take the wide kernel
   uint32_t spin_max;
+  // SG_SSSP_STEP_ARCS: a pop of at most this many arcs takes the arc-parallel step sized to them
+  // (0: the lane path unless an entry's degree is past lane_deg)
+  uint32_t step_arcs;
 };
 static SsspKnobs sssp_knobs() {
   SsspKnobs k;
@@ -1031,13 +1076,14 @@ static SsspKnobs sssp_knobs() {
   k.lane_deg = (uint32_t)std::max(0, knob_int("SG_SSSP_LANE_DEG", 64));
   k.persist = !knob_off("SG_SSSP_PERSIST");
   k.spin_max = sssp_spin_max();
+  k.step_arcs = (uint32_t)std::max(0, knob_int("SG_SSSP_STEP_ARCS", 256));
   return k;
 }
 
 void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
   const SsspKnobs k = sssp_knobs();
   const uint32_t n = net->n_nodes;
-  const size_t lds = sssp_lds_bytes(n);
+  size_t lds = sssp_lds_bytes(n);
   if (!sssp_lds_fits(n)) throw Error(SG_ERR_INVALID_ARG, "graph too large for the LDS-resident search");
   if ((uint64_t)net->n_arcs * 12 >= (1ull << 31)) throw Error(SG_ERR_INVALID_ARG, "too many arcs for 32-bit offsets");
   const int vec = l.n_used % 4 == 0 && ((uintptr_t)l.out_lat & 15) == 0 && ((uintptr_t)l.out_loss & 15) == 0;
@@ -1057,6 +1103,10 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
   // Chained rows: persistent workgroups on an undirected graph (the arc t -> s mirrors s -> t),
   // never the flagged launch (the caller passes claim words only with SG_SSSP_CHAIN on)
   const SsspChainDesc* chain = persist && !l.done && !net->directed ? l.chain : nullptr;
+  // the pop classes (counting build): their LDS words behind the ring, where the CU has room for them
+  unsigned long long* pops = l.work ? l.pops : nullptr;
+  if (pops && lds + SSSP_POP_WORDS * 8 + SSSP_STATIC_LDS > LDS_PER_CU) pops = nullptr;
+  if (pops) lds += SSSP_POP_WORDS * 8;
   auto go = [&](auto kern) {
     SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)(LDS_PER_CU - SSSP_STATIC_LDS)));
@@ -1064,7 +1114,7 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
                        l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
                        l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
                        k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
-                       l.done, chain, ctx->apsp_ret + 4, (int)l.ident);
+                       l.done, chain, ctx->apsp_ret + 4, (int)l.ident, k.step_arcs, pops);
   };
   // <counting, threads, lane arcs, fill symbol, flagged>
   if (l.done) {  // the flagged one-launch plan

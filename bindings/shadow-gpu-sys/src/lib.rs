@@ -371,6 +371,8 @@ pub const SG_TIMERS_COUNT_WORK: u32 = 2;
 /// network.use_shortest_path (configuration.rs:315-326)
 pub const SG_ROUTE_SHORTEST_PATH: u32 = 1;
 pub const SG_ROUTE_OUT_DEVICE: u32 = 2;
+/// sg_link_queue: carry each wait to the packet's later hops
+pub const SG_LINK_QUEUE_CARRY: u32 = 4;
 pub const SG_CELL_WIDE: u32 = 0xFFFF_FFFF;
 pub const SG_COMM_ID_BYTES: usize = 128;
 
@@ -508,7 +510,9 @@ unsafe extern "C" {
     /// per-link service cost (cost_ps picoseconds per unit of weight[packet[i]], NULL weight: 1), the
     /// server free from link_free_in[L] (NULL: 0).  Per record wait, done and the records ahead; per
     /// link the new free time, the busy time, the largest and the summed wait, the deepest queue.
-    /// First order: a wait is not propagated to the packet's later hops.
+    /// First order: a wait is not propagated to the packet's later hops, unless flags carries
+    /// SG_LINK_QUEUE_CARRY: then packet is required, n_weights bounds it, every link serves in
+    /// ascending (carried enter, packet) order and the call iterates until no time moves.
     pub fn sg_link_queue(ctx: *mut sg_ctx, flags: u32, n_links: u32, link_off: *const u64, n_records: u64,
                          enter_ns: *const u64, packet: *const u32, weight: *const u32, n_weights: u32,
                          cost_ps: *const u64, link_free_in: *const u64, out_wait_ns: *mut u64,

@@ -797,8 +797,9 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  *   out_link_wait_sum_ns  u64, wraps
  *   out_link_ahead_max    u32
  * An empty segment has 0 in the last four.  n_records == 0 is legal.
- * FIRST ORDER: a wait is not propagated to the packet's later hops; enter_ns
- * downstream is the trace's.  CHAINING out_link_free into a later call's
+ * FIRST ORDER, unless SG_LINK_QUEUE_CARRY is set (below): a wait is not propagated
+ * to the packet's later hops; enter_ns downstream is the trace's.
+ * CHAINING out_link_free into a later call's
  * link_free_in equals one call over both calls' records only when every record of
  * the later call arrives after every record of the earlier one on its link.
  *
@@ -815,7 +816,56 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  * above; packet[i] >= n_weights, SG_ERR_INVALID_ARG with the pair (link, i -
  * link_off[link]) of the smallest such i; done_i reaching 2^64 - 1,
  * SG_ERR_TIME_OVERFLOW with the same kind of pair, the smallest i.
- * Timers: "link_queue" (work = records), "link_queue_ahead". */
+ * Timers: "link_queue" (work = records), "link_queue_ahead".
+ *
+ * SG_LINK_QUEUE_CARRY in flags: every wait is carried to the packet's later hops.
+ * Without the flag the call is what it was, bit for bit, with the same launches.
+ * Inputs.  packet is required.  n_weights is the number of packets: it bounds
+ * packet[i] whether or not weight is NULL.  enter_ns is the uncongested schedule;
+ * the library only reads it.
+ * A packet's chain.  The records with equal packet value, taken in ascending input
+ * enter_ns, are that packet's chain.  gap_i = enter_ns[next(i)] - enter_ns[i] is the
+ * uncongested time from entering record i's link to entering the link of the
+ * packet's next record; it must be at least 1 (in a real trace it is the link
+ * latency; with `watch` it is the link latency plus the latencies of the unwatched
+ * links in between, so an unwatched link behaves as a link of infinite rate with
+ * no extra work).  No hop or exit_ns argument is needed.
+ * Carried times.  enter'_i = enter_ns[i] for the first record of a chain,
+ * enter'_next(i) = done_i + gap_i otherwise: store and forward, service is paid on
+ * every link.
+ * Each link's queue.  Link L serves its records in ascending (enter', packet)
+ * order, not in the order given.  The recurrence is unchanged, starting from
+ * link_free_in[L]: start = max(enter', done), done = start + s, wait = start -
+ * enter'; ahead is the number of records earlier in that order with done_j >
+ * enter'_i; s is exactly the value above.  (A packet's chain visits a link once, as
+ * a tree path does: two records of one packet on one link have no order here.)
+ * Outputs.  The result is the unique solution of these equations: what an
+ * event-driven simulation yields when it processes arrivals in global (time,
+ * packet) order.  Outputs keep their meaning and their index: out_wait_ns[i],
+ * out_done_ns[i] and out_ahead[i] belong to input record i, so the result does not
+ * depend on the order in which a link's records are given.  out_link_free[L] is the
+ * done of the record served last; the per-link sums are over the carried
+ * schedule.  With every cost_ps 0 and no link_free_in, enter' = enter_ns and all
+ * waits are 0; a chain of one record per packet gives the result above for sorted
+ * segments.  The carried enter time of record i is done_i - s_i - wait_i.
+ * The call iterates (sort every link by the carried times, scan, carry done + gap
+ * to the next record) until no time moves, and SYNCHRONISES ONCE PER ITERATION; an
+ * iteration settles at least the smallest gap of simulated time.
+ * SG_LINK_QUEUE_CARRY_ITERS (default 4096) bounds the iterations: reaching it is an
+ * error, never a partial answer.
+ * Errors with the flag.  Every output untouched: NULL packet, SG_ERR_INVALID_ARG;
+ * n_records > 2^32 - 2, SG_ERR_CAPACITY.  Found on the device (outputs undefined,
+ * never a trap, no index formed from a bad value), in this order: a bad link_off;
+ * packet[i] >= n_weights, both as above; two records of one packet with equal
+ * enter_ns, SG_ERR_INVALID_ARG with the pair (link, i - link_off[link]) of the
+ * smallest such record index i; done or done + gap reaching 2^64 - 1,
+ * SG_ERR_TIME_OVERFLOW, pair unspecified; not converged within the bound,
+ * SG_ERR_CAPACITY with the pair (iterations run, UINT32_MAX).
+ * Timers with the flag: "link_queue_index" (the chains), "link_queue_sort",
+ * "link_queue" (the scan), "link_queue_carry" (the propagate step),
+ * "link_queue_ahead"; read_timer("link_queue_iters") gives the iterations of the
+ * last carried call. */
+#define SG_LINK_QUEUE_CARRY 0x4u
 int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
                       const uint64_t* link_off, uint64_t n_records,
                       const uint64_t* enter_ns, const uint32_t* packet,

@@ -133,6 +133,12 @@ struct sg_ctx {
   // link queues (sg_queue.hip): the device copies of a host-mode call's six inputs and eight
   // outputs, the tile aggregates, the done times when the caller takes none, the flag words
   sg::DevBuf q_buf[14], q_agg, q_done, q_flag;
+  // the carried form (SG_LINK_QUEUE_CARRY; it shares tr_key, tr_key2 and tr_work with the link
+  // trace's sort, and p_sums through scan_counts): the per-packet counters with the fill's
+  // cursors and the sort's work counter, the packet offsets, the records in chain order, next,
+  // gap, the carried enter times, and a link-sorted pass: enter, packet, the permutation, done,
+  // wait, ahead
+  sg::DevBuf qc_cnt, qc_off, qc_list, qc_next, qc_gap, qc_cur, qc_enter, qc_packet, qc_perm, qc_done, qc_wait, qc_ahead;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

@@ -33,13 +33,19 @@
 //                   maximum by the same wave reduction.
 // No workgroup waits on another inside a launch.  SG_LINK_QUEUE_SERIAL = 1 replaces agg, carry
 // and rescan by k_queue_serial, a lane per link looping over its segment.
+//
+// SG_LINK_QUEUE_CARRY carries every wait to the packet's later hops: a fixed point over the same
+// scan, with every link sorted anew by the carried times in each iteration ("the carried form",
+// below queue_run's helpers).
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "sg_internal.h"
 #include "sg_knobs.h"
 #include "sg_scan.h"
+#include "sg_segsort.h"
 
 namespace sg {
 namespace {
@@ -54,7 +60,9 @@ constexpr u64 Q_MAX = ~0ull;
 constexpr uint32_t Q_NO_LINK = 0xFFFFFFFFu;
 
 // flag words (all ones: nothing found; the smallest value wins)
-enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_WORDS = 3 };
+// (the carried form adds Q_DUP, the smallest record with a twin in its packet's chain, and
+// Q_CHANGED, 0 once an iteration moved an enter time)
+enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_WORDS = 5 };
 
 struct QArgs {
   const u64* off;
@@ -414,6 +422,302 @@ u64 bad_link_off(const uint64_t* off, uint32_t n_links, uint64_t n) {
               (uint32_t)link, 0xFFFFFFFFu);
 }
 
+// The queue scan of a.enter / a.packet as they lie, in either form, on the context stream.
+void launch_scan(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial) {
+  hipStream_t st = ctx->stream;
+  if (serial) {
+    hipLaunchKernelGGL(k_queue_serial, dim3(grid_for(a.n_links, Q_THREADS, 16u * (unsigned)ctx->n_cu)), dim3(Q_THREADS),
+                       0, st, a);
+    SG_CHECK_LAUNCH();
+  } else {
+    hipLaunchKernelGGL(k_queue_agg, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_queue_carry, dim3(1), dim3(Q_CARRY_THREADS), 0, st, a, n_tiles);
+    SG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_queue_rescan, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+  }
+}
+
+// ---- the carried form (SG_LINK_QUEUE_CARRY): a wait moves the packet's later hops.
+//
+// Set-up, once: the records of every packet in ascending input (enter, record) order -- a
+// histogram per packet (k_carry_count, which also checks packet[i] < n_packets), scan_counts, a
+// fill with a cursor per packet (k_carry_fill) and the segmented sort of sg_segsort.h with packets
+// for segments -- then k_carry_chain: next[i], gap[i] = enter[next] - enter[i] (0: two records of
+// one packet at one time, flagged) and cur[i] = enter[i].
+// An iteration: keys (cur[i], packet[i], i) (k_carry_keys), the segmented sort by link over the
+// caller's link_off, the queue scan over the sorted order (done only), and k_carry_propagate, a
+// lane per sorted record: cur[next] = done + gap, and the changed word when that moved it.  Every
+// cur cell has one writer, and the sort copied the keys before: the update is in place.  The host
+// reads the flag words once per iteration; when nothing changed, the scan runs once more over the
+// same order with every output the caller takes, k_queue_ahead after it, and k_carry_scatter
+// moves wait, done and ahead through the permutation to the input indices.
+// No index is formed from a value that was not checked: a record index read from the sort's
+// output is compared with n (two records of one packet on one link can meet at one carried time
+// while the iteration is under way; the sort then ranks them alike and leaves a slot unwritten).
+constexpr uint32_t Q_NO_NEXT = 0xFFFFFFFFu;
+
+struct CArgs {
+  u64 n;
+  uint32_t n_packets;
+  const u64* enter;  // the uncongested schedule
+  const uint32_t* packet;
+  uint32_t* cnt;   // records per packet
+  uint32_t* fill;  // the fill's cursor per packet
+  const u64* pkt_off;
+  uint4* key;
+  uint32_t* list;  // the records packet by packet, ascending (enter, record)
+  uint32_t* next;
+  u64* gap;
+  u64* cur;
+  // a link-sorted pass
+  const uint32_t* perm;
+  u64* s_done;
+  u64* s_wait;
+  uint32_t* s_ahead;
+  u64* flag;
+};
+
+__device__ __forceinline__ bool carry_bad(const CArgs& c) {
+  return c.flag[Q_BAD_OFF] != Q_MAX || c.flag[Q_BAD_PACKET] != Q_MAX;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_count(const CArgs c) {
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  const uint32_t p = c.packet[i];
+  if (p >= c.n_packets)
+    atomicMin(&c.flag[Q_BAD_PACKET], i);
+  else
+    atomicAdd(&c.cnt[p], 1u);
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_fill(const CArgs c) {
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (i >= c.n || carry_bad(c)) return;
+  const uint32_t p = c.packet[i];
+  if (p >= c.n_packets) return;
+  const u64 at = c.pkt_off[p] + atomicAdd(&c.fill[p], 1u);
+  const u64 e = c.enter[i];
+  if (at < c.pkt_off[p + 1]) c.key[at] = make_uint4((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)i, 0u);
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_chain(const CArgs c) {
+  const u64 j = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (j >= c.n || carry_bad(c)) return;
+  const uint32_t i = c.list[j];
+  if (i >= c.n) return;
+  const uint32_t p = c.packet[i];
+  if (p >= c.n_packets) return;
+  const u64 e = c.enter[i];
+  uint32_t nx = Q_NO_NEXT;
+  u64 g = 0ull;
+  if (j + 1 < c.pkt_off[p + 1]) {
+    nx = c.list[j + 1];
+    if (nx >= c.n) {
+      nx = Q_NO_NEXT;
+    } else {
+      g = c.enter[nx] - e;  // (the list is ascending)
+      if (g == 0ull) atomicMin(&c.flag[Q_DUP], (u64)i);  // (equal times lie in record order: i < nx)
+    }
+  }
+  c.next[i] = nx;
+  c.gap[i] = g;
+  c.cur[i] = e;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_keys(const CArgs c) {
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  const u64 e = c.cur[i];
+  c.key[i] = make_uint4((uint32_t)e, (uint32_t)(e >> 32), c.packet[i], (uint32_t)i);
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_propagate(const CArgs c) {
+  const u64 j = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (j >= c.n) return;
+  const uint32_t i = c.perm[j];
+  if (i >= c.n) return;
+  const uint32_t nx = c.next[i];
+  if (nx == Q_NO_NEXT) return;  // (else below n: k_carry_chain checked it)
+  const u64 v = sat_add(c.s_done[j], c.gap[i]);
+  if (v == Q_MAX) atomicMin(&c.flag[Q_OVERFLOW], j);
+  if (v != c.cur[nx]) {
+    c.cur[nx] = v;
+    c.flag[Q_CHANGED] = 0ull;
+  }
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_carry_scatter(const CArgs c, u64* wait, u64* done, uint32_t* ahead) {
+  const u64 j = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (j >= c.n) return;
+  const uint32_t i = c.perm[j];
+  if (i >= c.n) return;
+  if (wait) wait[i] = c.s_wait[j];
+  if (done) done[i] = c.s_done[j];
+  if (ahead) ahead[i] = c.s_ahead[j];
+}
+
+using PairOf = std::function<void(u64, uint32_t&, uint32_t&)>;
+
+// read_timer("link_queue_iters") = (0, the iterations of the last carried call, its records).
+// Kept whether or not the timers are on: the iterations are part of what a caller is told.
+void set_iters(sg_ctx* ctx, u64 n, uint32_t iters) {
+  KernelTimer* t = nullptr;
+  for (auto& kv : ctx->timers)
+    if (kv.first == "link_queue_iters") t = &kv.second;
+  if (!t) {
+    ctx->timers.emplace_back("link_queue_iters", KernelTimer());
+    t = &ctx->timers.back().second;
+  }
+  t->work = (double)n;
+  t->launches = iters;
+}
+
+// `a`: the call's arrays on the device (n > 0 records, agg_* set for the scan form, flag words all ones).
+void queue_carry(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial, bool want_ahead, const PairOf& pair_of,
+                 const std::function<void(u64)>& throw_bad_packet) {
+  hipStream_t st = ctx->stream;
+  const u64 n = a.n;
+  const uint32_t nl = a.n_links, np = a.n_weights;
+  const int cap = knob_int("SG_LINK_QUEUE_CARRY_ITERS", 4096, 1, INT_MAX);
+  const uint32_t piece = (uint32_t)knob_int("SG_LINK_TRACE_PIECE", (int)TR_PIECE_MAX, (int)TR_RANK_MAX, (int)TR_PIECE_MAX);
+  const uint64_t work_cap64 = segsort_work_cap(n, piece);
+  if (work_cap64 > 0xFFFFFFFFull) throw Error(SG_ERR_CAPACITY, "more records than one carried call sorts");
+  const uint32_t work_cap = (uint32_t)work_cap64;
+  const dim3 g_rec(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), blk(Q_THREADS);
+
+  // the counters and the cursors per packet and the sort's work counter: one block, zeroed
+  uint32_t* ctr = ctx->qc_cnt.get<uint32_t>(2 * (size_t)np + 1);
+  SG_HIP(hipMemsetAsync(ctr, 0, (2 * (size_t)np + 1) * 4, st));
+  uint32_t* n_work = ctr + 2 * (size_t)np;
+  u64* pkt_off = ctx->qc_off.get<u64>((size_t)np + 2);  // (the last word: the scan's total)
+  uint4* key = ctx->tr_key.get<uint4>(n);
+  uint4* key2 = ctx->tr_key2.get<uint4>(n);
+  uint2* work = ctx->tr_work.get<uint2>(work_cap);
+  u64* s_enter = ctx->qc_enter.get<u64>(n);
+  uint32_t* s_packet = ctx->qc_packet.get<uint32_t>(n);
+  uint32_t* perm = ctx->qc_perm.get<uint32_t>(n);
+  CArgs c = {};
+  c.n = n;
+  c.n_packets = np;
+  c.enter = a.enter;
+  c.packet = a.packet;
+  c.cnt = ctr;
+  c.fill = ctr + np;
+  c.pkt_off = pkt_off;
+  c.key = key;
+  c.list = ctx->qc_list.get<uint32_t>(n);
+  c.next = ctx->qc_next.get<uint32_t>(n);
+  c.gap = ctx->qc_gap.get<u64>(n);
+  c.cur = ctx->qc_cur.get<u64>(n);
+  c.perm = perm;
+  c.s_done = ctx->qc_done.get<u64>(n);
+  c.s_wait = a.wait ? ctx->qc_wait.get<u64>(n) : nullptr;
+  c.s_ahead = a.ahead ? ctx->qc_ahead.get<uint32_t>(n) : nullptr;
+  c.flag = a.flag;
+
+  // link_off's check alone: no output is written before the last pass
+  QArgs v = a;
+  v.link_free = v.busy = v.wmax = v.wsum = nullptr;
+  v.amax = nullptr;
+  hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), blk, 0, st, v);
+  SG_CHECK_LAUNCH();
+  {
+    TimedLaunch tl(ctx, "link_queue_index", (double)n);
+    hipLaunchKernelGGL(k_carry_count, g_rec, blk, 0, st, c);
+    SG_CHECK_LAUNCH();
+    scan_counts(ctx, c.cnt, np, pkt_off, pkt_off + np + 1);
+    hipLaunchKernelGGL(k_carry_fill, g_rec, blk, 0, st, c);
+    SG_CHECK_LAUNCH();
+    const TraceOut chain = {c.list, nullptr, nullptr, nullptr};
+    segsort_enqueue(ctx, pkt_off, np, (const uint4*)key, nullptr, key2, nullptr, chain, piece, work, work_cap, n_work);
+    hipLaunchKernelGGL(k_carry_chain, g_rec, blk, 0, st, c);
+    SG_CHECK_LAUNCH();
+  }
+  u64 h[Q_WORDS];
+  copy_to_host(ctx, h, a.flag, sizeof(h));
+  if (h[Q_BAD_OFF] != Q_MAX) throw_bad_off(h[Q_BAD_OFF]);
+  if (h[Q_BAD_PACKET] != Q_MAX) throw_bad_packet(h[Q_BAD_PACKET]);
+  if (h[Q_DUP] != Q_MAX) {
+    uint32_t lk, at;
+    pair_of(h[Q_DUP], lk, at);
+    throw Error(SG_ERR_INVALID_ARG,
+                "record " + std::to_string(h[Q_DUP]) + " (link " + std::to_string(lk) +
+                    ") enters at the time of another record of its packet",
+                lk, at);
+  }
+
+  // the scan's view of a sorted pass
+  QArgs s = v;
+  s.enter = s_enter;
+  s.packet = s_packet;
+  s.wait = nullptr;
+  s.done = c.s_done;
+  s.ahead = nullptr;
+  const TraceOut sorted = {s_packet, perm, s_enter, nullptr};
+  uint32_t iters = 0;
+  bool settled = false;
+  while (!settled && iters < (uint32_t)cap) {
+    iters++;
+    SG_HIP(hipMemsetAsync(a.flag + Q_CHANGED, 0xff, 8, st));
+    SG_HIP(hipMemsetAsync(n_work, 0, 4, st));
+    {
+      TimedLaunch tl(ctx, "link_queue_sort", (double)n);
+      hipLaunchKernelGGL(k_carry_keys, g_rec, blk, 0, st, c);
+      SG_CHECK_LAUNCH();
+      segsort_enqueue(ctx, a.off, nl, (const uint4*)key, nullptr, key2, nullptr, sorted, piece, work, work_cap, n_work);
+    }
+    {
+      TimedLaunch tl(ctx, "link_queue", (double)n);
+      launch_scan(ctx, s, n_tiles, serial);
+    }
+    {
+      TimedLaunch tl(ctx, "link_queue_carry", (double)n);
+      hipLaunchKernelGGL(k_carry_propagate, g_rec, blk, 0, st, c);
+      SG_CHECK_LAUNCH();
+    }
+    copy_to_host(ctx, h, a.flag, sizeof(h));
+    set_iters(ctx, n, iters);
+    if (h[Q_OVERFLOW] != Q_MAX) {
+      uint32_t lk, at;
+      pair_of(h[Q_OVERFLOW], lk, at);
+      throw Error(SG_ERR_TIME_OVERFLOW, "a record of link " + std::to_string(lk) + " is served or carried past 2^64 - 1 ns",
+                  lk, at);
+    }
+    settled = h[Q_CHANGED] == Q_MAX;
+  }
+  if (!settled)
+    throw Error(SG_ERR_CAPACITY,
+                "the carried times still moved after " + std::to_string(iters) + " iterations (SG_LINK_QUEUE_CARRY_ITERS)",
+                iters, 0xFFFFFFFFu);
+
+  // the last pass, over the order the last iteration sorted: every output the caller takes
+  s.wait = c.s_wait;
+  s.ahead = c.s_ahead;
+  s.link_free = a.link_free;
+  s.busy = a.busy;
+  s.wmax = a.wmax;
+  s.wsum = a.wsum;
+  s.amax = a.amax;
+  hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), blk, 0, st, s);
+  SG_CHECK_LAUNCH();
+  {
+    TimedLaunch tl(ctx, "link_queue", (double)n);
+    launch_scan(ctx, s, n_tiles, serial);
+  }
+  if (want_ahead) {
+    TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+    hipLaunchKernelGGL(k_queue_ahead, g_rec, blk, 0, st, s);
+    SG_CHECK_LAUNCH();
+  }
+  if (a.wait || a.done || a.ahead) {
+    hipLaunchKernelGGL(k_carry_scatter, g_rec, blk, 0, st, c, a.wait, a.done, a.ahead);
+    SG_CHECK_LAUNCH();
+  }
+}
+
 struct QueueCall {
   sg_ctx* ctx;
   uint32_t flags, n_links;
@@ -445,6 +749,12 @@ void queue_run(const QueueCall& c) {
   const bool dev = (c.flags & SG_ROUTE_OUT_DEVICE) != 0;
   const uint32_t nl = c.n_links;
   const uint64_t n = c.n;
+  if (c.flags & SG_LINK_QUEUE_CARRY) {
+    if (!c.packet) throw Error(SG_ERR_INVALID_ARG, "SG_LINK_QUEUE_CARRY without packet");
+    // (the record index is a word of the sort's key, and UINT32_MAX is its padding)
+    if (n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one carried call takes");
+  }
+  const bool carry = (c.flags & SG_LINK_QUEUE_CARRY) != 0 && n != 0;  // (no record: nothing to carry)
   if (!dev) {
     const u64 bad = bad_link_off(c.link_off, nl, n);
     if (bad != Q_MAX) throw_bad_off(bad);
@@ -495,60 +805,65 @@ void queue_run(const QueueCall& c) {
   a.wsum = (u64*)out(c.wsum, (size_t)nl * 8);
   a.amax = (uint32_t*)out(c.amax, (size_t)nl * 4);
   const bool want_ahead = (a.ahead || a.amax);
-  if (want_ahead && !a.done) a.done = ctx->q_done.get<u64>(n);
+  if (want_ahead && !a.done && !carry) a.done = ctx->q_done.get<u64>(n);
   a.flag = ctx->q_flag.get<u64>(Q_WORDS);
   SG_HIP(hipMemsetAsync(a.flag, 0xff, Q_WORDS * 8, st));
 
   const bool serial = knob_int("SG_LINK_QUEUE_SERIAL", 0) != 0;
-  hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), dim3(Q_THREADS), 0, st, a);
-  SG_CHECK_LAUNCH();
-  if (n) {
-    TimedLaunch tl(ctx, "link_queue", (double)n);
-    if (serial) {
-      hipLaunchKernelGGL(k_queue_serial, dim3(grid_for(nl, Q_THREADS, 16u * (unsigned)ctx->n_cu)), dim3(Q_THREADS), 0,
-                         st, a);
-      SG_CHECK_LAUNCH();
-    } else {
-      u64* agg = ctx->q_agg.get<u64>(3 * (size_t)n_tiles);
-      a.agg_s = agg;
-      a.agg_m = agg + n_tiles;
-      a.agg_h = (uint32_t*)(agg + 2 * (size_t)n_tiles);
-      hipLaunchKernelGGL(k_queue_agg, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
-      SG_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_queue_carry, dim3(1), dim3(Q_CARRY_THREADS), 0, st, a, n_tiles);
-      SG_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_queue_rescan, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
-      SG_CHECK_LAUNCH();
-    }
-  }
-  if (n && want_ahead) {
-    TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
-    hipLaunchKernelGGL(k_queue_ahead, dim3(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), dim3(Q_THREADS), 0, st, a);
-    SG_CHECK_LAUNCH();
-  }
   // read_timer("link_queue_serial") = (0, 1 when the last call took the lane-per-link form, its records)
   timer_set_counter(ctx, "link_queue_serial", (double)n, serial ? 1u : 0u);
-  u64 h[Q_WORDS];
-  copy_to_host(ctx, h, a.flag, sizeof(h));
-  if (h[Q_BAD_OFF] != Q_MAX) throw_bad_off(h[Q_BAD_OFF]);
-  if (h[Q_BAD_PACKET] != Q_MAX || h[Q_OVERFLOW] != Q_MAX) {
-    const bool pk = h[Q_BAD_PACKET] != Q_MAX;
-    const u64 i = pk ? h[Q_BAD_PACKET] : h[Q_OVERFLOW];
-    // the record's link: link_off is valid, the host's or a copy of the device's
-    std::vector<uint64_t> hoff;
+  if (!serial && n) {
+    u64* agg = ctx->q_agg.get<u64>(3 * (size_t)n_tiles);
+    a.agg_s = agg;
+    a.agg_m = agg + n_tiles;
+    a.agg_h = (uint32_t*)(agg + 2 * (size_t)n_tiles);
+  }
+  // the (link, record in the link) of record i: link_off is valid, the host's or a copy of the device's
+  std::vector<uint64_t> hoff;
+  auto pair_of = [&](u64 i, uint32_t& lk, uint32_t& at) {
     const uint64_t* off = c.link_off;
     if (dev) {
-      hoff.resize((size_t)nl + 1);
-      SG_HIP(hipMemcpy(hoff.data(), c.link_off, hoff.size() * 8, hipMemcpyDeviceToHost));
+      if (hoff.empty()) {
+        hoff.resize((size_t)nl + 1);
+        SG_HIP(hipMemcpy(hoff.data(), c.link_off, hoff.size() * 8, hipMemcpyDeviceToHost));
+      }
       off = hoff.data();
     }
-    const uint32_t lk = (uint32_t)(std::upper_bound(off + 1, off + nl + 1, (uint64_t)i) - off - 1);
-    const uint32_t at = (uint32_t)std::min<uint64_t>(i - off[lk], 0xFFFFFFFFull);
-    if (pk)
-      throw Error(SG_ERR_INVALID_ARG,
-                  "packet[" + std::to_string(i) + "] is not below n_weights (link " + std::to_string(lk) + ")", lk, at);
-    throw Error(SG_ERR_TIME_OVERFLOW,
-                "record " + std::to_string(i) + " of link " + std::to_string(lk) + " is served past 2^64 - 1 ns", lk, at);
+    lk = (uint32_t)(std::upper_bound(off + 1, off + nl + 1, (uint64_t)i) - off - 1);
+    at = (uint32_t)std::min<uint64_t>(i - off[lk], 0xFFFFFFFFull);
+  };
+  auto throw_bad_packet = [&](u64 i) {
+    uint32_t lk, at;
+    pair_of(i, lk, at);
+    throw Error(SG_ERR_INVALID_ARG,
+                "packet[" + std::to_string(i) + "] is not below n_weights (link " + std::to_string(lk) + ")", lk, at);
+  };
+
+  if (carry) {
+    queue_carry(ctx, a, n_tiles, serial, want_ahead, pair_of, throw_bad_packet);
+  } else {
+    hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), dim3(Q_THREADS), 0, st, a);
+    SG_CHECK_LAUNCH();
+    if (n) {
+      TimedLaunch tl(ctx, "link_queue", (double)n);
+      launch_scan(ctx, a, n_tiles, serial);
+    }
+    if (n && want_ahead) {
+      TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+      hipLaunchKernelGGL(k_queue_ahead, dim3(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), dim3(Q_THREADS), 0, st, a);
+      SG_CHECK_LAUNCH();
+    }
+    u64 h[Q_WORDS];
+    copy_to_host(ctx, h, a.flag, sizeof(h));
+    if (h[Q_BAD_OFF] != Q_MAX) throw_bad_off(h[Q_BAD_OFF]);
+    if (h[Q_BAD_PACKET] != Q_MAX) throw_bad_packet(h[Q_BAD_PACKET]);
+    if (h[Q_OVERFLOW] != Q_MAX) {
+      const u64 i = h[Q_OVERFLOW];
+      uint32_t lk, at;
+      pair_of(i, lk, at);
+      throw Error(SG_ERR_TIME_OVERFLOW,
+                  "record " + std::to_string(i) + " of link " + std::to_string(lk) + " is served past 2^64 - 1 ns", lk, at);
+    }
   }
   for (const Back& b : back)
     if (b.bytes) SG_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));

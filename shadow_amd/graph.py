@@ -213,6 +213,37 @@ class LinkQueueResult(NamedTuple):
     link_ahead_max: np.ndarray
 
 
+class LinkQueueCarried(NamedTuple):
+    """What sg_link_queue gives with SG_LINK_QUEUE_CARRY (carry=True): LinkQueueResult's eight
+    fields over the carried schedule, at the input records' indices; enter_ns (u64), the carried
+    enter time of every record, done - service - wait; and the iterations the fixed point took."""
+    wait_ns: np.ndarray
+    done_ns: np.ndarray
+    ahead: np.ndarray
+    link_free: np.ndarray
+    link_busy_ns: np.ndarray
+    link_wait_max_ns: np.ndarray
+    link_wait_sum_ns: np.ndarray
+    link_ahead_max: np.ndarray
+    enter_ns: np.ndarray
+    iterations: int
+
+
+def _carried(ctx: "Context", res: LinkQueueResult, link_off, packet, weight, cost) -> LinkQueueCarried:
+    """The carried result of a call that succeeded: enter' = done - s - wait, exactly (host arrays;
+    s = ceil(weight cost / 1000) is below 2^64 here, since every done is)."""
+    off = np.asarray(link_off).astype(np.int64)
+    n = len(res.done_ns)
+    per = np.repeat(np.asarray(cost, np.uint64), np.diff(off))
+    w = np.ones(n, np.uint64) if weight is None else np.asarray(weight, np.uint32).astype(np.uint64)[np.asarray(packet).astype(np.int64)]
+    if n == 0 or int(per.max()) < 1 << 32:  # (the product fits 64 bits)
+        prod = w * per
+        s = prod // np.uint64(1000) + (prod % np.uint64(1000) != 0).astype(np.uint64)
+    else:
+        s = np.array([-((-int(a) * int(b)) // 1000) for a, b in zip(w.tolist(), per.tolist())], dtype=np.uint64)
+    return LinkQueueCarried(*res, res.done_ns - s - res.wait_ns, int(ctx.read_timer("link_queue_iters")[1]) if n else 0)
+
+
 def cost_ps_from_bandwidth(bits_per_second, unit_bytes: int = 1):
     """sg_link_queue's cost_ps of a link rate: the picoseconds one weight unit of unit_bytes bytes
     takes at bits_per_second, rounded up (1e9 gives 8,000, 100e9 gives 80).  A sequence of rates
@@ -237,14 +268,22 @@ def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
     return a
 
 
-def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None) -> LinkQueueResult:
+def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False):
     """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
     records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
     arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
     cost_ps: picoseconds of service per weight unit, one value or one per link
     (cost_ps_from_bandwidth); free_ns: when each link's server is free (None: 0).  A record starts
     at max(enter, the link's previous done), takes ceil(weight cost_ps / 1000) ns and waits start -
-    enter.  First order: a wait is not carried to the packet's later hops (sg_link_queue)."""
+    enter.  First order, a LinkQueueResult: a wait is not carried to the packet's later hops
+    (sg_link_queue).
+    carry=True: every wait is carried (SG_LINK_QUEUE_CARRY), a LinkQueueCarried.  packet is then
+    required, and without weight the packets number max(packet) + 1.  The records of one packet,
+    in ascending enter_ns, are its chain; a record enters at the previous one's done plus the
+    input's gap between the two, and every link serves in ascending (carried enter, packet)
+    order.  Results stay at the input records' indices."""
+    if carry and packet is None:
+        raise ValueError("packet: required with carry=True")
     off = np.ascontiguousarray(link_off, dtype=np.uint64)
     n_links = len(off) - 1
     if n_links < 0:
@@ -261,20 +300,26 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
                           np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64),
                           np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint32))
     ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    n_weights = 0 if wt is None else len(wt)
+    if carry and wt is None:
+        n_weights = int(pkt.max()) + 1 if n else 0
     check(ctx.handle, load().sg_link_queue(
-        ctx.handle, 0, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)), ptr(pkt), ptr(wt), 0 if wt is None else len(wt), ptr(cost),
+        ctx.handle, _capi.SG_LINK_QUEUE_CARRY if carry else 0, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)),
+        ptr(pkt if n or pkt is None else np.zeros(1, np.uint32)), ptr(wt), n_weights, ptr(cost),
         ptr(free), *[ptr(a) for a in res]))
-    return res
+    return _carried(ctx, res, off, pkt, wt, cost) if carry else res
 
 
 def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
-                        free_ns) -> LinkQueueResult:
+                        free_ns, carry: bool = False, n_packets: int = 0):
     """sg_link_queue on a device trace (torch tensors on `dev`: off, enter, packet; weight or
-    None), every output taken and copied to the host."""
+    None), every output taken and copied to the host.  carry: with SG_LINK_QUEUE_CARRY, a
+    LinkQueueCarried; n_packets bounds the packet numbers when there is no weight."""
     import torch
 
     up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)  # noqa: E731
-    cost = up(_per_link_u64(cost_ps, n_links, "cost_ps"))
+    h_cost = _per_link_u64(cost_ps, n_links, "cost_ps")
+    cost = up(h_cost)
     free = None if free_ns is None else up(_per_link_u64(free_ns, n_links, "free_ns"))
     rec = lambda dt: torch.zeros(max(n_records, 1), dtype=dt, device=dev)  # noqa: E731
     lnk = lambda dt: torch.zeros(max(n_links, 1), dtype=dt, device=dev)  # noqa: E731
@@ -283,12 +328,17 @@ def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, 
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     torch.cuda.synchronize(dev)
     check(ctx.handle, load().sg_link_queue(
-        ctx.handle, _capi.SG_ROUTE_OUT_DEVICE, n_links, ptr(off), n_records, ptr(enter),
-        None if weight is None else ptr(packet), ptr(weight), 0 if weight is None else weight.numel(), ptr(cost),
+        ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0), n_links, ptr(off), n_records,
+        ptr(enter), None if weight is None and not carry else ptr(packet), ptr(weight),
+        (n_packets if carry else 0) if weight is None else weight.numel(), ptr(cost),
         ptr(free), *[ptr(t) for t in outs]))
     lens = [n_records] * 3 + [n_links] * 5
     dts = [np.uint64, np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32]
-    return LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
+    res = LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
+    if not carry:
+        return res
+    return _carried(ctx, res, off.cpu().numpy().view(np.uint64), packet[:n_records].cpu().numpy().view(np.uint32),
+                    None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost)
 
 
 class PathTree:
@@ -593,14 +643,19 @@ class PathTree:
             int(bin_ns), int(n_bins), series.ctypes.data, outside.ctypes.data))
         return series, outside
 
-    def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None):
+    def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
+                         carry=False):
         """The link trace of one round's batch and the FIFO queue of every link under a link rate,
         (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
         gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
         between the two calls (sg_link_trace_packets, then sg_link_queue).  weight as in
         link_load_round: None (every crossing weighs 1), "payload" or a u32 array per packet;
         cost_ps and free_ns as in shadow_amd.link_queue; hosts, packets, status and watch as in
-        link_trace_round.  First order: a crossing's wait is not added to the packet's later hops."""
+        link_trace_round.  First order: a crossing's wait is not added to the packet's later hops.
+        carry=True: it is (SG_LINK_QUEUE_CARRY).  queue is then a LinkQueueCarried, and a seventh
+        entry follows it: the carried exit_ns per record, exit_ns + (done_ns - enter_ns), when the
+        crossing leaves its link under the rates; a packet's last hop's value is its arrival.  An
+        unwatched link is crossed at its latency, as a link of infinite rate."""
         import torch
 
         npk = len(packets)
@@ -657,10 +712,11 @@ class PathTree:
             if rc != _capi.SG_ERR_CAPACITY or t <= cap:
                 break
             cap = t
-        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns)
-        return (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32),
-                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
-                leave[:t].cpu().numpy().view(np.uint64), queue)
+        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk)
+        out = (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32),
+               hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
+               leave[:t].cpu().numpy().view(np.uint64), queue)
+        return out + (out[4] + (queue.done_ns - out[3]),) if carry else out
 
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
@@ -1035,7 +1091,7 @@ class NetworkGraph:
     def link_queue_device(self, link_off_ptr: int, n_records: int, enter_ptr: int, packet_ptr: int, weight_ptr: int,
                           n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
                           ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
-                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0) -> None:
+                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False) -> None:
         """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
         device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
         packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
@@ -1043,10 +1099,12 @@ class NetworkGraph:
         cost (device u64 per link, picoseconds per weight unit); free_in (device u64 per link, 0:
         all zero).  Outputs, any of them 0 but not all: per record wait u64, done u64, ahead u32;
         per link link_free u64 (not free_in's array), busy u64, wait_max u64, wait_sum u64,
-        ahead_max u32 (sg_link_queue)."""
+        ahead_max u32 (sg_link_queue).  carry: every wait is carried to the packet's later hops
+        (SG_LINK_QUEUE_CARRY: packet is required and n_weights bounds it); the call then
+        synchronises once per iteration, read_timer("link_queue_iters") tells how many it took."""
         vp = lambda x: C.c_void_p(x or None)  # noqa: E731
         check(self.ctx.handle, load().sg_link_queue(
-            self.ctx.handle, _capi.SG_ROUTE_OUT_DEVICE, len(self.links()[0]), vp(link_off_ptr), int(n_records),
+            self.ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0), len(self.links()[0]), vp(link_off_ptr), int(n_records),
             vp(enter_ptr), vp(packet_ptr), vp(weight_ptr), int(n_weights), vp(cost_ptr), vp(free_in_ptr), vp(wait_ptr),
             vp(done_ptr), vp(ahead_ptr), vp(link_free_ptr), vp(busy_ptr), vp(wait_max_ptr), vp(wait_sum_ptr),
             vp(ahead_max_ptr)))

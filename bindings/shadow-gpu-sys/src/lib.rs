@@ -373,6 +373,8 @@ pub const SG_ROUTE_SHORTEST_PATH: u32 = 1;
 pub const SG_ROUTE_OUT_DEVICE: u32 = 2;
 /// sg_link_queue: carry each wait to the packet's later hops
 pub const SG_LINK_QUEUE_CARRY: u32 = 4;
+/// sg_link_queue: cost_ps carries a longest wait per link in its second half; tail drop
+pub const SG_LINK_QUEUE_DROP: u32 = 8;
 pub const SG_CELL_WIDE: u32 = 0xFFFF_FFFF;
 pub const SG_COMM_ID_BYTES: usize = 128;
 

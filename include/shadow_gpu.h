@@ -864,8 +864,53 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  * Timers with the flag: "link_queue_index" (the chains), "link_queue_sort",
  * "link_queue" (the scan), "link_queue_carry" (the propagate step),
  * "link_queue_ahead"; read_timer("link_queue_iters") gives the iterations of the
- * last carried call. */
+ * last carried call.
+ *
+ * SG_LINK_QUEUE_DROP in flags: every link has a finite buffer and drops at its tail.
+ * Without the flag the call is what it was, bit for bit, with the same launches.
+ * Inputs.  cost_ps has 2 * n_links entries: limit_ns[L] = cost_ps[n_links + L] is the
+ * longest wait link L's buffer holds, the unfinished work a record may find, measured
+ * in service time.  2^64 - 1: no limit; 0: a record is dropped whenever it would wait
+ * at all.  With byte weights a buffer of B bytes in front of the server is
+ * min(ceil(B * cost_ps[L] / 1000), 2^64 - 1).  In host mode 2 * n_links entries are
+ * staged.
+ * Each link's queue, in the order served (the order given; with SG_LINK_QUEUE_CARRY
+ * ascending (enter', packet) over the records that arrive), `done` starting at
+ * link_free_in[L]:
+ *   start_i = max(enter_i, done)
+ *   start_i - enter_i > limit_ns[L]:  record i is DROPPED, done is unchanged
+ *   otherwise record i is SERVED:     done = min(start_i + s_i, 2^64 - 1) -> done_i,
+ *                                     wait_i = start_i - enter_i
+ * with s_i exactly the value above.  ahead_i counts served records only: the earlier
+ * served records of the link's order with done_j > enter_i.
+ * With SG_LINK_QUEUE_CARRY the chain successor of a dropped or absent record is
+ * ABSENT: it enters no queue.  Apart from that the equations are the carried ones,
+ * and the result is what an event-driven simulation in global (time, packet) order
+ * yields.
+ * Outputs.  There is no new array: a record's state is read from values a served
+ * record cannot produce.
+ *   state     out_wait_ns   out_done_ns               out_ahead
+ *   served    as above      as above                  as above (served only)
+ *   dropped   2^64 - 1      its (carried) enter time  the served records it found
+ *   absent    2^64 - 1      2^64 - 1                  0
+ * out_link_free[L] is the done of the record served last, link_free_in[L] when none
+ * was served.  Busy, wait max, wait sum and ahead max run over served records only.
+ * out_link_ahead_max then has 2 * n_links entries: [n_links + L] is the number of
+ * records dropped on L (u32).  out_link_busy_ns then has 2 * n_links entries:
+ * [n_links + L] is the sum of s_i over the records dropped on L (wraps).  Absent
+ * records count nowhere; an empty link has 0 in both second halves.
+ * With every limit 2^64 - 1 the flagged call equals the unflagged one in every
+ * first-half output, with or without SG_LINK_QUEUE_CARRY, and the second halves are 0.
+ * The carried enter time of a served record is done_i - s_i - wait_i, of a dropped
+ * record out_done_ns[i], of an absent record 2^64 - 1.
+ * Errors with the flag are unchanged in kind and order, and n_records > 2^32 - 2 is
+ * SG_ERR_CAPACITY, every output untouched.  SG_ERR_TIME_OVERFLOW is raised by served
+ * records only: a served done, or with SG_LINK_QUEUE_CARRY done + gap, reaching
+ * 2^64 - 1; a dropped record never overflows.  SG_LINK_QUEUE_CARRY_ITERS bounds the
+ * iterations as above.
+ * Timers with the flag: "link_queue" (the walk), "link_queue_ahead" (the outputs). */
 #define SG_LINK_QUEUE_CARRY 0x4u
+#define SG_LINK_QUEUE_DROP 0x8u
 int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
                       const uint64_t* link_off, uint64_t n_records,
                       const uint64_t* enter_ns, const uint32_t* packet,

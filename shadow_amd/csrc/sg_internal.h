@@ -139,6 +139,10 @@ struct sg_ctx {
   // gap, the carried enter times, and a link-sorted pass: enter, packet, the permutation, done,
   // wait, ahead
   sg::DevBuf qc_cnt, qc_off, qc_list, qc_next, qc_gap, qc_cur, qc_enter, qc_packet, qc_perm, qc_done, qc_wait, qc_ahead;
+  // finite buffers (SG_LINK_QUEUE_DROP; p_sums through scan_counts): the period heads and then
+  // the served marks, their exclusive sums, the period starts, the long periods with their
+  // counter, and per record the running done and the wait; the carried form's sorted done
+  sg::DevBuf qd_mark, qd_pos, qd_start, qd_long, qd_run, qd_wait, qd_done;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

@@ -37,6 +37,10 @@
 // SG_LINK_QUEUE_CARRY carries every wait to the packet's later hops: a fixed point over the same
 // scan, with every link sorted anew by the carried times in each iteration ("the carried form",
 // below queue_run's helpers).
+//
+// SG_LINK_QUEUE_DROP gives every link a finite buffer and drops at its tail: the unlimited scan
+// above only marks the busy periods, which are then walked from an idle server side by side
+// ("finite buffers", below k_queue_ahead).
 #include <algorithm>
 #include <functional>
 #include <string>
@@ -407,6 +411,300 @@ __global__ void __launch_bounds__(Q_THREADS) k_queue_ahead(const QArgs a) {
   if (key != Q_NO_LINK && (lane == 0 || below != key) && m) atomicMax(&a.amax[key], m);
 }
 
+// ---- finite buffers (SG_LINK_QUEUE_DROP): tail drop under a longest wait per link.
+//
+// The limited recurrence -- start = max(enter, done); start - enter > limit: dropped, done as it
+// was; else done = start + s -- is no constant-size scan (the map of one record is not closed
+// under composition), but its `done` never exceeds the unlimited queue's.  A record the unlimited
+// scan serves without waiting therefore finds the limited server idle too: the limited queue
+// restarts there, and a link's records fall into independent busy periods.
+//   agg, carry       the unlimited scan's first two launches, as above;
+//   k_drop_heads     the tile again with its carry: mark[i] = 1 where the unlimited wait is 0 or a
+//                    segment starts.  No caller output, no overflow flag (the pass may saturate);
+//   scan_counts      the marks' exclusive sums, and k_drop_starts: the period starts, compacted;
+//   k_drop_lane      a lane per period: one of at most D_SHORT records is walked by its lane,
+//                    a longer one is appended to the list of long periods;
+//   k_drop_wave      a wave per long period: 64 records per coalesced load (the next 64 in flight
+//                    meanwhile), the scalar `done` stepped through them by lane reads of a uniform
+//                    lane; every lane keeps the `done` before its record and finishes it alone.
+// A walk leaves per record wt (the wait; all ones: not served), run (the `done` after it: it never
+// falls within a segment, a dropped record repeats the value before it) and mark (1: served).
+// SG_LINK_QUEUE_SERIAL = 1: k_drop_serial, a lane per link, leaves the same three arrays.
+//   k_drop_finish    a lane per record: the caller's wait, done and ahead (one binary search over
+//                    run, then a difference of the served marks' exclusive sums), out_link_free,
+//                    and the per-link sums by the wave reduction of k_queue_ahead.
+// Carried (d.absent): a record whose enter time is all ones is absent: it sorts last on its link,
+// is a period of its own in the unlimited pass, and is skipped by every walk.
+constexpr uint32_t D_SHORT = 32;  // the longest period a lane walks
+
+struct DArgs {
+  QArgs q;           // the inputs, agg_*, flag; wait / done / ahead and the per-link arrays: k_drop_finish's
+  const u64* limit;  // cost + n_links
+  uint32_t absent;   // carried: enter == MAX is an absent record
+  uint32_t lng_cap;
+  uint32_t* mark;  // the period heads, then the served records
+  u64* pos;        // n + 2: the exclusive sums of mark, the total twice
+  uint32_t* start;  // the period starts
+  uint32_t* lng;    // the long periods, in any order
+  uint32_t* n_long;
+  u64* run;
+  u64* wt;
+  uint32_t* drops;  // the second halves of out_link_ahead_max and out_link_busy_ns, or null
+  u64* refused;
+};
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_links(const DArgs d) {
+  const u64 q = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (q >= d.q.n_links) return;
+  if (d.drops) d.drops[q] = 0u;
+  if (d.refused) d.refused[q] = 0ull;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_heads(const DArgs d) {
+  __shared__ QElem s_wave[16];
+  const QArgs& a = d.q;
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const u64 base = (u64)blockIdx.x * Q_TILE + (u64)threadIdx.x * Q_PER;
+  QLane r;
+  const QElem x = lane_load<false>(a, base, r);
+  QElem total;
+  const QElem ex = block_exclusive_op(x, q_identity(), s_wave, &total, QOp());
+  u64 done = ex.head ? ex.m : max(sat_add(a.agg_m[blockIdx.x], ex.s), ex.m);
+#pragma unroll
+  for (uint32_t k = 0; k < Q_PER; k++) {
+    if (k >= r.count) continue;
+    const bool head = (r.head >> k) & 1u;
+    if (head) done = a.free_in ? a.free_in[r.link[k]] : 0ull;
+    d.mark[base + k] = head || r.e[k] >= done ? 1u : 0u;
+    done = sat_add(max(r.e[k], done), r.s[k]);
+  }
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_starts(const DArgs d) {
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (i >= d.q.n || d.q.flag[Q_BAD_OFF] != Q_MAX) return;
+  if (!d.mark[i]) return;
+  const u64 at = d.pos[i];
+  if (at < d.q.n) d.start[at] = (uint32_t)i;
+}
+
+// One record under the drop rule: the wait (all ones: not served) and the new `done`.
+__device__ __forceinline__ u64 drop_step(u64& done, u64 e, u64 s, u64 lim, bool absent) {
+  if (absent && e == Q_MAX) return Q_MAX;
+  const u64 start = max(e, done), w = start - e;
+  if (w > lim) return Q_MAX;
+  done = sat_add(start, s);
+  return w;
+}
+
+// Records [i0, i1) of link lk, one after the other.
+template <bool FLAG>
+__device__ __forceinline__ void drop_walk(const DArgs& d, uint32_t lk, u64 i0, u64 i1, u64 done) {
+  const QArgs& a = d.q;
+  const u64 cost = a.cost[lk], lim = d.limit[lk];
+  for (u64 i = i0; i < i1; i++) {
+    const u64 s = service_ns(record_weight(a, i, FLAG), cost), e = a.enter[i];
+    const u64 w = drop_step(done, e, s, lim, d.absent != 0u);
+    if (w != Q_MAX && done == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], i);
+    d.wt[i] = w;
+    d.run[i] = done;
+    d.mark[i] = w != Q_MAX ? 1u : 0u;
+  }
+}
+
+// Period p's records [i0, i1) and link, and the `done` it starts from: the link's free_in at a
+// segment's first record, else the head's own enter time (the server is idle there).  False: not
+// a period of a valid compaction.
+__device__ __forceinline__ bool drop_period(const DArgs& d, u64 p, u64 np, u64& i0, u64& i1, uint32_t& lk, u64& done) {
+  const QArgs& a = d.q;
+  i0 = d.start[p];
+  i1 = p + 1 < np ? (u64)d.start[p + 1] : a.n;
+  if (i0 >= i1 || i1 > a.n) return false;
+  lk = link_of(a.off, a.n_links, i0);
+  if (i1 > a.off[lk + 1]) return false;
+  done = i0 == a.off[lk] ? (a.free_in ? a.free_in[lk] : 0ull) : a.enter[i0];
+  return true;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_lane(const DArgs d) {
+  const QArgs& a = d.q;
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const u64 p = (u64)blockIdx.x * Q_THREADS + threadIdx.x, np = min(d.pos[a.n], a.n);
+  if (p >= np) return;
+  u64 i0, i1, done;
+  uint32_t lk;
+  if (!drop_period(d, p, np, i0, i1, lk, done)) return;
+  if (i1 - i0 > D_SHORT) {
+    const uint32_t slot = atomicAdd(d.n_long, 1u);
+    if (slot < d.lng_cap) d.lng[slot] = (uint32_t)p;
+    return;
+  }
+  drop_walk<false>(d, lk, i0, i1, done);
+}
+
+__device__ __forceinline__ u64 uniform64(u64 v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((u64)hi << 32) | lo;
+}
+
+__device__ __forceinline__ u64 lane_read64(u64 v, uint32_t k) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)k);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)k);
+  return ((u64)hi << 32) | lo;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_wave(const DArgs d) {
+  const QArgs& a = d.q;
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const uint32_t lane = threadIdx.x & 63u, waves = Q_THREADS / 64u;
+  const uint32_t n_long = min(*d.n_long, d.lng_cap);
+  const u64 np = min(d.pos[a.n], a.n);
+  const bool absent = d.absent != 0u;
+  for (uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * waves + (threadIdx.x >> 6))); w < n_long;
+       w += gridDim.x * waves) {
+    const u64 p = d.lng[w];
+    if (p >= np) continue;
+    u64 i0, i1, done;
+    uint32_t lk;
+    if (!drop_period(d, p, np, i0, i1, lk, done)) continue;
+    i0 = uniform64(i0);
+    i1 = uniform64(i1);
+    done = uniform64(done);
+    lk = (uint32_t)__builtin_amdgcn_readfirstlane((int)lk);
+    // (in scalar registers before the first load below is issued: the stepping loop waits for no memory)
+    const u64 cost = uniform64(a.cost[lk]), lim = uniform64(d.limit[lk]);
+    u64 e = 0ull, s = 0ull;
+    if (i0 + lane < i1) {
+      e = a.enter[i0 + lane];
+      s = service_ns(record_weight(a, i0 + lane, false), cost);
+    }
+    for (u64 b = i0; b < i1; b += 64ull) {
+      // the next 64 records, in flight while these are stepped through
+      u64 e2 = 0ull, s2 = 0ull;
+      if (b + 64ull + lane < i1) {
+        e2 = a.enter[b + 64ull + lane];
+        s2 = service_ns(record_weight(a, b + 64ull + lane, false), cost);
+      }
+      const uint32_t cnt = (uint32_t)min((u64)64ull, i1 - b);
+      u64 before = 0ull;
+      for (uint32_t k = 0; k < cnt; k++) {
+        const u64 ek = lane_read64(e, k), sk = lane_read64(s, k);
+        if (lane == k) before = done;
+        drop_step(done, ek, sk, lim, absent);
+      }
+      if (lane < cnt) {
+        const u64 i = b + lane;
+        const u64 wt = drop_step(before, e, s, lim, absent);
+        if (wt != Q_MAX && before == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], i);
+        d.wt[i] = wt;
+        d.run[i] = before;
+        d.mark[i] = wt != Q_MAX ? 1u : 0u;
+      }
+      e = e2;
+      s = s2;
+    }
+  }
+}
+
+// ---- the lane-per-link form under the drop rule
+__global__ void __launch_bounds__(Q_THREADS) k_drop_serial(const DArgs d) {
+  const QArgs& a = d.q;
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const u64 stride = (u64)gridDim.x * Q_THREADS;
+  for (u64 q = (u64)blockIdx.x * Q_THREADS + threadIdx.x; q < a.n_links; q += stride) {
+    const uint32_t lk = (uint32_t)q;
+    drop_walk<true>(d, lk, a.off[lk], a.off[lk + 1], a.free_in ? a.free_in[lk] : 0ull);
+  }
+}
+
+// A wave's segmented reduction of x by f over runs of equal keys in consecutive lanes; the first
+// lane of a run holds the run's value.  Every lane calls.
+template <class T, class F>
+__device__ __forceinline__ T wave_run_reduce(uint32_t key, T x, F f) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t k2 = __shfl_down(key, d, 64);
+    const T y = __shfl_down(x, d, 64);
+    if (lane + d < 64 && k2 == key) x = f(x, y);
+  }
+  return x;
+}
+
+__global__ void __launch_bounds__(Q_THREADS) k_drop_finish(const DArgs d, uint32_t want_ahead) {
+  const QArgs& a = d.q;
+  if (a.flag[Q_BAD_OFF] != Q_MAX) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const u64 i = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  uint32_t key = Q_NO_LINK, ahead = 0u, drops = 0u;
+  u64 busy = 0ull, wmax = 0ull, wsum = 0ull, refused = 0ull;
+  if (i < a.n) {
+    key = link_of(a.off, a.n_links, i);
+    const u64 i0 = a.off[key], i1 = a.off[key + 1];
+    const u64 e = a.enter[i], w = d.wt[i], r = d.run[i];
+    const bool absent = d.absent && e == Q_MAX, served = w != Q_MAX;
+    if (want_ahead && !absent) {
+      u64 lo = i0, hi = i;  // the first j of the prefix with run[j] > e: the served from there on are ahead
+      while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (d.run[mid] > e)
+          hi = mid;
+        else
+          lo = mid + 1;
+      }
+      ahead = (uint32_t)min(d.pos[i] - d.pos[lo], (u64)0xFFFFFFFFull);
+    }
+    if (a.wait) a.wait[i] = w;
+    if (a.done) a.done[i] = served ? r : e;
+    if (a.ahead) a.ahead[i] = ahead;
+    if (a.link_free) {
+      // run after the last record that arrives: the done of the record served last, or free_in
+      if (absent) {
+        if (i == i0) a.link_free[key] = a.free_in ? a.free_in[key] : 0ull;
+      } else if (i + 1 == i1 || (d.absent && a.enter[i + 1] == Q_MAX)) {
+        a.link_free[key] = r;
+      }
+    }
+    if (!absent) {
+      const u64 s = service_ns(record_weight(a, i, false), a.cost[key]);
+      if (served) {
+        busy = s;
+        wmax = wsum = w;
+      } else {
+        refused = s;
+        drops = 1u;
+        ahead = 0u;  // (the maximum runs over served records)
+      }
+    }
+  }
+  if (!a.busy && !a.wmax && !a.wsum && !a.amax) return;  // (the same for every lane)
+  const auto add64 = [](u64 x, u64 y) { return x + y; };
+  const auto max64 = [](u64 x, u64 y) { return max(x, y); };
+  const uint32_t below = __shfl_up(key, 1, 64);
+  const bool first = key != Q_NO_LINK && (lane == 0 || below != key);
+  if (a.busy) {
+    busy = wave_run_reduce(key, busy, add64);
+    refused = wave_run_reduce(key, refused, add64);
+    if (first && busy) atomicAdd(&a.busy[key], busy);
+    if (first && refused) atomicAdd(&d.refused[key], refused);
+  }
+  if (a.wmax) {
+    wmax = wave_run_reduce(key, wmax, max64);
+    if (first && wmax) atomicMax(&a.wmax[key], wmax);
+  }
+  if (a.wsum) {
+    wsum = wave_run_reduce(key, wsum, add64);
+    if (first && wsum) atomicAdd(&a.wsum[key], wsum);
+  }
+  if (a.amax) {
+    ahead = wave_run_reduce(key, ahead, [](uint32_t x, uint32_t y) { return max(x, y); });
+    drops = wave_run_reduce(key, drops, [](uint32_t x, uint32_t y) { return x + y; });
+    if (first && ahead) atomicMax(&a.amax[key], ahead);
+    if (first && drops) atomicAdd(&d.drops[key], drops);
+  }
+}
+
 // the first bad link of a host link_off; all ones when it is good
 u64 bad_link_off(const uint64_t* off, uint32_t n_links, uint64_t n) {
   if (off[0] != 0) return 0;
@@ -437,6 +735,42 @@ void launch_scan(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial) {
     hipLaunchKernelGGL(k_queue_rescan, dim3(n_tiles), dim3(Q_THREADS), 0, st, a);
     SG_CHECK_LAUNCH();
   }
+}
+
+// The walk under the drop rule, in either form: wt, run and the served marks of every record.
+void launch_drop(sg_ctx* ctx, const DArgs& d, uint32_t n_tiles, bool serial) {
+  hipStream_t st = ctx->stream;
+  const QArgs& a = d.q;
+  const dim3 g_rec(grid_for(a.n, Q_THREADS, 0x7FFFFFFFu)), blk(Q_THREADS);
+  if (serial) {
+    hipLaunchKernelGGL(k_drop_serial, dim3(grid_for(a.n_links, Q_THREADS, 16u * (unsigned)ctx->n_cu)), blk, 0, st, d);
+    SG_CHECK_LAUNCH();
+    return;
+  }
+  hipLaunchKernelGGL(k_queue_agg, dim3(n_tiles), blk, 0, st, a);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_queue_carry, dim3(1), dim3(Q_CARRY_THREADS), 0, st, a, n_tiles);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_drop_heads, dim3(n_tiles), blk, 0, st, d);
+  SG_CHECK_LAUNCH();
+  scan_counts(ctx, d.mark, (uint32_t)a.n, d.pos, d.pos + a.n + 1);
+  SG_HIP(hipMemsetAsync(d.n_long, 0, 4, st));
+  hipLaunchKernelGGL(k_drop_starts, g_rec, blk, 0, st, d);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_drop_lane, g_rec, blk, 0, st, d);
+  SG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_drop_wave, dim3(grid_for(d.lng_cap, Q_THREADS / 64u, 8u * (unsigned)ctx->n_cu)), blk, 0, st, d);
+  SG_CHECK_LAUNCH();
+}
+
+// Every output the caller takes, from a walk's three arrays.
+void launch_drop_finish(sg_ctx* ctx, const DArgs& d, bool want_ahead) {
+  hipStream_t st = ctx->stream;
+  const QArgs& a = d.q;
+  if (want_ahead) scan_counts(ctx, d.mark, (uint32_t)a.n, d.pos, d.pos + a.n + 1);
+  hipLaunchKernelGGL(k_drop_finish, dim3(grid_for(a.n, Q_THREADS, 0x7FFFFFFFu)), dim3(Q_THREADS), 0, st, d,
+                     want_ahead ? 1u : 0u);
+  SG_CHECK_LAUNCH();
 }
 
 // ---- the carried form (SG_LINK_QUEUE_CARRY): a wait moves the packet's later hops.
@@ -549,6 +883,26 @@ __global__ void __launch_bounds__(Q_THREADS) k_carry_propagate(const CArgs c) {
   }
 }
 
+// The same under SG_LINK_QUEUE_DROP: the successor of a record that is not served (wt all ones:
+// dropped or absent) is absent, cur = MAX; only a served record can carry past 2^64 - 1.
+__global__ void __launch_bounds__(Q_THREADS) k_carry_propagate_drop(const CArgs c, const u64* wt) {
+  const u64 j = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
+  if (j >= c.n) return;
+  const uint32_t i = c.perm[j];
+  if (i >= c.n) return;
+  const uint32_t nx = c.next[i];
+  if (nx == Q_NO_NEXT) return;
+  u64 v = Q_MAX;
+  if (wt[j] != Q_MAX) {
+    v = sat_add(c.s_done[j], c.gap[i]);
+    if (v == Q_MAX) atomicMin(&c.flag[Q_OVERFLOW], j);
+  }
+  if (v != c.cur[nx]) {
+    c.cur[nx] = v;
+    c.flag[Q_CHANGED] = 0ull;
+  }
+}
+
 __global__ void __launch_bounds__(Q_THREADS) k_carry_scatter(const CArgs c, u64* wait, u64* done, uint32_t* ahead) {
   const u64 j = (u64)blockIdx.x * Q_THREADS + threadIdx.x;
   if (j >= c.n) return;
@@ -576,8 +930,9 @@ void set_iters(sg_ctx* ctx, u64 n, uint32_t iters) {
 }
 
 // `a`: the call's arrays on the device (n > 0 records, agg_* set for the scan form, flag words all ones).
+// `drop`: the call's DArgs under SG_LINK_QUEUE_DROP (its scratch arrays set), else null.
 void queue_carry(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial, bool want_ahead, const PairOf& pair_of,
-                 const std::function<void(u64)>& throw_bad_packet) {
+                 const std::function<void(u64)>& throw_bad_packet, const DArgs* drop) {
   hipStream_t st = ctx->stream;
   const u64 n = a.n;
   const uint32_t nl = a.n_links, np = a.n_weights;
@@ -657,6 +1012,14 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial, boo
   s.done = c.s_done;
   s.ahead = nullptr;
   const TraceOut sorted = {s_packet, perm, s_enter, nullptr};
+  // under the drop rule a walk's `run` is the sorted pass's done
+  DArgs ds = {};
+  if (drop) {
+    ds = *drop;
+    ds.q = s;
+    ds.absent = 1u;
+    ds.run = c.s_done;
+  }
   uint32_t iters = 0;
   bool settled = false;
   while (!settled && iters < (uint32_t)cap) {
@@ -671,11 +1034,17 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial, boo
     }
     {
       TimedLaunch tl(ctx, "link_queue", (double)n);
-      launch_scan(ctx, s, n_tiles, serial);
+      if (drop)
+        launch_drop(ctx, ds, n_tiles, serial);
+      else
+        launch_scan(ctx, s, n_tiles, serial);
     }
     {
       TimedLaunch tl(ctx, "link_queue_carry", (double)n);
-      hipLaunchKernelGGL(k_carry_propagate, g_rec, blk, 0, st, c);
+      if (drop)
+        hipLaunchKernelGGL(k_carry_propagate_drop, g_rec, blk, 0, st, c, (const u64*)ds.wt);
+      else
+        hipLaunchKernelGGL(k_carry_propagate, g_rec, blk, 0, st, c);
       SG_CHECK_LAUNCH();
     }
     copy_to_host(ctx, h, a.flag, sizeof(h));
@@ -703,14 +1072,26 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, uint32_t n_tiles, bool serial, boo
   s.amax = a.amax;
   hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), blk, 0, st, s);
   SG_CHECK_LAUNCH();
-  {
-    TimedLaunch tl(ctx, "link_queue", (double)n);
-    launch_scan(ctx, s, n_tiles, serial);
-  }
-  if (want_ahead) {
-    TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
-    hipLaunchKernelGGL(k_queue_ahead, g_rec, blk, 0, st, s);
+  if (drop) {
+    // (k_drop_finish reads run while it writes done: the sorted done of the last pass has an array of its own)
+    s.done = a.done ? ctx->qd_done.get<u64>(n) : nullptr;
+    c.s_done = s.done;
+    ds.q = s;
+    hipLaunchKernelGGL(k_drop_links, dim3(grid_for(nl, Q_THREADS)), blk, 0, st, ds);
     SG_CHECK_LAUNCH();
+    // (no time moved: the last iteration's walk is this order's, wt, run and the marks stand)
+    TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+    launch_drop_finish(ctx, ds, want_ahead);
+  } else {
+    {
+      TimedLaunch tl(ctx, "link_queue", (double)n);
+      launch_scan(ctx, s, n_tiles, serial);
+    }
+    if (want_ahead) {
+      TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+      hipLaunchKernelGGL(k_queue_ahead, g_rec, blk, 0, st, s);
+      SG_CHECK_LAUNCH();
+    }
   }
   if (a.wait || a.done || a.ahead) {
     hipLaunchKernelGGL(k_carry_scatter, g_rec, blk, 0, st, c, a.wait, a.done, a.ahead);
@@ -755,6 +1136,10 @@ void queue_run(const QueueCall& c) {
     if (n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one carried call takes");
   }
   const bool carry = (c.flags & SG_LINK_QUEUE_CARRY) != 0 && n != 0;  // (no record: nothing to carry)
+  const bool drop = (c.flags & SG_LINK_QUEUE_DROP) != 0;
+  // (the period starts are u32 record indices, and the marks are summed by scan_counts)
+  if (drop && n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one call with SG_LINK_QUEUE_DROP takes");
+  const size_t nl2 = drop ? 2 * (size_t)nl : (size_t)nl;  // cost_ps, out_link_busy_ns, out_link_ahead_max
   if (!dev) {
     const u64 bad = bad_link_off(c.link_off, nl, n);
     if (bad != Q_MAX) throw_bad_off(bad);
@@ -794,18 +1179,18 @@ void queue_run(const QueueCall& c) {
   a.enter = (const u64*)in(c.enter, n * 8);
   a.packet = (const uint32_t*)in(c.packet, n * 4);
   a.weight = (const uint32_t*)in(c.weight, (size_t)c.n_weights * 4);
-  a.cost = (const u64*)in(c.cost, (size_t)nl * 8);
+  a.cost = (const u64*)in(c.cost, nl2 * 8);
   a.free_in = (const u64*)in(c.free_in, (size_t)nl * 8);
   a.wait = (u64*)out(c.wait, n * 8);
   a.done = (u64*)out(c.done, n * 8);
   a.ahead = (uint32_t*)out(c.ahead, n * 4);
   a.link_free = (u64*)out(c.link_free, (size_t)nl * 8);
-  a.busy = (u64*)out(c.busy, (size_t)nl * 8);
+  a.busy = (u64*)out(c.busy, nl2 * 8);
   a.wmax = (u64*)out(c.wmax, (size_t)nl * 8);
   a.wsum = (u64*)out(c.wsum, (size_t)nl * 8);
-  a.amax = (uint32_t*)out(c.amax, (size_t)nl * 4);
+  a.amax = (uint32_t*)out(c.amax, nl2 * 4);
   const bool want_ahead = (a.ahead || a.amax);
-  if (want_ahead && !a.done && !carry) a.done = ctx->q_done.get<u64>(n);
+  if (want_ahead && !a.done && !carry && !drop) a.done = ctx->q_done.get<u64>(n);
   a.flag = ctx->q_flag.get<u64>(Q_WORDS);
   SG_HIP(hipMemsetAsync(a.flag, 0xff, Q_WORDS * 8, st));
 
@@ -839,16 +1224,45 @@ void queue_run(const QueueCall& c) {
                 "packet[" + std::to_string(i) + "] is not below n_weights (link " + std::to_string(lk) + ")", lk, at);
   };
 
+  DArgs d = {};
+  if (drop) {
+    d.q = a;
+    d.limit = a.cost + nl;
+    d.drops = a.amax ? a.amax + nl : nullptr;
+    d.refused = a.busy ? a.busy + nl : nullptr;
+    if (n) {
+      d.lng_cap = (uint32_t)(n / (D_SHORT + 1u) + 1u);
+      d.mark = ctx->qd_mark.get<uint32_t>(n);
+      d.pos = ctx->qd_pos.get<u64>((size_t)n + 2);
+      d.start = ctx->qd_start.get<uint32_t>(n);
+      d.lng = ctx->qd_long.get<uint32_t>((size_t)d.lng_cap + 1);
+      d.n_long = d.lng + d.lng_cap;
+      d.run = ctx->qd_run.get<u64>(n);
+      d.wt = ctx->qd_wait.get<u64>(n);
+    }
+  }
+
   if (carry) {
-    queue_carry(ctx, a, n_tiles, serial, want_ahead, pair_of, throw_bad_packet);
+    queue_carry(ctx, a, n_tiles, serial, want_ahead, pair_of, throw_bad_packet, drop ? &d : nullptr);
   } else {
     hipLaunchKernelGGL(k_queue_links, dim3(grid_for((size_t)nl + 1, Q_THREADS)), dim3(Q_THREADS), 0, st, a);
     SG_CHECK_LAUNCH();
-    if (n) {
+    if (drop) {
+      hipLaunchKernelGGL(k_drop_links, dim3(grid_for(nl, Q_THREADS)), dim3(Q_THREADS), 0, st, d);
+      SG_CHECK_LAUNCH();
+    }
+    if (n && drop) {
+      {
+        TimedLaunch tl(ctx, "link_queue", (double)n);
+        launch_drop(ctx, d, n_tiles, serial);
+      }
+      TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
+      launch_drop_finish(ctx, d, want_ahead);
+    } else if (n) {
       TimedLaunch tl(ctx, "link_queue", (double)n);
       launch_scan(ctx, a, n_tiles, serial);
     }
-    if (n && want_ahead) {
+    if (n && want_ahead && !drop) {
       TimedLaunch tl(ctx, "link_queue_ahead", (double)n);
       hipLaunchKernelGGL(k_queue_ahead, dim3(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), dim3(Q_THREADS), 0, st, a);
       SG_CHECK_LAUNCH();

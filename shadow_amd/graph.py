@@ -229,18 +229,111 @@ class LinkQueueCarried(NamedTuple):
     iterations: int
 
 
-def _carried(ctx: "Context", res: LinkQueueResult, link_off, packet, weight, cost) -> LinkQueueCarried:
-    """The carried result of a call that succeeded: enter' = done - s - wait, exactly (host arrays;
-    s = ceil(weight cost / 1000) is below 2^64 here, since every done is)."""
+class LinkQueueDropped(NamedTuple):
+    """What sg_link_queue gives with SG_LINK_QUEUE_DROP (limit_ns=...): LinkQueueResult's eight
+    fields, the per-link arrays cut back to n_links entries and running over served records only;
+    dropped (bool per record: wait_ns is then 2^64 - 1 and done_ns its enter time); per link
+    link_drops (u32, the records dropped) and link_refused_ns (u64, their summed service)."""
+    wait_ns: np.ndarray
+    done_ns: np.ndarray
+    ahead: np.ndarray
+    link_free: np.ndarray
+    link_busy_ns: np.ndarray
+    link_wait_max_ns: np.ndarray
+    link_wait_sum_ns: np.ndarray
+    link_ahead_max: np.ndarray
+    dropped: np.ndarray
+    link_drops: np.ndarray
+    link_refused_ns: np.ndarray
+
+
+class LinkQueueCarriedDropped(NamedTuple):
+    """What sg_link_queue gives with SG_LINK_QUEUE_CARRY and SG_LINK_QUEUE_DROP: LinkQueueDropped's
+    fields over the carried schedule; absent (bool per record: a record after a dropped or absent
+    one in its packet's chain, it enters no queue, wait_ns and done_ns are 2^64 - 1); enter_ns, the
+    carried enter time (done - service - wait served, done_ns dropped, 2^64 - 1 absent); and the
+    iterations the fixed point took."""
+    wait_ns: np.ndarray
+    done_ns: np.ndarray
+    ahead: np.ndarray
+    link_free: np.ndarray
+    link_busy_ns: np.ndarray
+    link_wait_max_ns: np.ndarray
+    link_wait_sum_ns: np.ndarray
+    link_ahead_max: np.ndarray
+    dropped: np.ndarray
+    link_drops: np.ndarray
+    link_refused_ns: np.ndarray
+    absent: np.ndarray
+    enter_ns: np.ndarray
+    iterations: int
+
+
+_UMAX = 0xFFFFFFFFFFFFFFFF
+
+
+def queue_limit_ns(buffer_units, cost_ps):
+    """sg_link_queue's limit_ns of a buffer of buffer_units weight units (bytes, with byte weights)
+    in front of a link's server: min(ceil(buffer_units cost_ps / 1000), 2^64 - 1), exactly, on
+    Python integers.  Sequences (one of them may be a single value) give a u64 array, one limit
+    per link."""
+    def one(b, c) -> int:
+        b, c = int(b), int(c)
+        if b < 0 or c < 0:
+            raise ValueError("buffer_units, cost_ps: not negative")
+        return min(-((-b * c) // 1000), _UMAX)
+    if np.ndim(buffer_units) == 0 and np.ndim(cost_ps) == 0:
+        return one(buffer_units, cost_ps)
+    b, c = np.broadcast_arrays(np.asarray(buffer_units, dtype=object), np.asarray(cost_ps, dtype=object))
+    return np.array([one(x, y) for x, y in zip(b.ravel().tolist(), c.ravel().tolist())], dtype=np.uint64)
+
+
+def _service_ns(link_off, n: int, packet, weight, cost) -> np.ndarray:
+    """s = ceil(weight cost / 1000) per record, exactly (host arrays; below 2^64 wherever a record
+    was served, since its done is)."""
     off = np.asarray(link_off).astype(np.int64)
-    n = len(res.done_ns)
     per = np.repeat(np.asarray(cost, np.uint64), np.diff(off))
     w = np.ones(n, np.uint64) if weight is None else np.asarray(weight, np.uint32).astype(np.uint64)[np.asarray(packet).astype(np.int64)]
     if n == 0 or int(per.max()) < 1 << 32:  # (the product fits 64 bits)
         prod = w * per
-        s = prod // np.uint64(1000) + (prod % np.uint64(1000) != 0).astype(np.uint64)
-    else:
-        s = np.array([-((-int(a) * int(b)) // 1000) for a, b in zip(w.tolist(), per.tolist())], dtype=np.uint64)
+        return prod // np.uint64(1000) + (prod % np.uint64(1000) != 0).astype(np.uint64)
+    return np.array([min(-((-int(a) * int(b)) // 1000), _UMAX) for a, b in zip(w.tolist(), per.tolist())], dtype=np.uint64)
+
+
+def _dropped(ctx: "Context", raw, n_links: int, link_off, packet, weight, cost, carry: bool):
+    """The result of a flagged call that succeeded, from its eight raw arrays (busy and ahead max
+    with 2 n_links entries): the states from the sentinels, the per-link arrays cut back."""
+    wait, done, ahead, free, busy2, wmax, wsum, amax2 = raw
+    out = wait == np.uint64(_UMAX)
+    absent = out & (done == np.uint64(_UMAX))
+    dropped = out & ~absent
+    res = LinkQueueDropped(wait, done, ahead, free, busy2[:n_links], wmax, wsum, amax2[:n_links], dropped,
+                           amax2[n_links:2 * n_links], busy2[n_links:2 * n_links])
+    if not carry:
+        return res
+    n = len(done)
+    enter = done.copy()
+    srv = ~out
+    if srv.any():
+        s = _service_ns(link_off, n, packet, weight, cost)
+        enter[srv] = done[srv] - s[srv] - wait[srv]
+    return LinkQueueCarriedDropped(*res, absent, enter, int(ctx.read_timer("link_queue_iters")[1]) if n else 0)
+
+
+def _exit_carried(exit_ns, enter_ns, queue):
+    """The carried exit time per record of a round: exit + (done - enter), 2^64 - 1 at a dropped
+    or absent hop."""
+    out = exit_ns + (queue.done_ns - enter_ns)
+    if isinstance(queue, LinkQueueCarriedDropped):
+        out[queue.dropped | queue.absent] = np.uint64(_UMAX)
+    return out
+
+
+def _carried(ctx: "Context", res: LinkQueueResult, link_off, packet, weight, cost) -> LinkQueueCarried:
+    """The carried result of a call that succeeded: enter' = done - s - wait, exactly (host arrays;
+    s = ceil(weight cost / 1000) is below 2^64 here, since every done is)."""
+    n = len(res.done_ns)
+    s = _service_ns(link_off, n, packet, weight, cost)
     return LinkQueueCarried(*res, res.done_ns - s - res.wait_ns, int(ctx.read_timer("link_queue_iters")[1]) if n else 0)
 
 
@@ -268,7 +361,8 @@ def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
     return a
 
 
-def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False):
+def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False,
+               limit_ns=None):
     """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
     records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
     arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
@@ -281,7 +375,11 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     required, and without weight the packets number max(packet) + 1.  The records of one packet,
     in ascending enter_ns, are its chain; a record enters at the previous one's done plus the
     input's gap between the two, and every link serves in ascending (carried enter, packet)
-    order.  Results stay at the input records' indices."""
+    order.  Results stay at the input records' indices.
+    limit_ns: one u64 per link, the longest wait the link's buffer holds (queue_limit_ns; 2^64 - 1:
+    no limit) (SG_LINK_QUEUE_DROP).  A record that would wait longer is dropped: the server's time
+    is unchanged, and with carry=True the packet's later records are absent, they enter no queue.
+    A LinkQueueDropped, with carry=True a LinkQueueCarriedDropped."""
     if carry and packet is None:
         raise ValueError("packet: required with carry=True")
     off = np.ascontiguousarray(link_off, dtype=np.uint64)
@@ -296,45 +394,59 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     wt = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint32)
     cost = _per_link_u64(cost_ps, n_links, "cost_ps")
     free = None if free_ns is None else _per_link_u64(free_ns, n_links, "free_ns")
+    drop = limit_ns is not None
+    nl2 = 2 * n_links if drop else n_links
+    cost2 = np.concatenate([cost, _per_link_u64(limit_ns, n_links, "limit_ns")]) if drop else cost
+    flags = (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | (_capi.SG_LINK_QUEUE_DROP if drop else 0)
     res = LinkQueueResult(np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32),
-                          np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64),
-                          np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint32))
+                          np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint64), np.zeros(n_links, np.uint64),
+                          np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint32))
     ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
     n_weights = 0 if wt is None else len(wt)
     if carry and wt is None:
         n_weights = int(pkt.max()) + 1 if n else 0
     check(ctx.handle, load().sg_link_queue(
-        ctx.handle, _capi.SG_LINK_QUEUE_CARRY if carry else 0, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)),
-        ptr(pkt if n or pkt is None else np.zeros(1, np.uint32)), ptr(wt), n_weights, ptr(cost),
+        ctx.handle, flags, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)),
+        ptr(pkt if n or pkt is None else np.zeros(1, np.uint32)), ptr(wt), n_weights, ptr(cost2),
         ptr(free), *[ptr(a) for a in res]))
+    if drop:
+        return _dropped(ctx, res, n_links, off, pkt, wt, cost, carry)
     return _carried(ctx, res, off, pkt, wt, cost) if carry else res
 
 
 def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
-                        free_ns, carry: bool = False, n_packets: int = 0):
+                        free_ns, carry: bool = False, n_packets: int = 0, limit_ns=None):
     """sg_link_queue on a device trace (torch tensors on `dev`: off, enter, packet; weight or
     None), every output taken and copied to the host.  carry: with SG_LINK_QUEUE_CARRY, a
-    LinkQueueCarried; n_packets bounds the packet numbers when there is no weight."""
+    LinkQueueCarried; n_packets bounds the packet numbers when there is no weight.  limit_ns: with
+    SG_LINK_QUEUE_DROP, a LinkQueueDropped or LinkQueueCarriedDropped."""
     import torch
 
     up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)  # noqa: E731
     h_cost = _per_link_u64(cost_ps, n_links, "cost_ps")
-    cost = up(h_cost)
+    drop = limit_ns is not None
+    nl2 = 2 * n_links if drop else n_links
+    cost = up(np.concatenate([h_cost, _per_link_u64(limit_ns, n_links, "limit_ns")]) if drop else h_cost)
     free = None if free_ns is None else up(_per_link_u64(free_ns, n_links, "free_ns"))
     rec = lambda dt: torch.zeros(max(n_records, 1), dtype=dt, device=dev)  # noqa: E731
-    lnk = lambda dt: torch.zeros(max(n_links, 1), dtype=dt, device=dev)  # noqa: E731
-    outs = [rec(torch.int64), rec(torch.int64), rec(torch.int32), lnk(torch.int64), lnk(torch.int64), lnk(torch.int64),
-            lnk(torch.int64), lnk(torch.int32)]
+    lnk = lambda dt, k=n_links: torch.zeros(max(k, 1), dtype=dt, device=dev)  # noqa: E731
+    outs = [rec(torch.int64), rec(torch.int64), rec(torch.int32), lnk(torch.int64), lnk(torch.int64, nl2), lnk(torch.int64),
+            lnk(torch.int64), lnk(torch.int32, nl2)]
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     torch.cuda.synchronize(dev)
     check(ctx.handle, load().sg_link_queue(
-        ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0), n_links, ptr(off), n_records,
+        ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) |
+        (_capi.SG_LINK_QUEUE_DROP if drop else 0), n_links, ptr(off), n_records,
         ptr(enter), None if weight is None and not carry else ptr(packet), ptr(weight),
         (n_packets if carry else 0) if weight is None else weight.numel(), ptr(cost),
         ptr(free), *[ptr(t) for t in outs]))
-    lens = [n_records] * 3 + [n_links] * 5
+    lens = [n_records] * 3 + [n_links, nl2, n_links, n_links, nl2]
     dts = [np.uint64, np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32]
     res = LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
+    if drop:
+        return _dropped(ctx, res, n_links, off.cpu().numpy().view(np.uint64),
+                        None if weight is None and not carry else packet[:n_records].cpu().numpy().view(np.uint32),
+                        None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost, carry)
     if not carry:
         return res
     return _carried(ctx, res, off.cpu().numpy().view(np.uint64), packet[:n_records].cpu().numpy().view(np.uint32),
@@ -644,7 +756,7 @@ class PathTree:
         return series, outside
 
     def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
-                         carry=False):
+                         carry=False, limit_ns=None):
         """The link trace of one round's batch and the FIFO queue of every link under a link rate,
         (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
         gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
@@ -655,7 +767,10 @@ class PathTree:
         carry=True: it is (SG_LINK_QUEUE_CARRY).  queue is then a LinkQueueCarried, and a seventh
         entry follows it: the carried exit_ns per record, exit_ns + (done_ns - enter_ns), when the
         crossing leaves its link under the rates; a packet's last hop's value is its arrival.  An
-        unwatched link is crossed at its latency, as a link of infinite rate."""
+        unwatched link is crossed at its latency, as a link of infinite rate.
+        limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP, as in
+        shadow_amd.link_queue).  queue is then a LinkQueueDropped or, with carry=True, a
+        LinkQueueCarriedDropped, and the carried exit_ns is 2^64 - 1 at a dropped or absent hop."""
         import torch
 
         npk = len(packets)
@@ -712,11 +827,12 @@ class PathTree:
             if rc != _capi.SG_ERR_CAPACITY or t <= cap:
                 break
             cap = t
-        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk)
+        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk,
+                                    limit_ns)
         out = (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32),
                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
                leave[:t].cpu().numpy().view(np.uint64), queue)
-        return out + (out[4] + (queue.done_ns - out[3]),) if carry else out
+        return out + (_exit_carried(out[4], out[3], queue),) if carry else out
 
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
@@ -1091,7 +1207,7 @@ class NetworkGraph:
     def link_queue_device(self, link_off_ptr: int, n_records: int, enter_ptr: int, packet_ptr: int, weight_ptr: int,
                           n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
                           ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
-                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False) -> None:
+                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False, limit_ns=None) -> None:
         """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
         device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
         packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
@@ -1101,10 +1217,29 @@ class NetworkGraph:
         per link link_free u64 (not free_in's array), busy u64, wait_max u64, wait_sum u64,
         ahead_max u32 (sg_link_queue).  carry: every wait is carried to the packet's later hops
         (SG_LINK_QUEUE_CARRY: packet is required and n_weights bounds it); the call then
-        synchronises once per iteration, read_timer("link_queue_iters") tells how many it took."""
+        synchronises once per iteration, read_timer("link_queue_iters") tells how many it took.
+        limit_ns: a host array of one u64 per link, the longest wait its buffer holds
+        (SG_LINK_QUEUE_DROP).  cost is then copied, with the limits behind it, into the doubled
+        array the call takes; busy and ahead_max must have two entries per link (the second
+        halves: the refused service and the drops per link), and the per-record outputs carry
+        the states as sentinels (sg_link_queue)."""
         vp = lambda x: C.c_void_p(x or None)  # noqa: E731
+        n_links = len(self.links()[0])
+        flags = _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0)
+        if limit_ns is not None:
+            import torch
+
+            class _View:  # the n_links u64 at cost_ptr, for torch
+                __cuda_array_interface__ = {"shape": (n_links,), "typestr": "<i8", "data": (int(cost_ptr), False),
+                                            "version": 2}
+            old = torch.as_tensor(_View(), device="cuda")
+            lim = torch.from_numpy(_per_link_u64(limit_ns, n_links, "limit_ns").view(np.int64)).to(old.device)
+            cost2 = torch.cat([old, lim]).contiguous()
+            torch.cuda.synchronize(old.device)
+            cost_ptr = cost2.data_ptr()
+            flags |= _capi.SG_LINK_QUEUE_DROP
         check(self.ctx.handle, load().sg_link_queue(
-            self.ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0), len(self.links()[0]), vp(link_off_ptr), int(n_records),
+            self.ctx.handle, flags, n_links, vp(link_off_ptr), int(n_records),
             vp(enter_ptr), vp(packet_ptr), vp(weight_ptr), int(n_weights), vp(cost_ptr), vp(free_in_ptr), vp(wait_ptr),
             vp(done_ptr), vp(ahead_ptr), vp(link_free_ptr), vp(busy_ptr), vp(wait_max_ptr), vp(wait_sum_ptr),
             vp(ahead_max_ptr)))

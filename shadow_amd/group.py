@@ -296,7 +296,7 @@ class Group:
         return off, pkt, mem, hop, enter, leave, total.value
 
     def link_queue_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, cost_ps, watch=None,
-                         free_ns=None, root: int = 0, carry=False):
+                         free_ns=None, root: int = 0, carry=False, limit_ns=None):
         """The link trace of one sharded round and the FIFO queue of every link under a link rate,
         (link_off, packet, member, hop, enter_ns, exit_ns, queue): the first six as
         link_trace_round gives them, queue a graph.LinkQueueResult over the same records
@@ -306,10 +306,13 @@ class Group:
         array per member (as in link_load_round); cost_ps, free_ns as in shadow_amd.link_queue.
         carry=True: every wait is carried to the packet's later hops (SG_LINK_QUEUE_CARRY), on
         root's merged trace as well; queue is then a graph.LinkQueueCarried, and the carried
-        exit_ns per record follows it (PathTree.link_queue_round)."""
+        exit_ns per record follows it (PathTree.link_queue_round).
+        limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP), on
+        root's merged trace as well; queue is then a graph.LinkQueueDropped or
+        graph.LinkQueueCarriedDropped (PathTree.link_queue_round)."""
         import torch
 
-        from .graph import _link_queue_tensors
+        from .graph import _exit_carried, _link_queue_tensors
 
         tr = self._link_trace_tensors(graphs, hosts, rows, packets, status, watch, root)
         off, pkt, _, _, enter, _, t = tr
@@ -333,9 +336,9 @@ class Group:
                 parts.append(w.reshape(-1)[:len(packets[m])].view(torch.int32).to(dev))
             wt = torch.cat(parts).contiguous() if parts else None
         queue = _link_queue_tensors(self.contexts[root], dev, off.numel() - 1, off, t, enter, pkt, wt, cost_ps, free_ns,
-                                    carry, sum(len(p) for p in packets))
+                                    carry, sum(len(p) for p in packets), limit_ns)
         host = self._trace_to_host(*tr)
-        return host + (queue, host[5] + (queue.done_ns - host[4])) if carry else host + (queue,)
+        return host + (queue, _exit_carried(host[5], host[4], queue)) if carry else host + (queue,)
 
     def link_series_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, t0_ns: int, bin_ns: int,
                           n_bins: int, slots=None, at: str = "enter", out=None, root: int = 0):

@@ -166,8 +166,8 @@ void timer_add_work(sg_ctx* ctx, const char* name, double work) {
   ctx->timers.back().second.work = work;
 }
 
-void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n) {
-  if (!ctx->timing) return;
+void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n, bool always) {
+  if (!ctx->timing && !always) return;
   KernelTimer* t = nullptr;
   for (auto& kv : ctx->timers)
     if (kv.first == name) t = &kv.second;

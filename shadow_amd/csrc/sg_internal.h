@@ -130,16 +130,16 @@ struct sg_ctx {
   // link time series (sg_series.hip; it shares l_idx, l_flag, l_pred and p_lat): the device copy
   // of a host slot map, and the zeroed sums of a host-mode call or of a group member
   sg::DevBuf sr_slot, sr_series, sr_outside;
-  // link queues (sg_queue.hip): the device copies of a host-mode call's six inputs and eight
+  // link queues (sg_queue.hip, sg_queue.h): the device copies of a host-mode call's six inputs and eight
   // outputs, the tile aggregates, the done times when the caller takes none, the flag words
   sg::DevBuf q_buf[14], q_agg, q_done, q_flag;
-  // the carried form (SG_LINK_QUEUE_CARRY; it shares tr_key, tr_key2 and tr_work with the link
+  // the carried form (SG_LINK_QUEUE_CARRY, sg_queue_carry.hip; it shares tr_key, tr_key2 and tr_work with the link
   // trace's sort, and p_sums through scan_counts): the per-packet counters with the fill's
   // cursors and the sort's work counter, the packet offsets, the records in chain order, next,
   // gap, the carried enter times, and a link-sorted pass: enter, packet, the permutation, done,
   // wait, ahead
   sg::DevBuf qc_cnt, qc_off, qc_list, qc_next, qc_gap, qc_cur, qc_enter, qc_packet, qc_perm, qc_done, qc_wait, qc_ahead;
-  // finite buffers (SG_LINK_QUEUE_DROP; p_sums through scan_counts): the period heads and then
+  // finite buffers (SG_LINK_QUEUE_DROP, sg_queue_drop.hip; p_sums through scan_counts): the period heads and then
   // the served marks, their exclusive sums, the period starts, the long periods with their
   // counter, and per record the running done and the wait; the carried form's sorted done
   sg::DevBuf qd_mark, qd_pos, qd_start, qd_long, qd_run, qd_wait, qd_done;
@@ -425,8 +425,9 @@ void report_round_flags(sg_ctx* ctx);
 
 // Add algorithmic work to a timer after the fact (e.g. a device-side count).
 void timer_add_work(sg_ctx* ctx, const char* name, double work);
-// A counter pair of the last build under a timer's name: read_timer gives (0, n, work).
-void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n);
+// A counter pair of the last build under a timer's name: read_timer gives (0, n, work).  `always`:
+// kept whether or not the timers are on.
+void timer_set_counter(sg_ctx* ctx, const char* name, double work, uint64_t n, bool always = false);
 
 // RAII bracket for one instrumented launch: `TimedLaunch t(ctx, "k_walk", work);`
 // before the launch; the end event is recorded when `t` goes out of scope.

@@ -1,5 +1,5 @@
 // sg_scan.h -- the wave and workgroup scan helpers of the reduce-then-scan kernels: the u64 sums of
-// sg_scan.hip and the (head flag, S, M) elements of sg_queue.hip.  Device code only.
+// sg_scan.hip and the (head flag, S, M) elements of the link queues (sg_queue.h).  Device code only.
 //
 // An element type T needs scan_shfl_up(T, d) (the value of the lane d below, anything where there
 // is none) and an operator op(lower, upper) that is associative; it need not commute: the lower
@@ -17,7 +17,8 @@ __device__ __forceinline__ unsigned long long scan_shfl_up(unsigned long long x,
 }
 
 struct ScanPlus {
-  __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const {
+  template <class T>
+  __device__ __forceinline__ T operator()(T a, T b) const {
     return a + b;
   }
 };

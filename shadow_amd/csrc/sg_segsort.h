@@ -1,7 +1,7 @@
 // sg_segsort.h -- the three-tier segmented sort of 16-byte keys (time lo, time hi, tie word,
 // payload word), ascending (time, tie word) inside every segment of an offset array.  Its users:
 // the link trace (sg_trace.hip: segments are links, the tie word the packet, the payload the hop)
-// and the carried link queues (sg_queue.hip: a packet's records by input time, and every link's
+// and the carried link queues (sg_queue_carry.hip: a packet's records by input time, and every link's
 // records by carried time once per iteration).
 //   k_trace_sort_small  a wave per segment: up to 64 records are ranked in the wave's registers
 //                       (keys are unique, so ranks are a permutation); a longer segment is cut

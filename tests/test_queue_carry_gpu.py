@@ -7,6 +7,8 @@ otherwise each case runs in host and in device mode and in both forms of the sca
 segmented scan and, under SG_LINK_QUEUE_SERIAL = 1, the lane per link).  The reference is the
 event-driven simulation; the fixed-point loop gives the iteration counts.  Inputs:
 tests/queue_carry_cases.py; test_queue_carry_ref_cpu.py qualifies them."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -15,107 +17,28 @@ import link_cases as LC
 import queue_carry_cases as CC
 import queue_carry_ref as CR
 import queue_cases as QC
+import queue_gpu_calls as QG
 import queue_ref as QR
 import sweep_cases as WC
 import trace_cases as XC
 import trace_ref as XR
+from queue_gpu_calls import (CARRY, FORMS, INPUTS, PY_FIELDS, VIEW, _batch, _check_calls, _form, _host_table, _net, _pair,
+                             _sentinels, _untouched, ctx_error)
 
 pytestmark = pytest.mark.gpu
 
 MAX = QR.MAX
-VIEW = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
-FORMS = ("scan", "serial")
-INPUTS = ("link_off", "enter", "packet", "weight", "cost_ps", "free_in")
-CARRY = 4  # (the flag bit, by value: test_queue_carry_ref_cpu.py holds the layers' constants to it)
-
-
-def _sentinels(c, names):
-    n, nl = len(c["enter"]), len(c["link_off"]) - 1
-    return {k: np.full(n if k in QR.RECORD_FIELDS else nl, QC.SENT32 if QR.DTYPES[k] == np.uint32 else QC.SENT64,
-                       QR.DTYPES[k]) for k in names}
-
-
-def _call(ctx, c, names=QR.FIELDS, *, dev, carry=True, n_records=None):
-    """One sg_link_queue call on a case's arrays, the outputs `names` starting from sentinels.
-    Returns (status, outputs by name)."""
-    import torch
-
-    from shadow_amd import _capi
-
-    C = _capi.C
-    outs = _sentinels(c, names)
-    keep = []
-
-    def ptr(a):
-        if a is None:
-            return None
-        if not dev:
-            return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(np.zeros(1, a.dtype).ctypes.data)
-        t = torch.from_numpy(np.ascontiguousarray(a).view(VIEW[a.dtype]).copy() if a.size else np.zeros(1, VIEW[a.dtype])).cuda()
-        keep.append((a, t))
-        return C.c_void_p(t.data_ptr())
-
-    ip = [ptr(c[k]) for k in INPUTS]
-    n_in = len(keep)
-    op = {k: ptr(outs[k]) if k in outs else None for k in QR.FIELDS}
-    if dev:
-        torch.cuda.synchronize()
-    flags = (_capi.SG_ROUTE_OUT_DEVICE if dev else 0) | (CARRY if carry else 0)
-    rc = _capi.load().sg_link_queue(ctx.handle, flags, len(c["link_off"]) - 1, ip[0],
-                                    len(c["enter"]) if n_records is None else n_records, ip[1], ip[2], ip[3],
-                                    c["n_packets"], ip[4], ip[5], *[op[k] for k in QR.FIELDS])
-    if dev:
-        torch.cuda.synchronize()
-        for a, t in keep[n_in:]:
-            if a.size:
-                a[...] = t.cpu().numpy().view(a.dtype)
-    return rc, outs
-
-
-def _pair(ctx):
-    from shadow_amd import _capi
-
-    r, k = _capi.C.c_uint32(), _capi.C.c_uint32()
-    _capi.load().sg_ctx_last_error_pair(ctx.handle, _capi.C.byref(r), _capi.C.byref(k))
-    return r.value, k.value
-
-
-def _untouched(outs):
-    return all((a == (QC.SENT32 if a.dtype == np.uint32 else QC.SENT64)).all() for a in outs.values())
-
-
-def _form(monkeypatch, form):
-    monkeypatch.setenv("SG_LINK_QUEUE_SERIAL", "1" if form == "serial" else "0")
-
-
-def _iters(ctx):
-    return int(ctx.read_timer("link_queue_iters")[1])
+_call = functools.partial(QG._call, carry=True)
 
 
 def _check(ctx, monkeypatch, c, want=None, *, devs=(True, False), forms=FORMS, names=QR.FIELDS, iters=None):
     """The case in every mode and form against the reference (the event simulation unless `want`
     is given); iters: the iterations every call must have taken."""
-    from shadow_amd import _capi
-
     if want is None:
         rc, _, want, _, _ = CC.ref(c)
         assert rc == CR.OK
-    ctx.enable_timers(True)  # (read_timer("link_queue_serial") tells the form the last call took)
-    try:
-        for form in forms:
-            _form(monkeypatch, form)
-            for dev in devs:
-                rc, outs = _call(ctx, c, names, dev=dev)
-                _capi.check(ctx.handle, rc)
-                assert int(ctx.read_timer("link_queue_serial")[1]) == (form == "serial")
-                assert iters is None or _iters(ctx) == iters
-                for k in names:
-                    w = getattr(want, k)
-                    assert np.array_equal(outs[k], w), \
-                        f"{k} ({form}, {'device' if dev else 'host'}): {int((outs[k] != w).sum())} of {w.size} differ, " \
-                        f"first at {int(np.flatnonzero(outs[k] != w)[0])}"
-    finally:
-        ctx.enable_timers(False)
+    _check_calls(ctx, monkeypatch, c, {k: getattr(want, k) for k in names}, names, carry=True, devs=devs, forms=forms,
+                 iters=iters)
     return want
 
 
@@ -220,12 +143,6 @@ def test_output_subsets(ctx, monkeypatch):
 
 
 # ---- 4. errors
-def ctx_error(ctx):
-    from shadow_amd import _capi
-
-    return _capi.load().sg_ctx_last_error(ctx.handle).decode()
-
-
 @pytest.mark.parametrize("dev", [True, False], ids=["device", "host"])
 def test_argument_errors(ctx, dev):
     """With the flag, every output untouched: NULL packet (SG_ERR_INVALID_ARG), a record count past
@@ -346,28 +263,6 @@ def test_non_blocking_stream():
 
 
 # ---- 6. real traces
-def _net(g, ctx):
-    from shadow_amd import NetworkGraph
-
-    return NetworkGraph(g["n"], g["src"], g["dst"], g["lat"], g["loss"], g["directed"], ctx=ctx)
-
-
-def _host_table(hosts, ctx):
-    from shadow_amd.worker import HostTable
-
-    return HostTable(hosts["ip"], hosts["route"], hosts["seed"], ctx=ctx)
-
-
-def _batch(pk):
-    from shadow_amd.worker import PacketBatch
-
-    return PacketBatch.from_numpy(pk["src"], pk["dst_ip"], pk["payload"], pk["send_time"])
-
-
-PY_FIELDS = dict(zip(("wait_ns", "done_ns", "ahead", "link_free", "link_busy_ns", "link_wait_max_ns", "link_wait_sum_ns",
-                      "link_ahead_max"), QR.FIELDS))
-
-
 def _same_carried(got, want, cur, iters=None):
     """A LinkQueueCarried against the reference's Result, carried enter and iterations."""
     for a, b in PY_FIELDS.items():

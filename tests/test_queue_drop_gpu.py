@@ -8,6 +8,8 @@ parallel and, under SG_LINK_QUEUE_SERIAL = 1, the lane per link).  First order t
 plain loop (queue_drop_cases.fast, the same loop with `ahead` by bisection, for the large cases);
 carried it is the event-driven simulation, and the fixed-point loop gives the iteration counts.
 Inputs: tests/queue_drop_cases.py; test_queue_drop_ref_cpu.py qualifies them."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -17,18 +19,20 @@ import queue_carry_cases as CC
 import queue_cases as QC
 import queue_drop_cases as DC
 import queue_drop_ref as DR
+import queue_gpu_calls as QG
 import queue_ref as QR
 import sweep_cases as WC
 import trace_cases as XC
 import trace_ref as XR
-from test_queue_carry_gpu import INPUTS, PY_FIELDS, VIEW, _batch, _form, _host_table, _iters, _net, _pair, _untouched, ctx_error
+from queue_gpu_calls import (CARRY, DROP, FORMS, INPUTS, PY_FIELDS, VIEW, _batch, _check_calls, _form, _host_table, _net, _pair,
+                             _untouched, ctx_error)
 
 pytestmark = pytest.mark.gpu
 
 MAX = DR.MAX
-FORMS = ("scan", "serial")
-CARRY, DROP = 4, 8  # (the flag bits, by value: the two reference test files hold the layers' constants to them)
 RAW = QR.FIELDS  # the call's eight output arrays; busy and ahead_max have two entries per link
+_call = functools.partial(QG._call, drop=True)
+_sentinels = functools.partial(QG._sentinels, drop=True)
 
 
 def raw(want):
@@ -39,78 +43,16 @@ def raw(want):
     return out
 
 
-def _sentinels(c, names, drop=True):
-    n, nl = len(c["enter"]), len(c["link_off"]) - 1
-    size = lambda k: n if k in QR.RECORD_FIELDS else (2 * nl if drop and k in ("busy", "ahead_max") else nl)  # noqa: E731
-    return {k: np.full(size(k), QC.SENT32 if QR.DTYPES[k] == np.uint32 else QC.SENT64, QR.DTYPES[k]) for k in names}
-
-
-def _call(ctx, c, names=RAW, *, dev, carry=False, drop=True, n_records=None):
-    """One sg_link_queue call on a case's arrays, the outputs `names` starting from sentinels.
-    Returns (status, outputs by name)."""
-    import torch
-
-    from shadow_amd import _capi
-
-    C = _capi.C
-    outs = _sentinels(c, names, drop)
-    keep = []
-
-    def ptr(a):
-        if a is None:
-            return None
-        if not dev:
-            return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(np.zeros(1, a.dtype).ctypes.data)
-        t = torch.from_numpy(np.ascontiguousarray(a).view(VIEW[a.dtype]).copy() if a.size else np.zeros(1, VIEW[a.dtype])).cuda()
-        keep.append((a, t))
-        return C.c_void_p(t.data_ptr())
-
-    arrays = dict(c, cost_ps=np.concatenate([c["cost_ps"], c["limit_ns"]]) if drop else c["cost_ps"])
-    ip = [ptr(arrays[k]) for k in INPUTS]
-    n_in = len(keep)
-    op = {k: ptr(outs[k]) if k in outs else None for k in RAW}
-    if dev:
-        torch.cuda.synchronize()
-    flags = (_capi.SG_ROUTE_OUT_DEVICE if dev else 0) | (CARRY if carry else 0) | (DROP if drop else 0)
-    rc = _capi.load().sg_link_queue(ctx.handle, flags, len(c["link_off"]) - 1, ip[0],
-                                    len(c["enter"]) if n_records is None else n_records, ip[1], ip[2], ip[3],
-                                    c["n_packets"] if carry or c["weight"] is not None else 0, ip[4], ip[5],
-                                    *[op[k] for k in RAW])
-    if dev:
-        torch.cuda.synchronize()
-        for a, t in keep[n_in:]:
-            if a.size:
-                a[...] = t.cpu().numpy().view(a.dtype)
-    return rc, outs
-
-
 def _check(ctx, monkeypatch, c, want=None, *, carry=False, devs=(True, False), forms=FORMS, names=RAW, iters=None):
     """The case in every mode and form against the reference; iters: the iterations every carried
     call must have taken."""
-    from shadow_amd import _capi
-
     if want is None:
         if carry:
             rc, _, want, _, _ = DC.ref_carried(c)
         else:
             rc, _, want = DC.ref(c)
         assert rc == DR.OK
-    w = raw(want)
-    ctx.enable_timers(True)  # (read_timer("link_queue_serial") tells the form the last call took)
-    try:
-        for form in forms:
-            _form(monkeypatch, form)
-            for dev in devs:
-                rc, outs = _call(ctx, c, names, dev=dev, carry=carry)
-                _capi.check(ctx.handle, rc)
-                assert int(ctx.read_timer("link_queue_serial")[1]) == (form == "serial")
-                assert iters is None or _iters(ctx) == iters
-                for k in names:
-                    assert np.array_equal(outs[k], w[k]), \
-                        f"{k} ({form}, {'device' if dev else 'host'}): {int((outs[k] != w[k]).sum())} of {w[k].size} differ, " \
-                        f"first at {int(np.flatnonzero(outs[k] != w[k])[0])}"
-    finally:
-        ctx.enable_timers(False)
+    _check_calls(ctx, monkeypatch, c, raw(want), names, carry=carry, drop=True, devs=devs, forms=forms, iters=iters)
     return want
 
 

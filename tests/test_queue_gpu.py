@@ -15,99 +15,20 @@ import queue_ref as QR
 import sweep_cases as WC
 import trace_cases as XC
 import trace_ref as XR
+from queue_gpu_calls import (FORMS, INPUTS, PY_FIELDS, VIEW, _batch, _call, _check_calls, _form, _host_table, _net, _pair,
+                             _sentinels, _untouched, ctx_error)
 
 pytestmark = pytest.mark.gpu
 
 MAX = QR.MAX
-VIEW = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
-FORMS = ("scan", "serial")
-INPUTS = ("link_off", "enter", "packet", "weight", "cost_ps", "free_in")
-
-
-def _sentinels(c, names):
-    n, nl = len(c["enter"]), len(c["link_off"]) - 1
-    return {k: np.full(n if k in QR.RECORD_FIELDS else nl, QC.SENT32 if QR.DTYPES[k] == np.uint32 else QC.SENT64,
-                       QR.DTYPES[k]) for k in names}
-
-
-def _call(ctx, c, names=QR.FIELDS, *, dev, handle=True, alias_free=False, n_records=None):
-    """One sg_link_queue call on a case's arrays, the outputs `names` starting from sentinels.
-    Returns (status, outputs by name)."""
-    import torch
-
-    from shadow_amd import _capi
-
-    C = _capi.C
-    outs = _sentinels(c, names)
-    ins = [c[k] for k in INPUTS]
-    keep = []
-
-    def ptr(a):
-        if a is None:
-            return None
-        if not dev:
-            return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(np.zeros(1, a.dtype).ctypes.data)
-        t = torch.from_numpy(np.ascontiguousarray(a).view(VIEW[a.dtype]).copy() if a.size else np.zeros(1, VIEW[a.dtype])).cuda()
-        keep.append((a, t))
-        return C.c_void_p(t.data_ptr())
-
-    ip = [ptr(a) for a in ins]
-    n_in = len(keep)
-    op = {k: ptr(outs[k]) if k in outs else None for k in QR.FIELDS}
-    if alias_free:
-        op["link_free"] = ip[5]
-    if dev:
-        torch.cuda.synchronize()
-    rc = _capi.load().sg_link_queue(
-        ctx.handle if handle else None, _capi.SG_ROUTE_OUT_DEVICE if dev else 0, len(c["link_off"]) - 1, ip[0],
-        len(c["enter"]) if n_records is None else n_records, ip[1], ip[2], ip[3], 0 if c["weight"] is None else len(c["weight"]),
-        ip[4], ip[5], *[op[k] for k in QR.FIELDS])
-    if dev:
-        torch.cuda.synchronize()
-        for a, t in keep[n_in:]:
-            if a.size:
-                a[...] = t.cpu().numpy().view(a.dtype)
-    return rc, outs
-
-
-def _pair(ctx):
-    from shadow_amd import _capi
-
-    r, k = _capi.C.c_uint32(), _capi.C.c_uint32()
-    _capi.load().sg_ctx_last_error_pair(ctx.handle, _capi.C.byref(r), _capi.C.byref(k))
-    return r.value, k.value
-
-
-def _untouched(outs):
-    return all((a == (QC.SENT32 if a.dtype == np.uint32 else QC.SENT64)).all() for a in outs.values())
-
-
-def _form(monkeypatch, form):
-    monkeypatch.setenv("SG_LINK_QUEUE_SERIAL", "1" if form == "serial" else "0")
 
 
 def _check(ctx, monkeypatch, c, want=None, *, devs=(True, False), forms=FORMS, names=QR.FIELDS):
     """The case in every mode and form against the reference (the loop unless `want` is given)."""
-    from shadow_amd import _capi
-
     if want is None:
         rc, _, want = QC.ref(c)
         assert rc == QR.OK
-    ctx.enable_timers(True)  # (read_timer("link_queue_serial") tells the form the last call took)
-    try:
-        for form in forms:
-            _form(monkeypatch, form)
-            for dev in devs:
-                rc, outs = _call(ctx, c, names, dev=dev)
-                _capi.check(ctx.handle, rc)
-                assert int(ctx.read_timer("link_queue_serial")[1]) == (form == "serial")
-                for k in names:
-                    w = getattr(want, k)
-                    assert np.array_equal(outs[k], w), \
-                        f"{k} ({form}, {'device' if dev else 'host'}): {int((outs[k] != w).sum())} of {w.size} differ, " \
-                        f"first at {int(np.flatnonzero(outs[k] != w)[0])}"
-    finally:
-        ctx.enable_timers(False)
+    _check_calls(ctx, monkeypatch, c, {k: getattr(want, k) for k in names}, names, devs=devs, forms=forms)
     return want
 
 
@@ -310,12 +231,6 @@ def test_argument_errors(ctx, monkeypatch, dev):
         assert rc == _capi.SG_ERR_INVALID_ARG and _untouched(outs), name
 
 
-def ctx_error(ctx):
-    from shadow_amd import _capi
-
-    return _capi.load().sg_ctx_last_error(ctx.handle).decode()
-
-
 def _call_without(ctx, c, name, dev):
     """_call with one required input NULL (the sizes taken from the full case)."""
     import torch
@@ -387,28 +302,6 @@ def test_data_errors(ctx, monkeypatch, dev, form):
 
 
 # ---- 10. real traces
-def _net(g, ctx):
-    from shadow_amd import NetworkGraph
-
-    return NetworkGraph(g["n"], g["src"], g["dst"], g["lat"], g["loss"], g["directed"], ctx=ctx)
-
-
-def _host_table(hosts, ctx):
-    from shadow_amd.worker import HostTable
-
-    return HostTable(hosts["ip"], hosts["route"], hosts["seed"], ctx=ctx)
-
-
-def _batch(pk):
-    from shadow_amd.worker import PacketBatch
-
-    return PacketBatch.from_numpy(pk["src"], pk["dst_ip"], pk["payload"], pk["send_time"])
-
-
-PY_FIELDS = dict(zip(("wait_ns", "done_ns", "ahead", "link_free", "link_busy_ns", "link_wait_max_ns", "link_wait_sum_ns",
-                      "link_ahead_max"), QR.FIELDS))
-
-
 def _same_result(got, want):
     """A LinkQueueResult against the reference's Result, or against another LinkQueueResult."""
     for a, b in PY_FIELDS.items():

@@ -375,6 +375,9 @@ pub const SG_ROUTE_OUT_DEVICE: u32 = 2;
 pub const SG_LINK_QUEUE_CARRY: u32 = 4;
 /// sg_link_queue: cost_ps carries a longest wait per link in its second half; tail drop
 pub const SG_LINK_QUEUE_DROP: u32 = 8;
+/// sg_link_queue: enter_ns and the per-record outputs carry n_weights packets behind the records:
+/// each packet's base time in, its delay, arrival and the record that dropped it out
+pub const SG_LINK_QUEUE_PACKETS: u32 = 16;
 pub const SG_CELL_WIDE: u32 = 0xFFFF_FFFF;
 pub const SG_COMM_ID_BYTES: usize = 128;
 
@@ -515,6 +518,9 @@ unsafe extern "C" {
     /// First order: a wait is not propagated to the packet's later hops, unless flags carries
     /// SG_LINK_QUEUE_CARRY: then packet is required, n_weights bounds it, every link serves in
     /// ascending (carried enter, packet) order and the call iterates until no time moves.
+    /// With SG_LINK_QUEUE_PACKETS enter_ns, out_wait_ns, out_done_ns and out_ahead (all required) have
+    /// n_records + n_weights entries: a base time per packet in, its delay, arrival (u64::MAX: dropped)
+    /// and the record that dropped it out (0xFFFF_FFFE: arrived, 0xFFFF_FFFF: no record).
     pub fn sg_link_queue(ctx: *mut sg_ctx, flags: u32, n_links: u32, link_off: *const u64, n_records: u64,
                          enter_ns: *const u64, packet: *const u32, weight: *const u32, n_weights: u32,
                          cost_ps: *const u64, link_free_in: *const u64, out_wait_ns: *mut u64,

@@ -908,9 +908,56 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  * records only: a served done, or with SG_LINK_QUEUE_CARRY done + gap, reaching
  * 2^64 - 1; a dropped record never overflows.  SG_LINK_QUEUE_CARRY_ITERS bounds the
  * iterations as above.
- * Timers with the flag: "link_queue" (the walk), "link_queue_ahead" (the outputs). */
+ * Timers with the flag: "link_queue" (the walk), "link_queue_ahead" (the outputs).
+ *
+ * SG_LINK_QUEUE_PACKETS in flags: the result is folded onto the packets -- each packet's
+ * delay under the rates, its arrival, and the record where it was dropped.  The bit
+ * composes with SG_ROUTE_OUT_DEVICE, SG_LINK_QUEUE_CARRY and SG_LINK_QUEUE_DROP in every
+ * combination.  Without it the call is what it was, bit for bit, with the same
+ * launches; with it the first n_records entries of the per-record outputs and every
+ * per-link output equal the call without it.
+ * Inputs.  packet is required.  n_weights is the number of packets P: it bounds
+ * packet[i] whether or not weight is NULL.  enter_ns has n_records + P entries:
+ * enter_ns[n_records + p] = base_p is packet p's uncongested arrival time (a delivery
+ * round's deliver_time_ns[p]); the library only reads it.  In host mode n_records + P
+ * entries are staged.
+ * Outputs.  out_wait_ns, out_done_ns and out_ahead are all required and have
+ * n_records + P entries each; behind the records:
+ *   out_wait_ns[n_records + p] = delay(p)
+ *   out_done_ns[n_records + p] = arrive(p)
+ *   out_ahead[n_records + p]   = where(p)
+ * Definition.  R(p) is the set of records with packet[i] == p.  A record's state is
+ * read as above: served; dropped (wait 2^64 - 1, done not); absent (both 2^64 - 1);
+ * without SG_LINK_QUEUE_DROP every record is served.  All times here are the input
+ * enter_ns, not the carried ones.
+ *   drop(p)   the dropped record of R(p) with the smallest enter_ns, the smallest index
+ *             among equals; t_drop its enter_ns, +infinity when R(p) has none.
+ *   S(p)      the served records of R(p) with enter_ns < t_drop: what a first-order
+ *             result serves downstream of a drop does not count.
+ *   where(p)  the record index of drop(p); 0xFFFFFFFE when p arrived (R(p) is not empty
+ *             and nothing of it was dropped); 0xFFFFFFFF when R(p) is empty (the packet
+ *             was not counted, or it crossed no watched link).
+ *   delay(p)  with SG_LINK_QUEUE_CARRY done_l - enter_ns[l] for the record l of S(p)
+ *             with the largest enter_ns (the chain's waits and services telescope into
+ *             it); without, the sum over S(p) of done_i - enter_ns[i], wrapping: the
+ *             first-order sum of what each link adds.  0 when S(p) is empty.
+ *   arrive(p) 2^64 - 1 when p was dropped, else base_p + delay(p).  A packet with no
+ *             record keeps base_p whatever its value.
+ * Errors with the bit.  Every output untouched: a NULL packet, out_wait_ns,
+ * out_done_ns or out_ahead, SG_ERR_INVALID_ARG; n_records > 2^32 - 2, SG_ERR_CAPACITY
+ * (the two codes of where are the top two u32 values).  Found on the device, after
+ * the errors above and in their order, with their pairs: packet[i] >= n_weights (now
+ * also without weight); base_p + delay(p) of a packet that arrived reaching 2^64 - 1,
+ * SG_ERR_TIME_OVERFLOW, the pair names a record of that packet, which one is
+ * unspecified.  No index is formed from a flagged value.
+ * The packet pass runs after the outputs stand and before the flag words are read; with
+ * SG_LINK_QUEUE_CARRY they are read once more after it.
+ * Timers with the bit: "link_queue_packets" (work = records);
+ * read_timer("link_queue_lost") gives the packets the last such call found dropped,
+ * and P. */
 #define SG_LINK_QUEUE_CARRY 0x4u
 #define SG_LINK_QUEUE_DROP 0x8u
+#define SG_LINK_QUEUE_PACKETS 0x10u
 int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
                       const uint64_t* link_off, uint64_t n_records,
                       const uint64_t* enter_ns, const uint32_t* packet,
@@ -1308,6 +1355,11 @@ uint64_t sg_wire_count(const sg_wire* w);
  * packets->src_host[i], event_id = out->event_id[i], packet = packet_id ?
  * packet_id[i] : id_base + i, len = len[i]).  packet_id (device, n_packets, may
  * be NULL); len (device, n_packets): PacketRc::len() (packet.rs:388-390).
+ * A packet whose out->deliver_time_ns[i] is 2^64 - 1 adds no event (no event
+ * carries that time: EMUTIME_MAX is 2^64 - 2).  That is how a round under link
+ * rates leaves out the packets its queues dropped: out->deliver_time_ns is then
+ * sg_link_queue's arrive tail (SG_LINK_QUEUE_PACKETS).  sg_wire_count counts such a
+ * packet until the next pop, as it counts dropped packets.
  * w was created for the hosts table's n_hosts.  SG_ERR_INVALID_ARG for NULL
  * arguments; SG_ERR_CAPACITY when sg_wire_count + packets->n_packets exceeds
  * the capacity (checked on the host, so dropped packets count: conservative);

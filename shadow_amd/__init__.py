@@ -16,7 +16,7 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
 There is no CPU fallback: if libshadow_gpu.so is missing, `load()` raises.
 """
 from ._capi import LIB_PATH, ShadowGpuError, ShadowGpuUnavailable, load  # noqa: F401
-from .graph import (Context, IpAssignment, LinkQueueCarried, LinkQueueCarriedDropped, LinkQueueDropped, LinkQueueResult, NetworkGraph, PathProperties, PathTable,  # noqa: F401
+from .graph import (Context, IpAssignment, LinkQueueCarried, LinkQueueCarriedDropped, LinkQueueDropped, LinkQueueResult, NetworkGraph, PacketOutcomes, PathProperties, PathTable,  # noqa: F401
                     PathTree, RoutingInfo, cost_ps_from_bandwidth, default_context, generate_routing_info,
                     ipv4_to_u32, link_queue, queue_limit_ns, u32_to_ipv4)
 from .wire import PacketWire  # noqa: F401
@@ -25,4 +25,5 @@ from .group import Group, GroupDelivery  # noqa: F401
 __all__ = ["Context", "NetworkGraph", "PathProperties", "PathTable", "PathTree", "RoutingInfo", "IpAssignment",
            "generate_routing_info", "default_context", "load", "ShadowGpuError", "ShadowGpuUnavailable",
            "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire", "Group", "GroupDelivery", "LinkQueueResult", "LinkQueueCarried",
-           "link_queue", "cost_ps_from_bandwidth", "LinkQueueDropped", "LinkQueueCarriedDropped", "queue_limit_ns"]
+           "link_queue", "cost_ps_from_bandwidth", "LinkQueueDropped", "LinkQueueCarriedDropped", "queue_limit_ns",
+           "PacketOutcomes"]

@@ -78,6 +78,7 @@
 //   SG_LINK_SERIES_LDS | 4096 | 0 .. 8064 cells | tune | link time series: the most cells, n_slots x (n_bins + 2), a workgroup sums in an LDS matrix of its own; 0: never, every add goes to the matrix in memory
 //   SG_LINK_QUEUE_SERIAL | 0 | 0, 1 | tune | link queues: 1 takes a lane per link looping over its segment instead of the flat segmented scan
 //   SG_LINK_QUEUE_CARRY_ITERS | 4096 | 1 .. 2^31-1 | tune | link queues, carried form: the most iterations of the fixed point; reaching it is SG_ERR_CAPACITY
+//   SG_LINK_QUEUE_PACKETS_INDEX | 0 | 0, 1 | tune | link queues, the first-order packet pass: 0 folds the records onto their packets with atomics; 1 builds the carried form's index of every packet's records first and sums each packet's list in one lane
 //   SG_PATHS_STAGE | 1 | 0, 1 | tune | tree paths: 0 stores every hop record from its lane; 1 stages a wave's records in LDS and writes its span of the output with consecutive lanes
 //   SG_PATHS_STAGE_HOPS | 640 | 1 .. 1536 | tune | tree paths: records a wave stages; a wave whose span is longer stores from its lanes
 //   SG_RI_BLOCK_ROWS | n_used / 8; a group member: half its rows | >= 64, whole 64-row batches | test | RoutingInfo fill: rows per block

@@ -19,6 +19,8 @@
 // The *tile carry* is the `done` that enters a tile of the scan (k_queue_carry); *carried* is the flag's form.
 #pragma once
 
+#include <cstddef>
+
 #include "sg_internal.h"
 #include "sg_scan.h"
 
@@ -34,8 +36,10 @@ constexpr uint32_t Q_NO_LINK = 0xFFFFFFFFu;
 
 // flag words (all ones: nothing found; the smallest value wins)
 // (the carried form adds Q_DUP, the smallest record with a twin in its packet's chain, and
-// Q_CHANGED, 0 once an iteration moved an enter time)
-enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_WORDS = 5 };
+// Q_CHANGED, 0 once an iteration moved an enter time; the packet pass adds Q_PKT_OVERFLOW, the
+// smallest packet whose first-order arrival is past the range, and Q_LOST, a count from 0: the
+// packets dropped)
+enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_PKT_OVERFLOW = 5, Q_LOST = 6, Q_WORDS = 7 };
 
 // The outputs of a pass (null: not written), per record in the view's order and per link.
 struct QOuts {
@@ -69,6 +73,9 @@ struct QArgs {
   uint32_t* agg_h;
 };
 
+// (the kernels of every layer take the struct by value: a field added here moves their arguments)
+static_assert(sizeof(QArgs) == 168 && offsetof(QArgs, out) == 72 && offsetof(QArgs, flag) == 136, "QArgs keeps its layout");
+
 // A pass of the call `call` over the view (enter, packet) that writes `outs`.
 inline QArgs queue_pass(QArgs call, const u64* enter, const uint32_t* packet, const QOuts& outs) {
   call.enter = enter;
@@ -85,14 +92,14 @@ inline bool queue_serial(const QArgs& a) { return !a.agg_s; }
 // record, in an array of the drop layer's own (null) or, carried, in the sorted pass's done array;
 // the records whose enter time is all ones are then absent.  k_drop_finish reads run while it
 // writes the pass's done: the two are never one array (sg_queue_carry.hip's sorted_outs).
-struct QLocator;  // sg_queue.hip: the (link, record in the link) of a record, for an error's pair
+struct QLocator;  // sg_queue.hip: the (link, record in the link) of a record, for an error's pair; the packets lost
 // sg_queue.hip.  launch_links: link_off's check, the zeroes of the pass's per-link outputs.
 // launch_walk (timer link_queue): wait, done and the per-link sums in the scan or the serial form, or
 // under the drop rule the walk's three arrays, whose wt it returns.  queue_output_pass: the links,
 // the walk unless `walk_stands` (the last walk was this view's and holds), ahead (timer
 // link_queue_ahead).  queue_check_flags reads the flag words back -- it waits for the stream -- and
 // throws the first error: with `inputs` a bad link_off, packet index or twin; an overflow
-// (`carried`: its message).  True: no enter time moved.
+// (`carried`: its message), the packet pass's too.  True: no enter time moved.
 void launch_links(sg_ctx* ctx, const QArgs& a);
 const u64* launch_walk(sg_ctx* ctx, const QArgs& a, bool drop, u64* carried_run);
 void queue_output_pass(sg_ctx* ctx, const QArgs& a, bool drop, u64* carried_run, bool walk_stands);
@@ -102,7 +109,19 @@ void drop_launch_links(sg_ctx* ctx, const QArgs& a);
 const u64* drop_launch_walk(sg_ctx* ctx, const QArgs& a, u64* carried_run);  // the walk's waits
 void drop_launch_finish(sg_ctx* ctx, const QArgs& a, u64* carried_run);
 // sg_queue_carry.hip.  `a`: the call on the device (n > 0, flag words all ones), every output the caller takes.
-void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, QLocator& where);
+// packets: the packet pass follows, and one more read of the flag words after it.
+void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, bool packets, QLocator& where);
+// The index step alone (timer link_queue_index; it also bounds packet[i] by a.n_weights): packet p's records
+// are list[pkt_off[p]] .. list[pkt_off[p + 1]], in ascending input (enter, record) order.
+struct QChains {
+  const u64* pkt_off;
+  const uint32_t* list;
+};
+QChains queue_packet_lists(sg_ctx* ctx, const QArgs& a);
+// sg_queue_packets.hip (SG_LINK_QUEUE_PACKETS).  `a`: the call, its per-record outputs written at the input
+// indices, n_weights packets behind the n records of enter, wait, done and ahead.  next: the carried
+// form's chain successors at input indices, null first order.
+void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next);
 
 __device__ __forceinline__ u64 sat_add(u64 a, u64 b) {
   const u64 r = a + b;

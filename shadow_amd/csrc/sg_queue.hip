@@ -30,6 +30,10 @@
 // SG_LINK_QUEUE_DROP gives every link a finite buffer and drops at its tail: the unlimited scan
 // above only marks the busy periods, which are then walked from an idle server side by side
 // (finite buffers, sg_queue_drop.hip).
+//
+// SG_LINK_QUEUE_PACKETS folds the result onto the packets, behind the records of the per-record
+// arrays: each packet's delay, its arrival and where it was dropped (the packet pass,
+// sg_queue_packets.hip).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -45,6 +49,21 @@ struct QLocator {
   uint32_t n_links;
   bool dev;
   std::vector<u64> host;
+  const uint32_t* packet;  // the caller's, n entries
+  u64 n;
+  u64 lost;  // the packet pass's count, as the last read of the flag words found it
+  // a record of packet p (an error's path: the whole array is read)
+  u64 record_of(uint32_t p) {
+    std::vector<uint32_t> h;
+    const uint32_t* pk = packet;
+    if (dev) {
+      h.resize((size_t)n);
+      if (n) SG_HIP(hipMemcpy(h.data(), packet, (size_t)n * 4, hipMemcpyDeviceToHost));
+      pk = h.data();
+    }
+    const uint32_t* at = std::find(pk, pk + n, p);
+    return at == pk + n ? 0ull : (u64)(at - pk);
+  }
   void locate(u64 i, uint32_t& lk, uint32_t& at) {
     const u64* off = link_off;
     if (dev) {
@@ -237,6 +256,15 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   }
   const bool carry = (flags & SG_LINK_QUEUE_CARRY) != 0 && n != 0;  // (no record: nothing to carry)
   const bool drop = (flags & SG_LINK_QUEUE_DROP) != 0;
+  const bool packets = (flags & SG_LINK_QUEUE_PACKETS) != 0;
+  if (packets) {
+    if (!c.packet) throw Error(SG_ERR_INVALID_ARG, "SG_LINK_QUEUE_PACKETS without packet");
+    if (!c.out.wait || !c.out.done || !c.out.ahead)
+      throw Error(SG_ERR_INVALID_ARG, "SG_LINK_QUEUE_PACKETS without out_wait_ns, out_done_ns or out_ahead");
+    // (a record index shares out_ahead's tail with the two codes)
+    if (n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one call with SG_LINK_QUEUE_PACKETS takes");
+  }
+  const size_t n_rec = (size_t)n + (packets ? (size_t)c.n_weights : 0);  // enter_ns and the per-record outputs
   // (the period starts are u32 record indices, and the marks are summed by scan_counts)
   if (drop && n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one call with SG_LINK_QUEUE_DROP takes");
   const size_t nl2 = drop ? 2 * (size_t)nl : (size_t)nl;  // cost_ps, out_link_busy_ns, out_link_ahead_max
@@ -275,15 +303,15 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   call.n = n;
   call.n_weights = c.n_weights;
   call.off = (const u64*)in(c.off, ((size_t)nl + 1) * 8);
-  const u64* enter = (const u64*)in(c.enter, n * 8);
+  const u64* enter = (const u64*)in(c.enter, n_rec * 8);
   const uint32_t* packet = (const uint32_t*)in(c.packet, n * 4);
   call.weight = (const uint32_t*)in(c.weight, (size_t)c.n_weights * 4);
   call.cost = (const u64*)in(c.cost, nl2 * 8);
   call.free_in = (const u64*)in(c.free_in, (size_t)nl * 8);
   QOuts outs = {};
-  outs.wait = (u64*)out(c.out.wait, n * 8);
-  outs.done = (u64*)out(c.out.done, n * 8);
-  outs.ahead = (uint32_t*)out(c.out.ahead, n * 4);
+  outs.wait = (u64*)out(c.out.wait, n_rec * 8);
+  outs.done = (u64*)out(c.out.done, n_rec * 8);
+  outs.ahead = (uint32_t*)out(c.out.ahead, n_rec * 4);
   outs.link_free = (u64*)out(c.out.link_free, (size_t)nl * 8);
   outs.busy = (u64*)out(c.out.busy, nl2 * 8);
   outs.wmax = (u64*)out(c.out.wmax, (size_t)nl * 8);
@@ -304,14 +332,17 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
     call.agg_h = (uint32_t*)(agg + 2 * (size_t)n_tiles64);
   }
   const QArgs a = queue_pass(call, enter, packet, outs);
-  QLocator where = {c.off, nl, dev, {}};
+  QLocator where = {c.off, nl, dev, {}, c.packet, n, 0};
 
   if (carry) {
-    queue_carry(ctx, a, drop, where);
+    queue_carry(ctx, a, drop, packets, where);
   } else {
     queue_output_pass(ctx, a, drop, nullptr, false);
+    if (packets) queue_packets(ctx, a, drop, nullptr);
     queue_check_flags(ctx, a.flag, where, false, true);
   }
+  // read_timer("link_queue_lost") = (0, the packets the last call with SG_LINK_QUEUE_PACKETS found dropped, its packets)
+  if (packets) timer_set_counter(ctx, "link_queue_lost", (double)c.n_weights, where.lost, true);
   for (const Back& b : back)
     if (b.bytes) SG_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
   if (!back.empty()) SG_HIP(hipStreamSynchronize(st));
@@ -347,6 +378,14 @@ bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carri
                               " is served past 2^64 - 1 ns",
                 lk, at);
   }
+  if (h[Q_PKT_OVERFLOW] != Q_MAX) {
+    where.locate(where.record_of((uint32_t)h[Q_PKT_OVERFLOW]), lk, at);
+    throw Error(SG_ERR_TIME_OVERFLOW,
+                "packet " + std::to_string(h[Q_PKT_OVERFLOW]) + " (a record of link " + std::to_string(lk) +
+                    ") arrives past 2^64 - 1 ns",
+                lk, at);
+  }
+  where.lost = h[Q_LOST];
   return h[Q_CHANGED] == Q_MAX;
 }
 

@@ -42,6 +42,9 @@ struct CArgs {
   u64* flag;
 };
 
+// (the kernels take the struct by value: a field added here moves their arguments)
+static_assert(sizeof(CArgs) == 112 && offsetof(CArgs, next) == 72, "CArgs keeps its layout");
+
 __device__ __forceinline__ bool carry_bad(const CArgs& c) {
   return c.flag[Q_BAD_OFF] != Q_MAX || c.flag[Q_BAD_PACKET] != Q_MAX;
 }
@@ -166,32 +169,69 @@ QOuts sorted_outs(sg_ctx* ctx, const QArgs& a, bool last, bool drop) {
   return o;
 }
 
-}  // namespace
+// The index step (timer link_queue_index): every packet's records in ascending input (enter, record)
+// order in c.list, packet p's at c.pkt_off[p] .. c.pkt_off[p + 1], and with `chain` next, gap and cur.
+struct CIndex {
+  CArgs c;
+  uint4* key2;
+  uint2* work;
+  uint32_t work_cap, piece;
+  uint32_t* n_work;
+};
 
-void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, QLocator& where) {
+CIndex carry_index(sg_ctx* ctx, const QArgs& a, const uint32_t* perm, bool chain) {
   hipStream_t st = ctx->stream;
   const u64 n = a.n;
-  const uint32_t nl = a.n_links, np = a.n_weights;
-  const int cap = knob_int("SG_LINK_QUEUE_CARRY_ITERS", 4096, 1, INT_MAX);
-  const uint32_t piece = (uint32_t)knob_int("SG_LINK_TRACE_PIECE", (int)TR_PIECE_MAX, (int)TR_RANK_MAX, (int)TR_PIECE_MAX);
-  const uint64_t work_cap64 = segsort_work_cap(n, piece);
+  const uint32_t np = a.n_weights;
+  CIndex x = {};
+  x.piece = (uint32_t)knob_int("SG_LINK_TRACE_PIECE", (int)TR_PIECE_MAX, (int)TR_RANK_MAX, (int)TR_PIECE_MAX);
+  const uint64_t work_cap64 = segsort_work_cap(n, x.piece);
   if (work_cap64 > 0xFFFFFFFFull) throw Error(SG_ERR_CAPACITY, "more records than one carried call sorts");
-  const uint32_t work_cap = (uint32_t)work_cap64;
+  x.work_cap = (uint32_t)work_cap64;
   const dim3 g_rec(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), blk(Q_THREADS);
-
   // the counters and the cursors per packet and the sort's work counter: one block, zeroed
   uint32_t* ctr = ctx->qc_cnt.get<uint32_t>(2 * (size_t)np + 1);
   SG_HIP(hipMemsetAsync(ctr, 0, (2 * (size_t)np + 1) * 4, st));
-  uint32_t* n_work = ctr + 2 * (size_t)np;
+  x.n_work = ctr + 2 * (size_t)np;
   u64* pkt_off = ctx->qc_off.get<u64>((size_t)np + 2);  // (the last word: the scan's total)
   uint4* key = ctx->tr_key.get<uint4>(n);
-  uint4* key2 = ctx->tr_key2.get<uint4>(n);
-  uint2* work = ctx->tr_work.get<uint2>(work_cap);
+  x.key2 = ctx->tr_key2.get<uint4>(n);
+  x.work = ctx->tr_work.get<uint2>(x.work_cap);
+  x.c = carry_args(ctx, a, ctr, pkt_off, key, perm);
+  const CArgs& c = x.c;
+  TimedLaunch tl(ctx, "link_queue_index", (double)n);
+  hipLaunchKernelGGL(k_carry_count, g_rec, blk, 0, st, c);
+  SG_CHECK_LAUNCH();
+  scan_counts(ctx, c.cnt, np, pkt_off, pkt_off + np + 1);
+  hipLaunchKernelGGL(k_carry_fill, g_rec, blk, 0, st, c);
+  SG_CHECK_LAUNCH();
+  const TraceOut lists = {c.list, nullptr, nullptr, nullptr};
+  segsort_enqueue(ctx, pkt_off, np, (const uint4*)key, nullptr, x.key2, nullptr, lists, x.piece, x.work, x.work_cap, x.n_work);
+  if (chain) {
+    hipLaunchKernelGGL(k_carry_chain, g_rec, blk, 0, st, c);
+    SG_CHECK_LAUNCH();
+  }
+  return x;
+}
+
+}  // namespace
+
+QChains queue_packet_lists(sg_ctx* ctx, const QArgs& a) {
+  const CIndex x = carry_index(ctx, a, nullptr, false);
+  return QChains{x.c.pkt_off, x.c.list};
+}
+
+void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, bool packets, QLocator& where) {
+  hipStream_t st = ctx->stream;
+  const u64 n = a.n;
+  const uint32_t nl = a.n_links;
+  const int cap = knob_int("SG_LINK_QUEUE_CARRY_ITERS", 4096, 1, INT_MAX);
+  const dim3 g_rec(grid_for(n, Q_THREADS, 0x7FFFFFFFu)), blk(Q_THREADS);
+
   u64* s_enter = ctx->qc_enter.get<u64>(n);
   uint32_t* s_packet = ctx->qc_packet.get<uint32_t>(n);
   uint32_t* perm = ctx->qc_perm.get<uint32_t>(n);
   const TraceOut sorted = {s_packet, perm, s_enter, nullptr};
-  const CArgs c = carry_args(ctx, a, ctr, pkt_off, key, perm);
   // link_off's check alone (no output is written before the last pass), an iteration's pass, the last pass
   const QArgs check = queue_pass(a, a.enter, a.packet, QOuts{});
   const QArgs iter = queue_pass(a, s_enter, s_packet, sorted_outs(ctx, a, false, drop));
@@ -199,18 +239,8 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, QLocator& where) {
   u64* run = drop ? iter.out.done : nullptr;  // (sg_queue.h: carried_run)
 
   launch_links(ctx, check);
-  {
-    TimedLaunch tl(ctx, "link_queue_index", (double)n);
-    hipLaunchKernelGGL(k_carry_count, g_rec, blk, 0, st, c);
-    SG_CHECK_LAUNCH();
-    scan_counts(ctx, c.cnt, np, pkt_off, pkt_off + np + 1);
-    hipLaunchKernelGGL(k_carry_fill, g_rec, blk, 0, st, c);
-    SG_CHECK_LAUNCH();
-    const TraceOut chain = {c.list, nullptr, nullptr, nullptr};
-    segsort_enqueue(ctx, pkt_off, np, (const uint4*)key, nullptr, key2, nullptr, chain, piece, work, work_cap, n_work);
-    hipLaunchKernelGGL(k_carry_chain, g_rec, blk, 0, st, c);
-    SG_CHECK_LAUNCH();
-  }
+  const CIndex x = carry_index(ctx, a, perm, true);
+  const CArgs& c = x.c;
   queue_check_flags(ctx, a.flag, where, true, true);
 
   uint32_t iters = 0;
@@ -218,12 +248,12 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, QLocator& where) {
   while (!settled && iters < (uint32_t)cap) {
     iters++;
     SG_HIP(hipMemsetAsync(a.flag + Q_CHANGED, 0xff, 8, st));
-    SG_HIP(hipMemsetAsync(n_work, 0, 4, st));
+    SG_HIP(hipMemsetAsync(x.n_work, 0, 4, st));
     {
       TimedLaunch tl(ctx, "link_queue_sort", (double)n);
       hipLaunchKernelGGL(k_carry_keys, g_rec, blk, 0, st, c);
       SG_CHECK_LAUNCH();
-      segsort_enqueue(ctx, a.off, nl, (const uint4*)key, nullptr, key2, nullptr, sorted, piece, work, work_cap, n_work);
+      segsort_enqueue(ctx, a.off, nl, (const uint4*)c.key, nullptr, x.key2, nullptr, sorted, x.piece, x.work, x.work_cap, x.n_work);
     }
     const u64* wt = launch_walk(ctx, iter, drop, run);  // (the walk's waits under the drop rule, else null)
     {
@@ -245,6 +275,11 @@ void queue_carry(sg_ctx* ctx, const QArgs& a, bool drop, QLocator& where) {
   if (a.out.wait || a.out.done || a.out.ahead) {
     hipLaunchKernelGGL(k_carry_scatter, g_rec, blk, 0, st, c, last.out, a.out);
     SG_CHECK_LAUNCH();
+  }
+  if (packets) {
+    // (the outputs stand at the input indices; only an arrival past the range is left to find)
+    queue_packets(ctx, a, drop, c.next);
+    queue_check_flags(ctx, a.flag, where, true, false);
   }
 }
 

@@ -46,6 +46,9 @@ struct DArgs {
   u64* refused;
 };
 
+// (the kernels take the struct by value: a field added here moves their arguments)
+static_assert(sizeof(DArgs) == 256 && offsetof(DArgs, limit) == sizeof(QArgs), "DArgs keeps its layout");
+
 // The pass `a` under the drop rule with the layer's scratch arrays (carried_run: sg_queue.h).
 DArgs drop_args(sg_ctx* ctx, const QArgs& a, u64* carried_run) {
   DArgs d = {};

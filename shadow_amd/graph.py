@@ -269,7 +269,35 @@ class LinkQueueCarriedDropped(NamedTuple):
     iterations: int
 
 
+class PacketOutcomes(NamedTuple):
+    """What sg_link_queue gives per packet with SG_LINK_QUEUE_PACKETS (outcomes=...): delay_ns (u64,
+    what the queues add to the packet: carried, its last served crossing's done - enter; first
+    order, the sum over its served crossings up to its first drop), arrive_ns (u64, base + delay,
+    2^64 - 1 when the packet was dropped), where (u32: the record that dropped it, WHERE_ARRIVED
+    when it arrived, WHERE_NOTHING when it has no record: not counted, or no watched link on its
+    path, and arrive_ns is then its base time); lost (bool); drop_link (u32, the link of `where`,
+    2^32 - 1 when not dropped); arrive_dev, arrive_ns as an int64 device tensor for
+    PacketWire.push(deliver_time_ns=...) where the call ran on device arrays, else None."""
+    delay_ns: np.ndarray
+    arrive_ns: np.ndarray
+    where: np.ndarray
+    lost: np.ndarray
+    drop_link: np.ndarray
+    arrive_dev: object
+
+
+WHERE_ARRIVED = 0xFFFFFFFE
+WHERE_NOTHING = 0xFFFFFFFF
 _UMAX = 0xFFFFFFFFFFFFFFFF
+
+
+def _outcomes(link_off, delay, arrive, where, arrive_dev=None) -> PacketOutcomes:
+    """PacketOutcomes from the three tails (host arrays) of a call that succeeded."""
+    lost = where < np.uint32(WHERE_ARRIVED)
+    link = np.full(len(where), 0xFFFFFFFF, np.uint32)
+    if lost.any():
+        link[lost] = np.searchsorted(np.asarray(link_off, np.uint64), where[lost].astype(np.uint64), side="right") - 1
+    return PacketOutcomes(delay, arrive, where, lost, link, arrive_dev)
 
 
 def queue_limit_ns(buffer_units, cost_ps):
@@ -362,7 +390,7 @@ def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
 
 
 def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False,
-               limit_ns=None):
+               limit_ns=None, outcomes=None):
     """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
     records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
     arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
@@ -379,9 +407,12 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     limit_ns: one u64 per link, the longest wait the link's buffer holds (queue_limit_ns; 2^64 - 1:
     no limit) (SG_LINK_QUEUE_DROP).  A record that would wait longer is dropped: the server's time
     is unchanged, and with carry=True the packet's later records are absent, they enter no queue.
-    A LinkQueueDropped, with carry=True a LinkQueueCarriedDropped."""
-    if carry and packet is None:
-        raise ValueError("packet: required with carry=True")
+    A LinkQueueDropped, with carry=True a LinkQueueCarriedDropped.
+    outcomes: a u64 array of one base time per packet, its arrival without the rates
+    (SG_LINK_QUEUE_PACKETS).  packet is then required, the packets number len(outcomes), as many
+    as weight has, and the call returns (the queue result as above, a PacketOutcomes)."""
+    if (carry or outcomes is not None) and packet is None:
+        raise ValueError("packet: required with carry=True and with outcomes")
     off = np.ascontiguousarray(link_off, dtype=np.uint64)
     n_links = len(off) - 1
     if n_links < 0:
@@ -398,28 +429,47 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     nl2 = 2 * n_links if drop else n_links
     cost2 = np.concatenate([cost, _per_link_u64(limit_ns, n_links, "limit_ns")]) if drop else cost
     flags = (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | (_capi.SG_LINK_QUEUE_DROP if drop else 0)
-    res = LinkQueueResult(np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32),
+    base = None if outcomes is None else np.ascontiguousarray(outcomes, dtype=np.uint64).ravel()
+    n_rec = n
+    if base is not None:
+        if wt is not None and len(wt) != len(base):
+            raise ValueError(f"outcomes: {len(wt)} base times, one per packet as weight has them")
+        flags |= _capi.SG_LINK_QUEUE_PACKETS
+        n_rec = n + len(base)
+        enter = np.concatenate([enter, base])
+    res = LinkQueueResult(np.zeros(n_rec, np.uint64), np.zeros(n_rec, np.uint64), np.zeros(n_rec, np.uint32),
                           np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint64), np.zeros(n_links, np.uint64),
                           np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint32))
     ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
     n_weights = 0 if wt is None else len(wt)
     if carry and wt is None:
         n_weights = int(pkt.max()) + 1 if n else 0
+    if base is not None:
+        n_weights = len(base)
     check(ctx.handle, load().sg_link_queue(
-        ctx.handle, flags, n_links, ptr(off), n, ptr(enter if n else np.zeros(1, np.uint64)),
+        ctx.handle, flags, n_links, ptr(off), n, ptr(enter if n_rec else np.zeros(1, np.uint64)),
         ptr(pkt if n or pkt is None else np.zeros(1, np.uint32)), ptr(wt), n_weights, ptr(cost2),
         ptr(free), *[ptr(a) for a in res]))
+    tails = None
+    if base is not None:
+        tails = _outcomes(off, res.wait_ns[n:], res.done_ns[n:], res.ahead[n:])
+        res = res._replace(wait_ns=res.wait_ns[:n], done_ns=res.done_ns[:n], ahead=res.ahead[:n])
     if drop:
-        return _dropped(ctx, res, n_links, off, pkt, wt, cost, carry)
-    return _carried(ctx, res, off, pkt, wt, cost) if carry else res
+        queue = _dropped(ctx, res, n_links, off, pkt, wt, cost, carry)
+    else:
+        queue = _carried(ctx, res, off, pkt, wt, cost) if carry else res
+    return queue if tails is None else (queue, tails)
 
 
 def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
-                        free_ns, carry: bool = False, n_packets: int = 0, limit_ns=None):
+                        free_ns, carry: bool = False, n_packets: int = 0, limit_ns=None, base=None):
     """sg_link_queue on a device trace (torch tensors on `dev`: off, enter, packet; weight or
     None), every output taken and copied to the host.  carry: with SG_LINK_QUEUE_CARRY, a
     LinkQueueCarried; n_packets bounds the packet numbers when there is no weight.  limit_ns: with
-    SG_LINK_QUEUE_DROP, a LinkQueueDropped or LinkQueueCarriedDropped."""
+    SG_LINK_QUEUE_DROP, a LinkQueueDropped or LinkQueueCarriedDropped.  base: an int64 tensor of
+    n_packets base times on `dev` (SG_LINK_QUEUE_PACKETS); enter then has room for them behind
+    its records, where a device-to-device copy places them, weight has n_packets entries, and the
+    call returns (the queue result, a PacketOutcomes with arrive_dev)."""
     import torch
 
     up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)  # noqa: E731
@@ -428,7 +478,13 @@ def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, 
     nl2 = 2 * n_links if drop else n_links
     cost = up(np.concatenate([h_cost, _per_link_u64(limit_ns, n_links, "limit_ns")]) if drop else h_cost)
     free = None if free_ns is None else up(_per_link_u64(free_ns, n_links, "free_ns"))
-    rec = lambda dt: torch.zeros(max(n_records, 1), dtype=dt, device=dev)  # noqa: E731
+    n_tail = 0
+    if base is not None:
+        n_tail = n_packets
+        if enter.numel() < n_records + n_tail or base.numel() < n_tail or (weight is not None and weight.numel() != n_tail):
+            raise ValueError("outcomes: one base time per packet, and room for them behind the records")
+        enter[n_records:n_records + n_tail].copy_(base[:n_tail])
+    rec = lambda dt: torch.zeros(max(n_records + n_tail, 1), dtype=dt, device=dev)  # noqa: E731
     lnk = lambda dt, k=n_links: torch.zeros(max(k, 1), dtype=dt, device=dev)  # noqa: E731
     outs = [rec(torch.int64), rec(torch.int64), rec(torch.int32), lnk(torch.int64), lnk(torch.int64, nl2), lnk(torch.int64),
             lnk(torch.int64), lnk(torch.int32, nl2)]
@@ -436,21 +492,47 @@ def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, 
     torch.cuda.synchronize(dev)
     check(ctx.handle, load().sg_link_queue(
         ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) |
-        (_capi.SG_LINK_QUEUE_DROP if drop else 0), n_links, ptr(off), n_records,
-        ptr(enter), None if weight is None and not carry else ptr(packet), ptr(weight),
-        (n_packets if carry else 0) if weight is None else weight.numel(), ptr(cost),
+        (_capi.SG_LINK_QUEUE_DROP if drop else 0) | (0 if base is None else _capi.SG_LINK_QUEUE_PACKETS),
+        n_links, ptr(off), n_records,
+        ptr(enter), None if weight is None and not carry and base is None else ptr(packet), ptr(weight),
+        (n_packets if carry or base is not None else 0) if weight is None else weight.numel(), ptr(cost),
         ptr(free), *[ptr(t) for t in outs]))
-    lens = [n_records] * 3 + [n_links, nl2, n_links, n_links, nl2]
+    lens = [n_records + n_tail] * 3 + [n_links, nl2, n_links, n_links, nl2]
     dts = [np.uint64, np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32]
     res = LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
+    h_off = off.cpu().numpy().view(np.uint64)
+    tails = None
+    if base is not None:
+        tails = _outcomes(h_off, res.wait_ns[n_records:], res.done_ns[n_records:], res.ahead[n_records:],
+                          outs[1][n_records:n_records + n_tail])
+        res = res._replace(wait_ns=res.wait_ns[:n_records], done_ns=res.done_ns[:n_records], ahead=res.ahead[:n_records])
     if drop:
-        return _dropped(ctx, res, n_links, off.cpu().numpy().view(np.uint64),
-                        None if weight is None and not carry else packet[:n_records].cpu().numpy().view(np.uint32),
-                        None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost, carry)
-    if not carry:
-        return res
-    return _carried(ctx, res, off.cpu().numpy().view(np.uint64), packet[:n_records].cpu().numpy().view(np.uint32),
-                    None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost)
+        queue = _dropped(ctx, res, n_links, h_off,
+                         None if weight is None and not carry else packet[:n_records].cpu().numpy().view(np.uint32),
+                         None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost, carry)
+    elif carry:
+        queue = _carried(ctx, res, h_off, packet[:n_records].cpu().numpy().view(np.uint32),
+                         None if weight is None else weight.cpu().numpy().view(np.uint32), h_cost)
+    else:
+        queue = res
+    return queue if tails is None else (queue, tails)
+
+
+def _base_times(x, n_packets: int, dev, what: str = "outcomes"):
+    """One base time per packet as an int64 tensor on `dev`: a Deliveries (its deliver_time_ns), or
+    a u64 array or tensor."""
+    import torch
+
+    x = getattr(x, "deliver_time_ns", x)
+    if isinstance(x, torch.Tensor):
+        if x.element_size() != 8 or x.is_floating_point():
+            raise ValueError(f"{what}: a uint64 array")
+        x = x.reshape(-1).view(torch.int64).to(dev)
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).ravel().view(np.int64)).to(dev)
+    if x.numel() < n_packets:
+        raise ValueError(f"{what}: {n_packets} entries, one per packet")
+    return x[:n_packets].contiguous()
 
 
 class PathTree:
@@ -756,7 +838,7 @@ class PathTree:
         return series, outside
 
     def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
-                         carry=False, limit_ns=None):
+                         carry=False, limit_ns=None, outcomes=None):
         """The link trace of one round's batch and the FIFO queue of every link under a link rate,
         (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
         gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
@@ -770,7 +852,11 @@ class PathTree:
         unwatched link is crossed at its latency, as a link of infinite rate.
         limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP, as in
         shadow_amd.link_queue).  queue is then a LinkQueueDropped or, with carry=True, a
-        LinkQueueCarriedDropped, and the carried exit_ns is 2^64 - 1 at a dropped or absent hop."""
+        LinkQueueCarriedDropped, and the carried exit_ns is 2^64 - 1 at a dropped or absent hop.
+        outcomes: the round's Deliveries, or a u64 array or tensor of one base time per packet
+        (SG_LINK_QUEUE_PACKETS).  A PacketOutcomes is then the tuple's last entry: every packet's
+        delay and arrival under the rates and where it was dropped, folded on the device; its
+        arrive_dev is what PacketWire.push(deliver_time_ns=...) takes."""
         import torch
 
         npk = len(packets)
@@ -797,6 +883,11 @@ class PathTree:
             weight = packets.payload_len
         if weight is not None:
             weight = to_dev(weight, np.uint32, torch.int32, "weight")
+        base = None
+        if outcomes is not None:
+            base = _base_times(outcomes, npk, dev)
+            if weight is not None:
+                weight = weight.reshape(-1)[:npk]
         g, n = self._graph, len(self.nodes)
         n_links = len(g.links()[0])
         if watch is not None:
@@ -818,7 +909,8 @@ class PathTree:
         cap = 8 * npk + 64
         while True:  # a first call at a guessed capacity, a second at the total the first reported
             pkt, hop = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(2))
-            enter, leave = (torch.zeros(cap, dtype=torch.int64, device=dev) for _ in range(2))
+            # (enter with room for the base times behind the records)
+            enter, leave = (torch.zeros(cap + k, dtype=torch.int64, device=dev) for k in (0 if base is None else npk, 0))
             torch.cuda.synchronize(dev)
             rc, t = g.link_trace_packets_device(
                 hosts, self.nodes, 0, self.n_sources, pred.data_ptr(), tlat.data_ptr(), packets,
@@ -828,11 +920,14 @@ class PathTree:
                 break
             cap = t
         queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk,
-                                    limit_ns)
+                                    limit_ns, base)
+        tails = ()
+        if base is not None:
+            queue, tails = queue[0], (queue[1],)
         out = (off.cpu().numpy().view(np.uint64), pkt[:t].cpu().numpy().view(np.uint32),
                hop[:t].cpu().numpy().view(np.uint32), enter[:t].cpu().numpy().view(np.uint64),
                leave[:t].cpu().numpy().view(np.uint64), queue)
-        return out + (_exit_carried(out[4], out[3], queue),) if carry else out
+        return (out + (_exit_carried(out[4], out[3], queue),) if carry else out) + tails
 
     def path_properties(self, src: int, dst: int) -> PathProperties:
         """The left fold default() + e1 + ... + ek over the tree path's edges (graph/mod.rs:322-331),
@@ -1207,7 +1302,8 @@ class NetworkGraph:
     def link_queue_device(self, link_off_ptr: int, n_records: int, enter_ptr: int, packet_ptr: int, weight_ptr: int,
                           n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
                           ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
-                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False, limit_ns=None) -> None:
+                          wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False, limit_ns=None,
+                          outcomes: bool = False) -> None:
         """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
         device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
         packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
@@ -1222,10 +1318,15 @@ class NetworkGraph:
         (SG_LINK_QUEUE_DROP).  cost is then copied, with the limits behind it, into the doubled
         array the call takes; busy and ahead_max must have two entries per link (the second
         halves: the refused service and the drops per link), and the per-record outputs carry
-        the states as sentinels (sg_link_queue)."""
+        the states as sentinels (sg_link_queue).
+        outcomes: the result per packet as well (SG_LINK_QUEUE_PACKETS).  enter, wait, done and
+        ahead then have n_records + n_weights entries and all three outputs are required: the
+        caller puts every packet's base time behind enter's records and finds its delay, its
+        arrival and the record that dropped it behind the records of wait, done and ahead."""
         vp = lambda x: C.c_void_p(x or None)  # noqa: E731
         n_links = len(self.links()[0])
-        flags = _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0)
+        flags = _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | \
+            (_capi.SG_LINK_QUEUE_PACKETS if outcomes else 0)
         if limit_ns is not None:
             import torch
 

@@ -296,7 +296,7 @@ class Group:
         return off, pkt, mem, hop, enter, leave, total.value
 
     def link_queue_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, cost_ps, watch=None,
-                         free_ns=None, root: int = 0, carry=False, limit_ns=None):
+                         free_ns=None, root: int = 0, carry=False, limit_ns=None, outcomes=None):
         """The link trace of one sharded round and the FIFO queue of every link under a link rate,
         (link_off, packet, member, hop, enter_ns, exit_ns, queue): the first six as
         link_trace_round gives them, queue a graph.LinkQueueResult over the same records
@@ -309,10 +309,14 @@ class Group:
         exit_ns per record follows it (PathTree.link_queue_round).
         limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP), on
         root's merged trace as well; queue is then a graph.LinkQueueDropped or
-        graph.LinkQueueCarriedDropped (PathTree.link_queue_round)."""
+        graph.LinkQueueCarriedDropped (PathTree.link_queue_round).
+        outcomes: one Deliveries, or u64 array or tensor of base times, per member
+        (SG_LINK_QUEUE_PACKETS); they are concatenated in member order on root's device, as the
+        packet numbers are, and a graph.PacketOutcomes over all members' packets is the tuple's
+        last entry (PathTree.link_queue_round)."""
         import torch
 
-        from .graph import _exit_carried, _link_queue_tensors
+        from .graph import _base_times, _exit_carried, _link_queue_tensors
 
         tr = self._link_trace_tensors(graphs, hosts, rows, packets, status, watch, root)
         off, pkt, _, _, enter, _, t = tr
@@ -335,10 +339,21 @@ class Group:
                     raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
                 parts.append(w.reshape(-1)[:len(packets[m])].view(torch.int32).to(dev))
             wt = torch.cat(parts).contiguous() if parts else None
+        npk = sum(len(p) for p in packets)
+        base, tails = None, ()
+        if outcomes is not None:
+            if len(outcomes) != len(packets):
+                raise ValueError(f"outcomes: {len(outcomes)} entries for {len(packets)} members")
+            parts = [_base_times(o, len(packets[m]), dev, f"outcomes[{m}]") for m, o in enumerate(outcomes)]
+            base = torch.cat(parts).contiguous() if parts else torch.zeros(0, dtype=torch.int64, device=dev)
+            if enter.numel() < t + npk:  # (room for the base times behind the records)
+                enter = torch.cat([enter[:t], torch.zeros(npk, dtype=torch.int64, device=dev)])
         queue = _link_queue_tensors(self.contexts[root], dev, off.numel() - 1, off, t, enter, pkt, wt, cost_ps, free_ns,
-                                    carry, sum(len(p) for p in packets), limit_ns)
+                                    carry, npk, limit_ns, base)
+        if base is not None:
+            queue, tails = queue[0], (queue[1],)
         host = self._trace_to_host(*tr)
-        return host + (queue, _exit_carried(host[5], host[4], queue)) if carry else host + (queue,)
+        return (host + (queue, _exit_carried(host[5], host[4], queue)) if carry else host + (queue,)) + tails
 
     def link_series_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, t0_ns: int, bin_ns: int,
                           n_bins: int, slots=None, at: str = "enter", out=None, root: int = 0):

@@ -77,12 +77,23 @@ class PacketWire:
         its whole batch, dropped packets included)."""
         return int(load().sg_wire_count(self.handle))
 
-    def push(self, packets, out, length, packet_id=None, id_base: int = 0) -> None:
+    def push(self, packets, out, length, packet_id=None, id_base: int = 0, deliver_time_ns=None) -> None:
         """One event per delivered packet of the round (`packets`: PacketBatch, `out`: its
         Deliveries).  length: int32 device tensor, PacketRc::len() per packet; packet_id: int32
-        device tensor or None (then id_base + the packet's index).  Asynchronous."""
+        device tensor or None (then id_base + the packet's index).  deliver_time_ns: an int64
+        device tensor of n_packets that replaces out.deliver_time_ns, e.g. the arrive_dev of a
+        round under link rates (graph.PacketOutcomes); a packet whose time is 2^64 - 1 adds no
+        event.  Asynchronous: the tensor must stay alive until the stream has run the push."""
+        d = out.c_struct()
+        if deliver_time_ns is not None:
+            if deliver_time_ns.element_size() != 8 or deliver_time_ns.numel() < len(packets) or \
+                    not deliver_time_ns.is_contiguous():
+                raise ValueError(f"deliver_time_ns: a contiguous int64 device tensor of {len(packets)} entries")
+            d = type(d)()  # (out's own struct is cached: a copy carries the other times)
+            C.memmove(C.byref(d), C.byref(out.c_struct()), C.sizeof(d))
+            d.deliver_time_ns = deliver_time_ns.data_ptr()
         check(self.ctx.handle, load().sg_wire_push(
-            self.ctx.handle, self.handle, C.byref(packets.c_struct()), C.byref(out.c_struct()),
+            self.ctx.handle, self.handle, C.byref(packets.c_struct()), C.byref(d),
             packet_id.data_ptr() if packet_id is not None else None, int(id_base), length.data_ptr()))
 
     def push_records(self, recv, n_records: int, host_map=None) -> None:

@@ -378,6 +378,9 @@ pub const SG_LINK_QUEUE_DROP: u32 = 8;
 /// sg_link_queue: enter_ns and the per-record outputs carry n_weights packets behind the records:
 /// each packet's base time in, its delay, arrival and the record that dropped it out
 pub const SG_LINK_QUEUE_PACKETS: u32 = 16;
+/// sg_link_queue: with SG_LINK_QUEUE_CARRY, link_free_in carries a horizon behind the links: records whose
+/// carried enter time is below it are settled, the rest come back pending with their re-based times
+pub const SG_LINK_QUEUE_WINDOW: u32 = 32;
 pub const SG_CELL_WIDE: u32 = 0xFFFF_FFFF;
 pub const SG_COMM_ID_BYTES: usize = 128;
 

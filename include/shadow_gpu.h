@@ -954,10 +954,68 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  * SG_LINK_QUEUE_CARRY they are read once more after it.
  * Timers with the bit: "link_queue_packets" (work = records);
  * read_timer("link_queue_lost") gives the packets the last such call found dropped,
- * and P. */
+ * and P.
+ *
+ * SG_LINK_QUEUE_WINDOW in flags: the carried form is settled up to a horizon H only, and the
+ * rest comes back as pending, in the form a later call takes as input: rounds queue
+ * behind one another.  The bit requires SG_LINK_QUEUE_CARRY and composes with
+ * SG_LINK_QUEUE_DROP, SG_LINK_QUEUE_PACKETS and SG_ROUTE_OUT_DEVICE in every combination.
+ * Without it the call is what it was, bit for bit, with the same launches.
+ * Input.  link_free_in is required and has n_links + 1 entries:
+ * link_free_in[n_links] = H (host mode stages n_links + 1 entries).
+ * n_records <= 2^32 - 3.
+ * Definition.  The closed solution is the result of the same call without the bit
+ * (the carried form, with the drop rule if flagged); e'_i is record i's carried enter
+ * time there.  A record is settled when it is served or dropped in the closed solution
+ * and e'_i < H (strict), or when it is absent and the dropped record of its chain is
+ * itself settled.  Every other record is pending: e'_i >= H, or absent behind a drop
+ * that is not settled.  A packet's settled records are a prefix of its chain.  A link
+ * serves in (e', packet) order, and a record's start, its drop decision and its done
+ * depend on earlier records of that order alone: the settled records' values depend
+ * neither on the pending records nor on any record a later call adds at or after H,
+ * and the library never computes the closed solution past H.
+ * Outputs.  A settled record gets the values it gets without the bit.  A pending
+ * record gets out_wait_ns = 2^64 - 1, out_ahead = 0xFFFFFFFF and out_done_ns = r_i, its
+ * re-based enter time: for the first pending record h of a chain r_h = enter_ns[h]
+ * when h is the chain's first record, else e'_h = done + gap of its predecessor (exact:
+ * the predecessor is settled and served); for every later one r_next(i) = r_i + gap_i.
+ * The per-link outputs run over settled records only, the second halves under
+ * SG_LINK_QUEUE_DROP too; out_link_free[L] is the done of the last settled served record
+ * of L, link_free_in[L] when there is none.  out_ahead counts this call's settled
+ * served records only: a crossing still in service from an earlier call is seen
+ * through link_free_in alone, so out_ahead and out_link_ahead_max of a sequence of
+ * calls are lower bounds of the closed solution's.
+ * With SG_LINK_QUEUE_PACKETS a packet with a pending record is in flight: where(p) =
+ * 0xFFFFFFFD, delay(p) = r_h - enter_ns[h] for its first pending record h (what the
+ * queues have added so far; 0 when h is its chain's first) and arrive(p) = base_p +
+ * delay(p), the re-based base.  Every other packet is as without the bit;
+ * read_timer("link_queue_lost") counts settled drops only.
+ * Two identities.  (1) With H = 2^64 - 1 the call equals the one without the bit in
+ * every output.  (2) Re-feeding: call 1 runs over records R at H1; call 2 runs at H2
+ * >= H1 over call 1's pending records (enter_ns = r, base = call 1's re-based base,
+ * their weights), the in-flight packets renumbered in their old relative order, new
+ * records N, all with enter_ns >= H1, their packets numbered after the in-flight
+ * ones, and link_free_in = call 1's out_link_free.  The settled outputs of both calls
+ * together are then the closed solution's values for every record of R and N with e' <
+ * H2, the packets of N numbered after those of R.  By induction a sequence of rounds
+ * that ends at H = 2^64 - 1 equals one carried call over the concatenated trace.
+ * Errors keep their kinds, order and pairs.  Every output untouched: the bit without
+ * SG_LINK_QUEUE_CARRY, or a NULL link_free_in, SG_ERR_INVALID_ARG; n_records > 2^32 - 3,
+ * SG_ERR_CAPACITY (after the two).  A re-based time or an in-flight packet's
+ * re-based base reaching 2^64 - 1 is SG_ERR_TIME_OVERFLOW, pair unspecified; an
+ * overflow of the closed solution past H is not found.  No index is formed from an
+ * unchecked value.
+ * The call synchronises once per iteration, as the carried form does; an iteration
+ * sorts and scans only the records whose carried time is below H.  With t_min the
+ * smallest enter_ns below H and g_min the smallest gap, iterations <= ceil((H -
+ * t_min) / g_min) + 1.  Timers with the bit: the carried form's, over the records
+ * sorted, and "link_queue_window" (the compaction and the scatter);
+ * read_timer("link_queue_iters") as before; read_timer("link_queue_active") gives the
+ * records sorted and scanned, summed over the call's iterations, and n_records. */
 #define SG_LINK_QUEUE_CARRY 0x4u
 #define SG_LINK_QUEUE_DROP 0x8u
 #define SG_LINK_QUEUE_PACKETS 0x10u
+#define SG_LINK_QUEUE_WINDOW 0x20u
 int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
                       const uint64_t* link_off, uint64_t n_records,
                       const uint64_t* enter_ns, const uint32_t* packet,

@@ -18,12 +18,15 @@ There is no CPU fallback: if libshadow_gpu.so is missing, `load()` raises.
 from ._capi import LIB_PATH, ShadowGpuError, ShadowGpuUnavailable, load  # noqa: F401
 from .graph import (Context, IpAssignment, LinkQueueCarried, LinkQueueCarriedDropped, LinkQueueDropped, LinkQueueResult, NetworkGraph, PacketOutcomes, PathProperties, PathTable,  # noqa: F401
                     PathTree, RoutingInfo, cost_ps_from_bandwidth, default_context, generate_routing_info,
-                    ipv4_to_u32, link_queue, queue_limit_ns, u32_to_ipv4)
+                    ipv4_to_u32, link_queue, link_queue_pending, queue_limit_ns, u32_to_ipv4,
+                    WHERE_ARRIVED, WHERE_IN_FLIGHT, WHERE_NOTHING)
+from .queue_session import LinkQueueSession, SettledPackets, SettledRecords  # noqa: F401
 from .wire import PacketWire  # noqa: F401
 from .group import Group, GroupDelivery  # noqa: F401
 
 __all__ = ["Context", "NetworkGraph", "PathProperties", "PathTable", "PathTree", "RoutingInfo", "IpAssignment",
            "generate_routing_info", "default_context", "load", "ShadowGpuError", "ShadowGpuUnavailable",
            "ipv4_to_u32", "u32_to_ipv4", "LIB_PATH", "PacketWire", "Group", "GroupDelivery", "LinkQueueResult", "LinkQueueCarried",
-           "link_queue", "cost_ps_from_bandwidth", "LinkQueueDropped", "LinkQueueCarriedDropped", "queue_limit_ns",
+           "link_queue", "link_queue_pending", "LinkQueueSession", "SettledPackets", "SettledRecords", "WHERE_ARRIVED",
+           "WHERE_IN_FLIGHT", "WHERE_NOTHING", "cost_ps_from_bandwidth", "LinkQueueDropped", "LinkQueueCarriedDropped", "queue_limit_ns",
            "PacketOutcomes"]

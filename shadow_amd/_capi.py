@@ -35,6 +35,7 @@ SG_ROUTE_OUT_DEVICE = 0x2
 SG_LINK_QUEUE_CARRY = 0x4  # sg_link_queue: carry each wait to the packet's later hops
 SG_LINK_QUEUE_DROP = 0x8  # sg_link_queue: a longest wait per link (cost_ps doubled), tail drop
 SG_LINK_QUEUE_PACKETS = 0x10  # sg_link_queue: the result per packet behind the records (delay, arrive, where)
+SG_LINK_QUEUE_WINDOW = 0x20  # sg_link_queue: settle the carried form below the horizon link_free_in[n_links] only
 
 SG_PKT_DELIVERED, SG_PKT_DROP_LOSS, SG_PKT_DROP_NO_DST, SG_PKT_SIM_END = range(4)
 

@@ -143,6 +143,10 @@ struct sg_ctx {
   // the served marks, their exclusive sums, the period starts, the long periods with their
   // counter, and per record the running done and the wait; the carried form's sorted done
   sg::DevBuf qd_mark, qd_pos, qd_start, qd_long, qd_run, qd_wait, qd_done;
+  // the windowed form (SG_LINK_QUEUE_WINDOW, sg_queue_window.hip; over the carried form's arrays): the chain
+  // predecessors, the active marks with their exclusive sums, the compact link offsets, the sort's
+  // work counter
+  sg::DevBuf qw_prev, qw_act, qw_pos, qw_off, qw_ctr;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

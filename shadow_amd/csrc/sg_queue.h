@@ -38,8 +38,9 @@ constexpr uint32_t Q_NO_LINK = 0xFFFFFFFFu;
 // (the carried form adds Q_DUP, the smallest record with a twin in its packet's chain, and
 // Q_CHANGED, 0 once an iteration moved an enter time; the packet pass adds Q_PKT_OVERFLOW, the
 // smallest packet whose first-order arrival is past the range, and Q_LOST, a count from 0: the
-// packets dropped)
-enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_PKT_OVERFLOW = 5, Q_LOST = 6, Q_WORDS = 7 };
+// packets dropped; the windowed form adds Q_ACTIVE, no flag but a count: the records below the horizon
+// as the last compaction found them, read with the others in the iteration's one read)
+enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_PKT_OVERFLOW = 5, Q_LOST = 6, Q_ACTIVE = 7, Q_WORDS = 8 };
 
 // The outputs of a pass (null: not written), per record in the view's order and per link.
 struct QOuts {
@@ -99,11 +100,11 @@ struct QLocator;  // sg_queue.hip: the (link, record in the link) of a record, f
 // the walk unless `walk_stands` (the last walk was this view's and holds), ahead (timer
 // link_queue_ahead).  queue_check_flags reads the flag words back -- it waits for the stream -- and
 // throws the first error: with `inputs` a bad link_off, packet index or twin; an overflow
-// (`carried`: its message), the packet pass's too.  True: no enter time moved.
+// (`carried`: its message), the packet pass's too.  True: no enter time moved.  active: Q_ACTIVE's value.
 void launch_links(sg_ctx* ctx, const QArgs& a);
 const u64* launch_walk(sg_ctx* ctx, const QArgs& a, bool drop, u64* carried_run);
 void queue_output_pass(sg_ctx* ctx, const QArgs& a, bool drop, u64* carried_run, bool walk_stands);
-bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carried, bool inputs);
+bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carried, bool inputs, u64* active = nullptr);
 // sg_queue_drop.hip.  The walk expects the tile carries of `a` in a.agg_m (the scan form).
 void drop_launch_links(sg_ctx* ctx, const QArgs& a);
 const u64* drop_launch_walk(sg_ctx* ctx, const QArgs& a, u64* carried_run);  // the walk's waits
@@ -120,8 +121,13 @@ struct QChains {
 QChains queue_packet_lists(sg_ctx* ctx, const QArgs& a);
 // sg_queue_packets.hip (SG_LINK_QUEUE_PACKETS).  `a`: the call, its per-record outputs written at the input
 // indices, n_weights packets behind the n records of enter, wait, done and ahead.  next: the carried
-// form's chain successors at input indices, null first order.
-void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next);
+// form's chain successors at input indices, null first order.  prev: the windowed form's chain
+// predecessors (null: not windowed): a record whose wait is all ones and whose ahead is 0xFFFFFFFF is
+// pending, and its packet in flight.
+void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next, const uint32_t* prev = nullptr);
+// sg_queue_window.hip (SG_LINK_QUEUE_WINDOW over the carried form).  `a` as queue_carry's, a.free_in with
+// the horizon behind the links' entries.
+void queue_window(sg_ctx* ctx, const QArgs& a, bool drop, bool packets, QLocator& where);
 
 __device__ __forceinline__ u64 sat_add(u64 a, u64 b) {
   const u64 r = a + b;

@@ -31,6 +31,9 @@
 // above only marks the busy periods, which are then walked from an idle server side by side
 // (finite buffers, sg_queue_drop.hip).
 //
+// SG_LINK_QUEUE_WINDOW settles the carried form up to a horizon only and hands the rest back as pending,
+// in the form a later call takes as input (the windowed form, sg_queue_window.hip).
+//
 // SG_LINK_QUEUE_PACKETS folds the result onto the packets, behind the records of the per-record
 // arrays: each packet's delay, its arrival and where it was dropped (the packet pass,
 // sg_queue_packets.hip).
@@ -254,6 +257,13 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
     // (the record index is a word of the sort's key, and UINT32_MAX is its padding)
     if (n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one carried call takes");
   }
+  const bool window = (flags & SG_LINK_QUEUE_WINDOW) != 0;
+  if (window) {
+    if (!(flags & SG_LINK_QUEUE_CARRY)) throw Error(SG_ERR_INVALID_ARG, "SG_LINK_QUEUE_WINDOW without SG_LINK_QUEUE_CARRY");
+    if (!c.free_in) throw Error(SG_ERR_INVALID_ARG, "SG_LINK_QUEUE_WINDOW without link_free_in (the horizon is its last entry)");
+    // (0xFFFFFFFD in where is "in flight": a record index stays below it)
+    if (n > 0xFFFFFFFDull) throw Error(SG_ERR_CAPACITY, "more records than one call with SG_LINK_QUEUE_WINDOW takes");
+  }
   const bool carry = (flags & SG_LINK_QUEUE_CARRY) != 0 && n != 0;  // (no record: nothing to carry)
   const bool drop = (flags & SG_LINK_QUEUE_DROP) != 0;
   const bool packets = (flags & SG_LINK_QUEUE_PACKETS) != 0;
@@ -307,7 +317,7 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   const uint32_t* packet = (const uint32_t*)in(c.packet, n * 4);
   call.weight = (const uint32_t*)in(c.weight, (size_t)c.n_weights * 4);
   call.cost = (const u64*)in(c.cost, nl2 * 8);
-  call.free_in = (const u64*)in(c.free_in, (size_t)nl * 8);
+  call.free_in = (const u64*)in(c.free_in, ((size_t)nl + (window ? 1 : 0)) * 8);  // (windowed: the horizon behind the links)
   QOuts outs = {};
   outs.wait = (u64*)out(c.out.wait, n_rec * 8);
   outs.done = (u64*)out(c.out.done, n_rec * 8);
@@ -334,7 +344,12 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   const QArgs a = queue_pass(call, enter, packet, outs);
   QLocator where = {c.off, nl, dev, {}, c.packet, n, 0};
 
-  if (carry) {
+  // read_timer("link_queue_active") = (0, the records the last windowed call sorted and scanned, summed over its
+  // iterations, its records)
+  if (window) timer_set_counter(ctx, "link_queue_active", (double)n, 0u, true);
+  if (carry && window) {
+    queue_window(ctx, a, drop, packets, where);
+  } else if (carry) {
     queue_carry(ctx, a, drop, packets, where);
   } else {
     queue_output_pass(ctx, a, drop, nullptr, false);
@@ -350,9 +365,10 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
 
 }  // namespace
 
-bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carried, bool inputs) {
+bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carried, bool inputs, u64* active) {
   u64 h[Q_WORDS];
   copy_to_host(ctx, h, flag, sizeof(h));
+  if (active) *active = h[Q_ACTIVE];
   uint32_t lk, at;
   if (inputs) {
     if (h[Q_BAD_OFF] != Q_MAX) throw_bad_off(h[Q_BAD_OFF]);

@@ -15,6 +15,10 @@
 //                    delay; when there is no successor the packet arrived and the same lane stores
 //                    arrive and where; a dropped record (a chain has at most one, and nothing is
 //                    served after it) stores where and arrive.
+// Windowed (prev: the chain predecessors), a record whose wait is all ones and whose ahead is
+// 0xFFFFFFFF is pending, out_done_ns its re-based enter time, and its packet is in flight: the
+// served record before a pending one stores where, the delay so far and the re-based base, a
+// pending record that is its chain's first stores where (delay 0 and the base are k_packets_init's).
 // First order there is no chain, and a served crossing downstream of a drop does not count:
 //   k_packets_init   as above, with arrive = all ones: the cell is t_drop until the last kernel;
 //   k_packets_tdrop  under the drop rule, a lane per record: atomicMin(t_drop, enter) for a dropped one;
@@ -37,6 +41,7 @@ namespace {
 
 constexpr uint32_t P_NOTHING = 0xFFFFFFFFu;  // no record of the packet
 constexpr uint32_t P_ARRIVED = 0xFFFFFFFEu;
+constexpr uint32_t P_IN_FLIGHT = 0xFFFFFFFDu;  // windowed: a record of the packet is pending
 constexpr uint32_t P_NO_NEXT = 0xFFFFFFFFu;
 
 struct PArgs {
@@ -48,6 +53,8 @@ struct PArgs {
   const u64* wait;  // the per-record outputs, at input indices
   const u64* done;
   const uint32_t* next;  // the carried form's chain successors; null: first order
+  const uint32_t* prev;  // the windowed form's chain predecessors; null: no record is pending
+  const uint32_t* ahead;
   const u64* base;
   u64* delay;
   u64* arrive;
@@ -80,11 +87,19 @@ __global__ void __launch_bounds__(Q_THREADS) k_packets_chain(const PArgs a) {
     const uint32_t p = a.packet[i];
     if (p < a.n_packets) {
       const u64 w = a.wait[i], d = a.done[i];
-      if (!a.drop || w != Q_MAX) {
+      if (a.prev && w == Q_MAX && a.ahead[i] == P_NO_NEXT) {
+        if (a.prev[i] == P_NO_NEXT) a.where[p] = P_IN_FLIGHT;
+      } else if (!a.drop || w != Q_MAX) {
         uint32_t nx = a.next[i];
         if (nx != P_NO_NEXT && nx >= a.n) nx = P_NO_NEXT;
         const u64 delay = d - a.enter[i];
-        if (nx == P_NO_NEXT) {
+        if (a.prev && nx != P_NO_NEXT && a.wait[nx] == Q_MAX && a.ahead[nx] == P_NO_NEXT) {
+          const u64 at = sat_add(a.base[p], delay);
+          if (at == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], i);
+          a.delay[p] = delay;
+          a.arrive[p] = at;
+          a.where[p] = P_IN_FLIGHT;
+        } else if (nx == P_NO_NEXT) {
           const u64 at = sat_add(a.base[p], delay);
           if (at == Q_MAX) atomicMin(&a.flag[Q_OVERFLOW], i);
           a.delay[p] = delay;
@@ -197,7 +212,7 @@ __global__ void __launch_bounds__(Q_THREADS) k_packets_lists(const PArgs a, cons
 
 }  // namespace
 
-void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next) {
+void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next, const uint32_t* prev) {
   hipStream_t st = ctx->stream;
   PArgs p = {};
   p.n = a.n;
@@ -208,6 +223,8 @@ void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next)
   p.wait = a.out.wait;
   p.done = a.out.done;
   p.next = next;
+  p.prev = prev;
+  p.ahead = a.out.ahead;
   p.base = a.enter + a.n;
   p.delay = a.out.wait + a.n;
   p.arrive = a.out.done + a.n;

@@ -288,12 +288,24 @@ class PacketOutcomes(NamedTuple):
 
 WHERE_ARRIVED = 0xFFFFFFFE
 WHERE_NOTHING = 0xFFFFFFFF
+WHERE_IN_FLIGHT = 0xFFFFFFFD  # with a horizon: a record of the packet is pending, arrive_ns is its re-based base
 _UMAX = 0xFFFFFFFFFFFFFFFF
 
 
-def _outcomes(link_off, delay, arrive, where, arrive_dev=None) -> PacketOutcomes:
-    """PacketOutcomes from the three tails (host arrays) of a call that succeeded."""
-    lost = where < np.uint32(WHERE_ARRIVED)
+def link_queue_pending(wait_ns, ahead):
+    """The pending records of a call with a horizon (SG_LINK_QUEUE_WINDOW), from the sentinels: wait_ns
+    2^64 - 1 and ahead 2^32 - 1; done_ns is then the record's re-based enter time, the enter_ns a
+    later call takes.  Host arrays or device tensors (a u64 / u32 array, or torch's int64 / int32
+    views of one); a bool mask of the same kind."""
+    if isinstance(wait_ns, np.ndarray):
+        return (wait_ns.view(np.uint64) == np.uint64(_UMAX)) & (np.asarray(ahead).view(np.uint32) == np.uint32(0xFFFFFFFF))
+    return (wait_ns == -1) & (ahead == -1)
+
+
+def _outcomes(link_off, delay, arrive, where, arrive_dev=None, window: bool = False) -> PacketOutcomes:
+    """PacketOutcomes from the three tails (host arrays) of a call that succeeded; window: a packet
+    may be in flight, which is not lost."""
+    lost = where < np.uint32(WHERE_IN_FLIGHT if window else WHERE_ARRIVED)
     link = np.full(len(where), 0xFFFFFFFF, np.uint32)
     if lost.any():
         link[lost] = np.searchsorted(np.asarray(link_off, np.uint64), where[lost].astype(np.uint64), side="right") - 1
@@ -390,7 +402,7 @@ def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
 
 
 def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False,
-               limit_ns=None, outcomes=None):
+               limit_ns=None, outcomes=None, horizon_ns=None):
     """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
     records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
     arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
@@ -410,7 +422,16 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     A LinkQueueDropped, with carry=True a LinkQueueCarriedDropped.
     outcomes: a u64 array of one base time per packet, its arrival without the rates
     (SG_LINK_QUEUE_PACKETS).  packet is then required, the packets number len(outcomes), as many
-    as weight has, and the call returns (the queue result as above, a PacketOutcomes)."""
+    as weight has, and the call returns (the queue result as above, a PacketOutcomes).
+    horizon_ns: with carry=True, settle only the records whose carried enter time is below it
+    (SG_LINK_QUEUE_WINDOW).  Every other record is pending (link_queue_pending tells which): its wait_ns
+    is 2^64 - 1, its ahead 2^32 - 1 and its done_ns, as its enter_ns in the result, the re-based
+    enter time a later call takes; it is neither dropped nor absent.  The per-link arrays run over
+    settled records, link_free is what the later call takes as free_ns, and a packet with a pending
+    record has where == WHERE_IN_FLIGHT, delay_ns what the queues added so far and arrive_ns its
+    re-based base (LinkQueueSession keeps all this from round to round)."""
+    if horizon_ns is not None and not carry:
+        raise ValueError("horizon_ns: with carry=True")
     if (carry or outcomes is not None) and packet is None:
         raise ValueError("packet: required with carry=True and with outcomes")
     off = np.ascontiguousarray(link_off, dtype=np.uint64)
@@ -429,6 +450,11 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     nl2 = 2 * n_links if drop else n_links
     cost2 = np.concatenate([cost, _per_link_u64(limit_ns, n_links, "limit_ns")]) if drop else cost
     flags = (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | (_capi.SG_LINK_QUEUE_DROP if drop else 0)
+    if horizon_ns is not None:
+        if not 0 <= int(horizon_ns) <= _UMAX:
+            raise ValueError("horizon_ns: a u64 time")
+        flags |= _capi.SG_LINK_QUEUE_WINDOW  # (the horizon rides behind the links' free times)
+        free = np.concatenate([np.zeros(n_links, np.uint64) if free is None else free, np.array([int(horizon_ns)], np.uint64)])
     base = None if outcomes is None else np.ascontiguousarray(outcomes, dtype=np.uint64).ravel()
     n_rec = n
     if base is not None:
@@ -452,13 +478,29 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
         ptr(free), *[ptr(a) for a in res]))
     tails = None
     if base is not None:
-        tails = _outcomes(off, res.wait_ns[n:], res.done_ns[n:], res.ahead[n:])
+        tails = _outcomes(off, res.wait_ns[n:], res.done_ns[n:], res.ahead[n:], window=horizon_ns is not None)
         res = res._replace(wait_ns=res.wait_ns[:n], done_ns=res.done_ns[:n], ahead=res.ahead[:n])
     if drop:
         queue = _dropped(ctx, res, n_links, off, pkt, wt, cost, carry)
     else:
         queue = _carried(ctx, res, off, pkt, wt, cost) if carry else res
+    if horizon_ns is not None:
+        queue = _windowed(queue)
     return queue if tails is None else (queue, tails)
+
+
+def _windowed(queue):
+    """A carried result of a call with a horizon: a pending record is neither dropped nor absent, and
+    its enter_ns is its re-based enter time."""
+    pend = link_queue_pending(queue.wait_ns, queue.ahead)
+    if not pend.any():
+        return queue
+    enter = queue.enter_ns.copy()
+    enter[pend] = queue.done_ns[pend]
+    queue = queue._replace(enter_ns=enter)
+    if isinstance(queue, LinkQueueCarriedDropped):
+        queue = queue._replace(dropped=queue.dropped & ~pend, absent=queue.absent & ~pend)
+    return queue
 
 
 def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
@@ -516,6 +558,90 @@ def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, 
     else:
         queue = res
     return queue if tails is None else (queue, tails)
+
+
+def _ahead_again(link_off, enter, packet, done, served, present):
+    """sg_link_queue's ahead of every present (served or dropped) record from a carried result on
+    host arrays: the served records before it in its link's (carried enter, packet) order whose
+    done is past its enter time.  A link's done times never fall along that order."""
+    off = np.asarray(link_off).astype(np.int64)
+    ahead = np.zeros(len(enter), np.uint32)
+    for lk in np.flatnonzero(np.diff(off) > 0):
+        idx = np.arange(off[lk], off[lk + 1])
+        idx = idx[present[idx]]
+        order = idx[np.lexsort((packet[idx], enter[idx]))]
+        srv = served[order]
+        before = np.cumsum(srv) - srv
+        gone = np.minimum(np.searchsorted(done[order][srv], enter[order], side="right"), before)
+        ahead[order] = (before - gone).astype(np.uint32)
+    return ahead
+
+
+def _step_windows(s, off, n: int, enter, packet, weight, base, window_ns: int, settled, max_calls=None) -> int:
+    """One device trace through the session s window by window: the whole trace goes in with the
+    first call, at the horizon (first enter time) + window_ns; every later call only steps the
+    horizon by window_ns, from the earliest pending record where that lies past the last horizon.
+    settled(SettledPackets, SettledRecords) takes every call's results.  Returns the calls made
+    (max_calls: stop there, with records still pending)."""
+    import torch
+
+    sign = torch.tensor(-2**63, dtype=torch.int64, device=s.dev)
+    umin = lambda t: int((t ^ sign).min() ^ sign) & _UMAX  # noqa: E731
+    H = min(umin(enter[:n]) + window_ns, _UMAX) if n else _UMAX
+    calls = 0
+    while True:
+        settled(*(s.advance(off, enter[:n], packet[:n], weight, base, H) if not calls else s.advance(None, None, None, None, None, H)))
+        calls += 1
+        if not s.pending or H == _UMAX or calls == max_calls:
+            return calls
+        H = min(max(H, umin(s._rec["enter"])) + window_ns, _UMAX)
+
+
+def _link_queue_windows(ctx: "Context", dev, n_links: int, off, n: int, enter, packet, weight, cost_ps, free_ns, n_packets: int,
+                        limit_ns, base, window_ns: int):
+    """A device trace solved window by window through a LinkQueueSession (PathTree.link_queue_round,
+    window_ns): _link_queue_tensors' result with carry."""
+    import torch
+
+    from .queue_session import LinkQueueSession
+
+    s = LinkQueueSession(ctx, cost_ps, limit_ns, free_ns, n_links=n_links, device=dev)
+    wait, done = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    delay, arrive, where = np.zeros(n_packets, np.uint64), np.zeros(n_packets, np.uint64), np.zeros(n_packets, np.uint32)
+    arrive_dev = torch.zeros(n_packets, dtype=torch.int64, device=dev)
+    ones = torch.ones(n_packets, dtype=torch.int32, device=dev) if weight is None else weight.reshape(-1)[:n_packets]
+    zero = torch.zeros(n_packets, dtype=torch.int64, device=dev) if base is None else base
+
+    def settled(pk, rc):
+        wait[rc.record], done[rc.record] = rc.wait_ns, rc.done_ns
+        delay[pk.packet], arrive[pk.packet], where[pk.packet] = pk.delay_ns, pk.arrive_ns, pk.where
+        arrive_dev[torch.from_numpy(pk.packet).to(dev)] = pk.arrive_dev
+
+    _step_windows(s, off, n, enter, packet, ones, zero, window_ns, settled)
+    h_off = off.cpu().numpy().view(np.uint64)
+    h_pkt = packet[:n].cpu().numpy().view(np.uint32)
+    h_wt = None if weight is None else weight.cpu().numpy().view(np.uint32)
+    h_cost = _per_link_u64(cost_ps, n_links, "cost_ps")
+    sums = s.link_sums
+    out = wait == np.uint64(_UMAX)
+    present = ~(out & (done == np.uint64(_UMAX)))
+    srv = ~out
+    e = done.copy()  # (the carried enter time: a dropped record's done is its own)
+    if srv.any():
+        e[srv] = done[srv] - _service_ns(h_off, n, h_pkt, h_wt, h_cost)[srv] - wait[srv]
+    ahead = _ahead_again(h_off, e, h_pkt, done, srv, present)
+    amax = np.zeros(n_links, np.uint32)
+    if srv.any():
+        link = np.repeat(np.arange(n_links), np.diff(h_off.astype(np.int64)))
+        np.maximum.at(amax, link[srv], ahead[srv])
+    drop = limit_ns is not None
+    res = LinkQueueResult(wait, done, ahead, s.link_free.copy(),
+                          np.concatenate([sums["busy_ns"], sums["refused_ns"]]) if drop else sums["busy_ns"],
+                          sums["wait_max_ns"], sums["wait_sum_ns"],
+                          np.concatenate([amax, sums["drops"].astype(np.uint32)]) if drop else amax)
+    queue = _dropped(ctx, res, n_links, h_off, h_pkt, h_wt, h_cost, True) if drop else _carried(ctx, res, h_off, h_pkt, h_wt, h_cost)
+    queue = queue._replace(iterations=s.iterations)
+    return queue if base is None else (queue, _outcomes(h_off, delay, arrive, where, arrive_dev))
 
 
 def _base_times(x, n_packets: int, dev, what: str = "outcomes"):
@@ -837,26 +963,12 @@ class PathTree:
             int(bin_ns), int(n_bins), series.ctypes.data, outside.ctypes.data))
         return series, outside
 
-    def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
-                         carry=False, limit_ns=None, outcomes=None):
-        """The link trace of one round's batch and the FIFO queue of every link under a link rate,
-        (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
-        gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
-        between the two calls (sg_link_trace_packets, then sg_link_queue).  weight as in
-        link_load_round: None (every crossing weighs 1), "payload" or a u32 array per packet;
-        cost_ps and free_ns as in shadow_amd.link_queue; hosts, packets, status and watch as in
-        link_trace_round.  First order: a crossing's wait is not added to the packet's later hops.
-        carry=True: it is (SG_LINK_QUEUE_CARRY).  queue is then a LinkQueueCarried, and a seventh
-        entry follows it: the carried exit_ns per record, exit_ns + (done_ns - enter_ns), when the
-        crossing leaves its link under the rates; a packet's last hop's value is its arrival.  An
-        unwatched link is crossed at its latency, as a link of infinite rate.
-        limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP, as in
-        shadow_amd.link_queue).  queue is then a LinkQueueDropped or, with carry=True, a
-        LinkQueueCarriedDropped, and the carried exit_ns is 2^64 - 1 at a dropped or absent hop.
-        outcomes: the round's Deliveries, or a u64 array or tensor of one base time per packet
-        (SG_LINK_QUEUE_PACKETS).  A PacketOutcomes is then the tuple's last entry: every packet's
-        delay and arrival under the rates and where it was dropped, folded on the device; its
-        arrive_dev is what PacketWire.push(deliver_time_ns=...) takes."""
+    def link_trace_device(self, hosts, packets, status=None, weight=None, watch=None, tail: int = 0):
+        """The link trace of one round's batch, left on the device (sg_link_trace_packets): (link_off,
+        the number of records t, enter, packet, weight, hop, exit) as torch tensors of at least t
+        entries -- int64 / int32 views of the u64 / u32 arrays; enter with `tail` more entries
+        behind its capacity; weight per packet, None where every crossing weighs 1.  hosts,
+        packets, status, weight and watch as in link_queue_round."""
         import torch
 
         npk = len(packets)
@@ -883,11 +995,8 @@ class PathTree:
             weight = packets.payload_len
         if weight is not None:
             weight = to_dev(weight, np.uint32, torch.int32, "weight")
-        base = None
-        if outcomes is not None:
-            base = _base_times(outcomes, npk, dev)
-            if weight is not None:
-                weight = weight.reshape(-1)[:npk]
+        if weight is not None and tail:
+            weight = weight.reshape(-1)[:npk]
         g, n = self._graph, len(self.nodes)
         n_links = len(g.links()[0])
         if watch is not None:
@@ -910,7 +1019,7 @@ class PathTree:
         while True:  # a first call at a guessed capacity, a second at the total the first reported
             pkt, hop = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(2))
             # (enter with room for the base times behind the records)
-            enter, leave = (torch.zeros(cap + k, dtype=torch.int64, device=dev) for k in (0 if base is None else npk, 0))
+            enter, leave = (torch.zeros(cap + k, dtype=torch.int64, device=dev) for k in (tail, 0))
             torch.cuda.synchronize(dev)
             rc, t = g.link_trace_packets_device(
                 hosts, self.nodes, 0, self.n_sources, pred.data_ptr(), tlat.data_ptr(), packets,
@@ -919,8 +1028,53 @@ class PathTree:
             if rc != _capi.SG_ERR_CAPACITY or t <= cap:
                 break
             cap = t
-        queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk,
-                                    limit_ns, base)
+        return off, t, enter, pkt, weight, hop, leave
+
+    def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
+                         carry=False, limit_ns=None, outcomes=None, window_ns=None):
+        """The link trace of one round's batch and the FIFO queue of every link under a link rate,
+        (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
+        gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
+        between the two calls (sg_link_trace_packets, then sg_link_queue).  weight as in
+        link_load_round: None (every crossing weighs 1), "payload" or a u32 array per packet;
+        cost_ps and free_ns as in shadow_amd.link_queue; hosts, packets, status and watch as in
+        link_trace_round.  First order: a crossing's wait is not added to the packet's later hops.
+        carry=True: it is (SG_LINK_QUEUE_CARRY).  queue is then a LinkQueueCarried, and a seventh
+        entry follows it: the carried exit_ns per record, exit_ns + (done_ns - enter_ns), when the
+        crossing leaves its link under the rates; a packet's last hop's value is its arrival.  An
+        unwatched link is crossed at its latency, as a link of infinite rate.
+        limit_ns: one u64 per link, the longest wait its buffer holds (SG_LINK_QUEUE_DROP, as in
+        shadow_amd.link_queue).  queue is then a LinkQueueDropped or, with carry=True, a
+        LinkQueueCarriedDropped, and the carried exit_ns is 2^64 - 1 at a dropped or absent hop.
+        outcomes: the round's Deliveries, or a u64 array or tensor of one base time per packet
+        (SG_LINK_QUEUE_PACKETS).  A PacketOutcomes is then the tuple's last entry: every packet's
+        delay and arrival under the rates and where it was dropped, folded on the device; its
+        arrive_dev is what PacketWire.push(deliver_time_ns=...) takes.
+        window_ns: with carry=True, solve the trace window by window: a LinkQueueSession takes the
+        whole trace and its horizon steps by window_ns from the first record on (past a stretch in
+        which nothing is pending it jumps to the next pending record), every call sorting and
+        scanning only the records below its horizon.  The result is the one carry=True gives, but
+        for `iterations`, the calls' sum.  A call counts `ahead` over its own settled records
+        only, so ahead and link_ahead_max are counted again here on the host, from the settled
+        carried enter and done times."""
+        import torch  # noqa: F401
+
+        if window_ns is not None and (not carry or int(window_ns) < 1):
+            raise ValueError("window_ns: a positive number of ns, with carry=True")
+
+        npk = len(packets)
+        dev = packets.src_host.device
+        base = None if outcomes is None else _base_times(outcomes, npk, dev)
+        off, t, enter, pkt, weight, hop, leave = self.link_trace_device(hosts, packets, status, weight, watch,
+                                                                        0 if base is None else npk)
+        g = self._graph
+        n_links = off.numel() - 1
+        if window_ns is not None:
+            queue = _link_queue_windows(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, npk, limit_ns, base,
+                                        int(window_ns))
+        else:
+            queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk,
+                                        limit_ns, base)
         tails = ()
         if base is not None:
             queue, tails = queue[0], (queue[1],)
@@ -1303,7 +1457,7 @@ class NetworkGraph:
                           n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
                           ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
                           wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False, limit_ns=None,
-                          outcomes: bool = False) -> None:
+                          outcomes: bool = False, horizon_ns=None) -> None:
         """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
         device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
         packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
@@ -1322,11 +1476,31 @@ class NetworkGraph:
         outcomes: the result per packet as well (SG_LINK_QUEUE_PACKETS).  enter, wait, done and
         ahead then have n_records + n_weights entries and all three outputs are required: the
         caller puts every packet's base time behind enter's records and finds its delay, its
-        arrival and the record that dropped it behind the records of wait, done and ahead."""
+        arrival and the record that dropped it behind the records of wait, done and ahead.
+        horizon_ns: with carry, settle only the records whose carried enter time is below it
+        (SG_LINK_QUEUE_WINDOW; link_queue tells what the pending ones get).  free_in is then copied, with the
+        horizon behind it, into the array of one more entry the call takes."""
         vp = lambda x: C.c_void_p(x or None)  # noqa: E731
         n_links = len(self.links()[0])
         flags = _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | \
             (_capi.SG_LINK_QUEUE_PACKETS if outcomes else 0)
+        if horizon_ns is not None:
+            import torch
+
+            if not carry or not 0 <= int(horizon_ns) <= _UMAX:
+                raise ValueError("horizon_ns: a u64 time, with carry")
+            h = np.array([int(horizon_ns)], np.uint64).view(np.int64)
+            if free_in_ptr:
+                class _Free:  # the n_links u64 at free_in_ptr, for torch
+                    __cuda_array_interface__ = {"shape": (n_links,), "typestr": "<i8", "data": (int(free_in_ptr), False),
+                                                "version": 2}
+                old_free = torch.as_tensor(_Free(), device="cuda")
+            else:
+                old_free = torch.zeros(n_links, dtype=torch.int64, device="cuda")
+            free2 = torch.cat([old_free, torch.from_numpy(h).to(old_free.device)]).contiguous()
+            torch.cuda.synchronize(old_free.device)
+            free_in_ptr = free2.data_ptr()
+            flags |= _capi.SG_LINK_QUEUE_WINDOW
         if limit_ns is not None:
             import torch
 

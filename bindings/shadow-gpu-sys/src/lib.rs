@@ -381,6 +381,10 @@ pub const SG_LINK_QUEUE_PACKETS: u32 = 16;
 /// sg_link_queue: with SG_LINK_QUEUE_CARRY, link_free_in carries a horizon behind the links: records whose
 /// carried enter time is below it are settled, the rest come back pending with their re-based times
 pub const SG_LINK_QUEUE_WINDOW: u32 = 32;
+/// sg_link_queue: cost_ps carries (t0_ns, bin_ns, n_bins, n_slots) and a slot per link behind its entries, and
+/// out_link_busy_ns a matrix behind its own: busy time, waiting time, weight served and weight dropped per
+/// slot and time bin, added on the device
+pub const SG_LINK_QUEUE_SERIES: u32 = 64;
 pub const SG_CELL_WIDE: u32 = 0xFFFF_FFFF;
 pub const SG_COMM_ID_BYTES: usize = 128;
 

@@ -1011,11 +1011,68 @@ int32_t sg_link_series_packets(sg_ctx* ctx, sg_net* net, sg_hosts* hosts,
  * t_min) / g_min) + 1.  Timers with the bit: the carried form's, over the records
  * sorted, and "link_queue_window" (the compaction and the scatter);
  * read_timer("link_queue_iters") as before; read_timer("link_queue_active") gives the
- * records sorted and scanned, summed over the call's iterations, and n_records. */
+ * records sorted and scanned, summed over the call's iterations, and n_records.
+ *
+ * SG_LINK_QUEUE_SERIES in flags: the result gets a time axis -- under the rates, per slot of
+ * watched links and per time bin, the server's busy time, the time-integral of the waiting
+ * queue, the weight served and the weight dropped, summed on the device into a matrix that
+ * stays there across calls and rounds.  The bit composes with SG_ROUTE_OUT_DEVICE,
+ * SG_LINK_QUEUE_CARRY, SG_LINK_QUEUE_DROP, SG_LINK_QUEUE_PACKETS and SG_LINK_QUEUE_WINDOW in every
+ * combination.  Without it the call is what it was, bit for bit, with the same launches;
+ * with it every other output equals the call without it.
+ * Input.  Let c0 = n_links (2 * n_links with SG_LINK_QUEUE_DROP).  cost_ps has four more u64
+ * entries: cost_ps[c0] = t0_ns, cost_ps[c0 + 1] = bin_ns, cost_ps[c0 + 2] = n_bins (B),
+ * cost_ps[c0 + 3] = n_slots.  n_slots == 0 is the identity map, S = n_links.  Otherwise S =
+ * n_slots and n_links more entries follow: cost_ps[c0 + 4 + L] is link L's slot, a value
+ * below S, or 2^64 - 1 for a link that is not watched; several links may share a slot.
+ * Host mode stages the tail too.
+ * Output.  out_wait_ns, out_done_ns and out_link_busy_ns are required, with
+ * SG_LINK_QUEUE_WINDOW out_ahead as well (it tells a pending record from a dropped one).
+ * out_link_busy_ns has c0 + 4 * S * (B + 2) entries; behind the per-link values lies
+ * M[k][s][c] = out_link_busy_ns[c0 + (k * S + s) * (B + 2) + c]: plane k in 0..3, slot s,
+ * column c in 0..B-1 for the bin T_c = [t0 + c * bin_ns, t0 + (c + 1) * bin_ns), column B for
+ * the time before t0_ns, column B + 1 for the time at or after t0 + B * bin_ns.  All interval
+ * arithmetic is as if unbounded: t0 + B * bin_ns may pass 2^64, and the decision is by the
+ * quotient, as in sg_link_series_packets.
+ * For every record i of a watched link with slot s the pass reads the call's own result;
+ * w_i = weight[packet[i]] (1 when weight is NULL), s_i the service time as above.
+ *   served   start_i = done_i - s_i, e'_i = start_i - wait_i (first order: enter_ns[i]).
+ *            plane 0, busy_ns:  column c gets |[start_i, done_i) ∩ T_c|
+ *            plane 1, wait_ns:  column c gets |[e'_i, start_i) ∩ T_c|
+ *            plane 2, served:   the column of done_i gets w_i
+ *   dropped  plane 3, dropped:  the column of e'_i (= out_done_ns[i]) gets w_i
+ *   absent, pending: nothing.
+ * Plane 0 divided by bin_ns is the link's utilisation in that bin, plane 1 divided by bin_ns
+ * its mean number waiting.  All sums are u64 and wrap.  In device mode they are ADDED to what M
+ * holds; in host mode the device sums start at zero and are added into the host array's tail
+ * (the head is written as before).  n_records == 0 is legal and leaves M as it is.
+ * IDENTITIES.  For every slot, summed over its links and over all B + 2 columns: plane 0
+ * equals out_link_busy_ns[L]; plane 1 equals out_link_wait_sum_ns[L] mod 2^64; with unit
+ * weights plane 3 equals the drop counts out_link_ahead_max[n_links + L] and plane 2 the
+ * number served.  From a zeroed matrix a slot of one link has M[0][s][c] <= bin_ns for c < B.
+ * With SG_LINK_QUEUE_WINDOW only settled records count, each with the closed solution's values:
+ * the matrices of a sequence of re-fed calls that ends at H = 2^64 - 1 sum to the matrix of
+ * one carried call over the concatenated trace, bit for bit.
+ * Errors with the bit.  Found on the host, every output untouched, after the argument errors
+ * above and before link_off's check, in this order: the bit without out_wait_ns, out_done_ns
+ * or out_link_busy_ns, or with SG_LINK_QUEUE_WINDOW and no out_ahead, SG_ERR_INVALID_ARG;
+ * bin_ns == 0 or n_bins == 0, SG_ERR_INVALID_ARG; n_bins or n_slots >= 2^32, or S * (B + 2) >
+ * 2^31, SG_ERR_CAPACITY; in host mode a slot value >= S other than 2^64 - 1,
+ * SG_ERR_INVALID_ARG with the pair (link, UINT32_MAX), the smallest such link.  In device
+ * mode the four header words are READ BACK BEFORE THE FIRST LAUNCH: one more synchronisation.
+ * Found on the device, after every error the call has without the bit: a bad slot value of
+ * a link that has a record, reported as above; it is treated as not watched, and no index is
+ * formed from it.
+ * The pass runs after the outputs stand at the input indices and before the flag words are
+ * read; with SG_LINK_QUEUE_CARRY they are read once more after it.  Its cost per record does
+ * not depend on the bins a wait or a service spans.
+ * Timers with the bit: "link_queue_series" (work = records);
+ * read_timer("link_queue_series_cells") gives S * (B + 2). */
 #define SG_LINK_QUEUE_CARRY 0x4u
 #define SG_LINK_QUEUE_DROP 0x8u
 #define SG_LINK_QUEUE_PACKETS 0x10u
 #define SG_LINK_QUEUE_WINDOW 0x20u
+#define SG_LINK_QUEUE_SERIES 0x40u
 int32_t sg_link_queue(sg_ctx* ctx, uint32_t flags, uint32_t n_links,
                       const uint64_t* link_off, uint64_t n_records,
                       const uint64_t* enter_ns, const uint32_t* packet,

@@ -36,6 +36,7 @@ SG_LINK_QUEUE_CARRY = 0x4  # sg_link_queue: carry each wait to the packet's late
 SG_LINK_QUEUE_DROP = 0x8  # sg_link_queue: a longest wait per link (cost_ps doubled), tail drop
 SG_LINK_QUEUE_PACKETS = 0x10  # sg_link_queue: the result per packet behind the records (delay, arrive, where)
 SG_LINK_QUEUE_WINDOW = 0x20  # sg_link_queue: settle the carried form below the horizon link_free_in[n_links] only
+SG_LINK_QUEUE_SERIES = 0x40  # sg_link_queue: busy, waiting, served and dropped per slot and time bin behind out_link_busy_ns
 
 SG_PKT_DELIVERED, SG_PKT_DROP_LOSS, SG_PKT_DROP_NO_DST, SG_PKT_SIM_END = range(4)
 

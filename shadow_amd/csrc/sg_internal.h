@@ -147,6 +147,9 @@ struct sg_ctx {
   // predecessors, the active marks with their exclusive sums, the compact link offsets, the sort's
   // work counter
   sg::DevBuf qw_prev, qw_act, qw_pos, qw_off, qw_ctr;
+  // the time series (SG_LINK_QUEUE_SERIES, sg_queue_series.hip): the difference array of a call, zeroed by it,
+  // and the chunk sums of the row pass over long rows
+  sg::DevBuf qs_diff, qs_part;
   // sg_routing_info_fill: double-buffered device row blocks, copied to the host
   // on copy_stream while the next block computes
   sg::DevBuf r_stage_lat[2], r_stage_loss[2], r_stage_pack[2];

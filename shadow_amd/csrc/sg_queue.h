@@ -39,8 +39,9 @@ constexpr uint32_t Q_NO_LINK = 0xFFFFFFFFu;
 // Q_CHANGED, 0 once an iteration moved an enter time; the packet pass adds Q_PKT_OVERFLOW, the
 // smallest packet whose first-order arrival is past the range, and Q_LOST, a count from 0: the
 // packets dropped; the windowed form adds Q_ACTIVE, no flag but a count: the records below the horizon
-// as the last compaction found them, read with the others in the iteration's one read)
-enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_PKT_OVERFLOW = 5, Q_LOST = 6, Q_ACTIVE = 7, Q_WORDS = 8 };
+// as the last compaction found them, read with the others in the iteration's one read; the time series
+// adds Q_BAD_SLOT, the smallest link whose slot is neither below the slots nor all ones)
+enum { Q_BAD_OFF = 0, Q_BAD_PACKET = 1, Q_OVERFLOW = 2, Q_DUP = 3, Q_CHANGED = 4, Q_PKT_OVERFLOW = 5, Q_LOST = 6, Q_ACTIVE = 7, Q_BAD_SLOT = 8, Q_WORDS = 9 };
 
 // The outputs of a pass (null: not written), per record in the view's order and per link.
 struct QOuts {
@@ -128,6 +129,20 @@ void queue_packets(sg_ctx* ctx, const QArgs& a, bool drop, const uint32_t* next,
 // sg_queue_window.hip (SG_LINK_QUEUE_WINDOW over the carried form).  `a` as queue_carry's, a.free_in with
 // the horizon behind the links' entries.
 void queue_window(sg_ctx* ctx, const QArgs& a, bool drop, bool packets, QLocator& where);
+// sg_queue_series.hip (SG_LINK_QUEUE_SERIES).  queue_series_plan: the four header words behind cost_ps'
+// c0 entries (cost_tail; dev: device memory, read back, which waits for the stream), checked, and in
+// host mode the slot map behind them.  queue_series (timer link_queue_series): `a` the call, its
+// per-record outputs written at the input indices, the slot map behind the header in a.cost and the
+// matrix behind the c0 entries of a.out.busy; it adds into the matrix and flags a bad slot value in
+// Q_BAD_SLOT, which queue_check_flags reports after every other error.
+struct QSeries {
+  u64 t0, bin;
+  uint32_t n_bins, n_slots;  // n_slots: S, n_links under the identity map
+  bool mapped;               // a slot per link follows the header
+  u64 cells;                 // S (n_bins + 2), a plane of the matrix
+};
+QSeries queue_series_plan(sg_ctx* ctx, const u64* cost_tail, bool dev, uint32_t n_links);
+void queue_series(sg_ctx* ctx, const QArgs& a, const QSeries& s, bool drop, bool window);
 
 __device__ __forceinline__ u64 sat_add(u64 a, u64 b) {
   const u64 r = a + b;

@@ -37,6 +37,10 @@
 // SG_LINK_QUEUE_PACKETS folds the result onto the packets, behind the records of the per-record
 // arrays: each packet's delay, its arrival and where it was dropped (the packet pass,
 // sg_queue_packets.hip).
+//
+// SG_LINK_QUEUE_SERIES sums the result per slot of watched links and per time bin into a matrix behind
+// out_link_busy_ns: busy time, waiting time, weight served, weight dropped (the time series,
+// sg_queue_series.hip).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -55,6 +59,7 @@ struct QLocator {
   const uint32_t* packet;  // the caller's, n entries
   u64 n;
   u64 lost;  // the packet pass's count, as the last read of the flag words found it
+  u64 bad_slot = Q_MAX;  // the time series' flag word, likewise
   // a record of packet p (an error's path: the whole array is read)
   u64 record_of(uint32_t p) {
     std::vector<uint32_t> h;
@@ -278,6 +283,18 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   // (the period starts are u32 record indices, and the marks are summed by scan_counts)
   if (drop && n > 0xFFFFFFFEull) throw Error(SG_ERR_CAPACITY, "more records than one call with SG_LINK_QUEUE_DROP takes");
   const size_t nl2 = drop ? 2 * (size_t)nl : (size_t)nl;  // cost_ps, out_link_busy_ns, out_link_ahead_max
+  // the time series: the header and the slot map behind cost_ps, the matrix behind out_link_busy_ns
+  const bool series = (flags & SG_LINK_QUEUE_SERIES) != 0;
+  QSeries sr = {};
+  size_t cost_tail = 0, busy_tail = 0;
+  if (series) {
+    if (!c.out.wait || !c.out.done || !c.out.busy || (window && !c.out.ahead))
+      throw Error(SG_ERR_INVALID_ARG,
+                  "SG_LINK_QUEUE_SERIES without out_wait_ns, out_done_ns or out_link_busy_ns (with SG_LINK_QUEUE_WINDOW: or out_ahead)");
+    sr = queue_series_plan(ctx, c.cost + nl2, dev, nl);
+    cost_tail = 4 + (sr.mapped ? (size_t)nl : 0);
+    busy_tail = 4 * (size_t)sr.cells;
+  }
   if (!dev) {
     const u64 bad = bad_link_off(c.off, nl, n);
     if (bad != Q_MAX) throw_bad_off(bad);
@@ -301,10 +318,11 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
     if (bytes) SG_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, st));
     return d;
   };
-  auto out = [&](void* p, size_t bytes) -> void* {
+  // (tail: bytes of the device copy behind the output's own, not copied back here)
+  auto out = [&](void* p, size_t bytes, size_t tail = 0) -> void* {
     sg::DevBuf& b = ctx->q_buf[slot++];
     if (!p || dev) return p;
-    char* d = b.get<char>(bytes);
+    char* d = b.get<char>(bytes + tail);
     back.push_back(Back{p, d, bytes});
     return d;
   };
@@ -316,14 +334,16 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   const u64* enter = (const u64*)in(c.enter, n_rec * 8);
   const uint32_t* packet = (const uint32_t*)in(c.packet, n * 4);
   call.weight = (const uint32_t*)in(c.weight, (size_t)c.n_weights * 4);
-  call.cost = (const u64*)in(c.cost, nl2 * 8);
+  call.cost = (const u64*)in(c.cost, (nl2 + cost_tail) * 8);
   call.free_in = (const u64*)in(c.free_in, ((size_t)nl + (window ? 1 : 0)) * 8);  // (windowed: the horizon behind the links)
   QOuts outs = {};
   outs.wait = (u64*)out(c.out.wait, n_rec * 8);
   outs.done = (u64*)out(c.out.done, n_rec * 8);
   outs.ahead = (uint32_t*)out(c.out.ahead, n_rec * 4);
   outs.link_free = (u64*)out(c.out.link_free, (size_t)nl * 8);
-  outs.busy = (u64*)out(c.out.busy, nl2 * 8);
+  outs.busy = (u64*)out(c.out.busy, nl2 * 8, busy_tail * 8);
+  // (host mode: the matrix's device sums start at zero and are added into the host array's tail)
+  if (series && !dev && busy_tail) SG_HIP(hipMemsetAsync(outs.busy + nl2, 0, busy_tail * 8, st));
   outs.wmax = (u64*)out(c.out.wmax, (size_t)nl * 8);
   outs.wsum = (u64*)out(c.out.wsum, (size_t)nl * 8);
   outs.amax = (uint32_t*)out(c.out.amax, nl2 * 4);
@@ -354,13 +374,31 @@ void queue_run(sg_ctx* ctx, uint32_t flags, const QArgs& c) {
   } else {
     queue_output_pass(ctx, a, drop, nullptr, false);
     if (packets) queue_packets(ctx, a, drop, nullptr);
+    if (series) queue_series(ctx, a, sr, drop, false);
     queue_check_flags(ctx, a.flag, where, false, true);
+  }
+  if (series) {
+    // (carried, the outputs stand at the input indices now, and the flag words are read once more)
+    if (carry) {
+      queue_series(ctx, a, sr, drop, window);
+      queue_check_flags(ctx, a.flag, where, true, false);
+    }
+    if (where.bad_slot != Q_MAX)
+      throw Error(SG_ERR_INVALID_ARG,
+                  "SG_LINK_QUEUE_SERIES: the slot of link " + std::to_string(where.bad_slot) + " is not below n_slots and not 2^64 - 1",
+                  (uint32_t)where.bad_slot, 0xFFFFFFFFu);
   }
   // read_timer("link_queue_lost") = (0, the packets the last call with SG_LINK_QUEUE_PACKETS found dropped, its packets)
   if (packets) timer_set_counter(ctx, "link_queue_lost", (double)c.n_weights, where.lost, true);
   for (const Back& b : back)
     if (b.bytes) SG_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+  std::vector<u64> sums;
+  if (series && !dev && busy_tail) {
+    sums.resize(busy_tail);
+    SG_HIP(hipMemcpyAsync(sums.data(), outs.busy + nl2, busy_tail * 8, hipMemcpyDeviceToHost, st));
+  }
   if (!back.empty()) SG_HIP(hipStreamSynchronize(st));
+  for (size_t k = 0; k < sums.size(); k++) c.out.busy[nl2 + k] += sums[k];
 }
 
 }  // namespace
@@ -402,6 +440,7 @@ bool queue_check_flags(sg_ctx* ctx, const u64* flag, QLocator& where, bool carri
                 lk, at);
   }
   where.lost = h[Q_LOST];
+  where.bad_slot = h[Q_BAD_SLOT];
   return h[Q_CHANGED] == Q_MAX;
 }
 

@@ -402,7 +402,7 @@ def _per_link_u64(x, n_links: int, what: str) -> np.ndarray:
 
 
 def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, cost_ps, free_ns=None, carry=False,
-               limit_ns=None, outcomes=None, horizon_ns=None):
+               limit_ns=None, outcomes=None, horizon_ns=None, series=None):
     """The FIFO queue of every link of a link trace under a link rate, on host arrays: link L owns
     records link_off[L] .. link_off[L + 1] (u64 offsets) in arrival order, enter_ns (u64) their
     arrival times, packet (u32) their index into weight (u32; None: every record weighs 1).
@@ -429,7 +429,9 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
     enter time a later call takes; it is neither dropped nor absent.  The per-link arrays run over
     settled records, link_free is what the later call takes as free_ns, and a packet with a pending
     record has where == WHERE_IN_FLIGHT, delay_ns what the queues added so far and arrive_ns its
-    re-based base (LinkQueueSession keeps all this from round to round)."""
+    re-based base (LinkQueueSession keeps all this from round to round).
+    series: a LinkQueueSeries (SG_LINK_QUEUE_SERIES); the call's busy time, waiting time, weight served and
+    weight dropped per slot and time bin are added into its matrix.  The result is unchanged."""
     if horizon_ns is not None and not carry:
         raise ValueError("horizon_ns: with carry=True")
     if (carry or outcomes is not None) and packet is None:
@@ -455,6 +457,10 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
             raise ValueError("horizon_ns: a u64 time")
         flags |= _capi.SG_LINK_QUEUE_WINDOW  # (the horizon rides behind the links' free times)
         free = np.concatenate([np.zeros(n_links, np.uint64) if free is None else free, np.array([int(horizon_ns)], np.uint64)])
+    if series is not None:
+        series._check(n_links)
+        flags |= _capi.SG_LINK_QUEUE_SERIES  # (the header and the slot map ride behind the costs, the matrix behind busy)
+        cost2 = series.host_cost(cost2)
     base = None if outcomes is None else np.ascontiguousarray(outcomes, dtype=np.uint64).ravel()
     n_rec = n
     if base is not None:
@@ -464,8 +470,8 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
         n_rec = n + len(base)
         enter = np.concatenate([enter, base])
     res = LinkQueueResult(np.zeros(n_rec, np.uint64), np.zeros(n_rec, np.uint64), np.zeros(n_rec, np.uint32),
-                          np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint64), np.zeros(n_links, np.uint64),
-                          np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint32))
+                          np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint64) if series is None else series.host_busy(nl2),
+                          np.zeros(n_links, np.uint64), np.zeros(n_links, np.uint64), np.zeros(nl2, np.uint32))
     ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
     n_weights = 0 if wt is None else len(wt)
     if carry and wt is None:
@@ -476,6 +482,9 @@ def link_queue(ctx: "Context", link_off, enter_ns, packet=None, weight=None, *, 
         ctx.handle, flags, n_links, ptr(off), n, ptr(enter if n_rec else np.zeros(1, np.uint64)),
         ptr(pkt if n or pkt is None else np.zeros(1, np.uint32)), ptr(wt), n_weights, ptr(cost2),
         ptr(free), *[ptr(a) for a in res]))
+    if series is not None:
+        series.add_host(res.link_busy_ns[nl2:])
+        res = res._replace(link_busy_ns=res.link_busy_ns[:nl2])
     tails = None
     if base is not None:
         tails = _outcomes(off, res.wait_ns[n:], res.done_ns[n:], res.ahead[n:], window=horizon_ns is not None)
@@ -504,14 +513,15 @@ def _windowed(queue):
 
 
 def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, enter, packet, weight, cost_ps,
-                        free_ns, carry: bool = False, n_packets: int = 0, limit_ns=None, base=None):
+                        free_ns, carry: bool = False, n_packets: int = 0, limit_ns=None, base=None, series=None):
     """sg_link_queue on a device trace (torch tensors on `dev`: off, enter, packet; weight or
     None), every output taken and copied to the host.  carry: with SG_LINK_QUEUE_CARRY, a
     LinkQueueCarried; n_packets bounds the packet numbers when there is no weight.  limit_ns: with
     SG_LINK_QUEUE_DROP, a LinkQueueDropped or LinkQueueCarriedDropped.  base: an int64 tensor of
     n_packets base times on `dev` (SG_LINK_QUEUE_PACKETS); enter then has room for them behind
     its records, where a device-to-device copy places them, weight has n_packets entries, and the
-    call returns (the queue result, a PacketOutcomes with arrive_dev)."""
+    call returns (the queue result, a PacketOutcomes with arrive_dev).  series: a LinkQueueSeries on `dev`
+    (SG_LINK_QUEUE_SERIES): the call adds into its matrix."""
     import torch
 
     up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)  # noqa: E731
@@ -530,18 +540,22 @@ def _link_queue_tensors(ctx: "Context", dev, n_links: int, off, n_records: int, 
     lnk = lambda dt, k=n_links: torch.zeros(max(k, 1), dtype=dt, device=dev)  # noqa: E731
     outs = [rec(torch.int64), rec(torch.int64), rec(torch.int32), lnk(torch.int64), lnk(torch.int64, nl2), lnk(torch.int64),
             lnk(torch.int64), lnk(torch.int32, nl2)]
+    if series is not None:
+        series._check(n_links, dev)
+        cost, outs[4] = series.device_cost(cost), series.device_busy(nl2)
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     torch.cuda.synchronize(dev)
     check(ctx.handle, load().sg_link_queue(
         ctx.handle, _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) |
-        (_capi.SG_LINK_QUEUE_DROP if drop else 0) | (0 if base is None else _capi.SG_LINK_QUEUE_PACKETS),
+        (_capi.SG_LINK_QUEUE_DROP if drop else 0) | (0 if base is None else _capi.SG_LINK_QUEUE_PACKETS) |
+        (0 if series is None else _capi.SG_LINK_QUEUE_SERIES),
         n_links, ptr(off), n_records,
         ptr(enter), None if weight is None and not carry and base is None else ptr(packet), ptr(weight),
         (n_packets if carry or base is not None else 0) if weight is None else weight.numel(), ptr(cost),
         ptr(free), *[ptr(t) for t in outs]))
     lens = [n_records + n_tail] * 3 + [n_links, nl2, n_links, n_links, nl2]
     dts = [np.uint64, np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32]
-    res = LinkQueueResult(*[t.cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
+    res = LinkQueueResult(*[t[:max(k, 1)].cpu().numpy().view(dt)[:k] for t, dt, k in zip(outs, dts, lens)])
     h_off = off.cpu().numpy().view(np.uint64)
     tails = None
     if base is not None:
@@ -598,14 +612,14 @@ def _step_windows(s, off, n: int, enter, packet, weight, base, window_ns: int, s
 
 
 def _link_queue_windows(ctx: "Context", dev, n_links: int, off, n: int, enter, packet, weight, cost_ps, free_ns, n_packets: int,
-                        limit_ns, base, window_ns: int):
+                        limit_ns, base, window_ns: int, series=None):
     """A device trace solved window by window through a LinkQueueSession (PathTree.link_queue_round,
     window_ns): _link_queue_tensors' result with carry."""
     import torch
 
     from .queue_session import LinkQueueSession
 
-    s = LinkQueueSession(ctx, cost_ps, limit_ns, free_ns, n_links=n_links, device=dev)
+    s = LinkQueueSession(ctx, cost_ps, limit_ns, free_ns, n_links=n_links, device=dev, series=series)
     wait, done = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
     delay, arrive, where = np.zeros(n_packets, np.uint64), np.zeros(n_packets, np.uint64), np.zeros(n_packets, np.uint32)
     arrive_dev = torch.zeros(n_packets, dtype=torch.int64, device=dev)
@@ -1031,7 +1045,7 @@ class PathTree:
         return off, t, enter, pkt, weight, hop, leave
 
     def link_queue_round(self, hosts, packets, status=None, weight=None, *, cost_ps, watch=None, free_ns=None,
-                         carry=False, limit_ns=None, outcomes=None, window_ns=None):
+                         carry=False, limit_ns=None, outcomes=None, window_ns=None, series=None):
         """The link trace of one round's batch and the FIFO queue of every link under a link rate,
         (link_off, packet, hop, enter_ns, exit_ns, queue): the first five as link_trace_round
         gives them, queue a LinkQueueResult over the same records.  The trace stays on the device
@@ -1056,7 +1070,10 @@ class PathTree:
         scanning only the records below its horizon.  The result is the one carry=True gives, but
         for `iterations`, the calls' sum.  A call counts `ahead` over its own settled records
         only, so ahead and link_ahead_max are counted again here on the host, from the settled
-        carried enter and done times."""
+        carried enter and done times.
+        series: a LinkQueueSeries over the graph's links (SG_LINK_QUEUE_SERIES): the round's busy time,
+        waiting time, weight served and weight dropped per slot and time bin are added into its
+        matrix on the device, with window_ns= by every window's call.  The result is unchanged."""
         import torch  # noqa: F401
 
         if window_ns is not None and (not carry or int(window_ns) < 1):
@@ -1071,10 +1088,10 @@ class PathTree:
         n_links = off.numel() - 1
         if window_ns is not None:
             queue = _link_queue_windows(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, npk, limit_ns, base,
-                                        int(window_ns))
+                                        int(window_ns), series)
         else:
             queue = _link_queue_tensors(g.ctx, dev, n_links, off, t, enter, pkt, weight, cost_ps, free_ns, carry, npk,
-                                        limit_ns, base)
+                                        limit_ns, base, series)
         tails = ()
         if base is not None:
             queue, tails = queue[0], (queue[1],)
@@ -1457,7 +1474,7 @@ class NetworkGraph:
                           n_weights: int, cost_ptr: int, free_in_ptr: int = 0, *, wait_ptr: int = 0, done_ptr: int = 0,
                           ahead_ptr: int = 0, link_free_ptr: int = 0, busy_ptr: int = 0, wait_max_ptr: int = 0,
                           wait_sum_ptr: int = 0, ahead_max_ptr: int = 0, carry: bool = False, limit_ns=None,
-                          outcomes: bool = False, horizon_ns=None) -> None:
+                          outcomes: bool = False, horizon_ns=None, series=None) -> None:
         """The FIFO queue of every link of a device link trace under a link rate, into caller-owned
         device arrays: link_off (u64, one entry per link of links() and one more), enter (u64) and
         packet (u32) of n_records records as link_trace_packets_device wrote them; weight (device
@@ -1479,7 +1496,11 @@ class NetworkGraph:
         arrival and the record that dropped it behind the records of wait, done and ahead.
         horizon_ns: with carry, settle only the records whose carried enter time is below it
         (SG_LINK_QUEUE_WINDOW; link_queue tells what the pending ones get).  free_in is then copied, with the
-        horizon behind it, into the array of one more entry the call takes."""
+        horizon behind it, into the array of one more entry the call takes.
+        series: a LinkQueueSeries over the graph's links (SG_LINK_QUEUE_SERIES); wait and done are then
+        required, with horizon_ns ahead as well.  cost is copied, with the series' header and slot
+        map behind it, the call writes its per-link busy values in front of the series' matrix and
+        adds into the matrix, and busy (if given) receives a copy of the per-link values."""
         vp = lambda x: C.c_void_p(x or None)  # noqa: E731
         n_links = len(self.links()[0])
         flags = _capi.SG_ROUTE_OUT_DEVICE | (_capi.SG_LINK_QUEUE_CARRY if carry else 0) | \
@@ -1513,11 +1534,30 @@ class NetworkGraph:
             torch.cuda.synchronize(old.device)
             cost_ptr = cost2.data_ptr()
             flags |= _capi.SG_LINK_QUEUE_DROP
+        own_busy = 0
+        if series is not None:
+            import torch
+
+            series._check(n_links)
+            c0 = 2 * n_links if limit_ns is not None else n_links
+
+            class _Cost:  # the c0 u64 at cost_ptr, for torch
+                __cuda_array_interface__ = {"shape": (c0,), "typestr": "<i8", "data": (int(cost_ptr), False), "version": 2}
+            cost3 = series.device_cost(torch.as_tensor(_Cost(), device="cuda"))
+            busy3 = series.device_busy(c0)
+            torch.cuda.synchronize(cost3.device)
+            cost_ptr, own_busy, busy_ptr = cost3.data_ptr(), busy_ptr, busy3.data_ptr()
+            flags |= _capi.SG_LINK_QUEUE_SERIES
         check(self.ctx.handle, load().sg_link_queue(
             self.ctx.handle, flags, n_links, vp(link_off_ptr), int(n_records),
             vp(enter_ptr), vp(packet_ptr), vp(weight_ptr), int(n_weights), vp(cost_ptr), vp(free_in_ptr), vp(wait_ptr),
             vp(done_ptr), vp(ahead_ptr), vp(link_free_ptr), vp(busy_ptr), vp(wait_max_ptr), vp(wait_sum_ptr),
             vp(ahead_max_ptr)))
+        if own_busy and c0:
+            class _Busy:  # the caller's c0 u64 at busy_ptr
+                __cuda_array_interface__ = {"shape": (c0,), "typestr": "<i8", "data": (int(own_busy), False), "version": 2}
+            torch.as_tensor(_Busy(), device="cuda").copy_(busy3[:c0])
+            torch.cuda.synchronize(busy3.device)
 
     def min_latency_device(self, latency_ptr: int, count: int) -> int:
         out = C.c_uint64()

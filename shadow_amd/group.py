@@ -296,7 +296,7 @@ class Group:
         return off, pkt, mem, hop, enter, leave, total.value
 
     def link_queue_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, cost_ps, watch=None,
-                         free_ns=None, root: int = 0, carry=False, limit_ns=None, outcomes=None):
+                         free_ns=None, root: int = 0, carry=False, limit_ns=None, outcomes=None, series=None):
         """The link trace of one sharded round and the FIFO queue of every link under a link rate,
         (link_off, packet, member, hop, enter_ns, exit_ns, queue): the first six as
         link_trace_round gives them, queue a graph.LinkQueueResult over the same records
@@ -313,7 +313,9 @@ class Group:
         outcomes: one Deliveries, or u64 array or tensor of base times, per member
         (SG_LINK_QUEUE_PACKETS); they are concatenated in member order on root's device, as the
         packet numbers are, and a graph.PacketOutcomes over all members' packets is the tuple's
-        last entry (PathTree.link_queue_round)."""
+        last entry (PathTree.link_queue_round).
+        series: a LinkQueueSeries on root's device (SG_LINK_QUEUE_SERIES): the round's busy time, waiting
+        time, weight served and weight dropped per slot and time bin are added into its matrix there."""
         import torch
 
         from .graph import _base_times, _exit_carried, _link_queue_tensors
@@ -349,7 +351,7 @@ class Group:
             if enter.numel() < t + npk:  # (room for the base times behind the records)
                 enter = torch.cat([enter[:t], torch.zeros(npk, dtype=torch.int64, device=dev)])
         queue = _link_queue_tensors(self.contexts[root], dev, off.numel() - 1, off, t, enter, pkt, wt, cost_ps, free_ns,
-                                    carry, npk, limit_ns, base)
+                                    carry, npk, limit_ns, base, series)
         if base is not None:
             queue, tails = queue[0], (queue[1],)
         host = self._trace_to_host(*tr)

@@ -58,9 +58,12 @@ class LinkQueueSession:
     SG_LINK_QUEUE_CARRY | SG_LINK_QUEUE_WINDOW | SG_LINK_QUEUE_PACKETS.  In-flight packets are numbered before the
     round's and keep their order, so (round, packet) order is the packet numbering of every call:
     a sequence of rounds followed by flush() equals one carried call over the concatenated trace.
-    `ahead` is not kept: a call counts only its own settled records (include/shadow_gpu.h)."""
+    `ahead` is not kept: a call counts only its own settled records (include/shadow_gpu.h).
+    series: a LinkQueueSeries over the same links (SG_LINK_QUEUE_SERIES in every call): every advance() adds
+    the records it settles into the series' matrix, so the rounds and flush() sum to the matrix of the
+    one carried call."""
 
-    def __init__(self, graph_or_ctx, cost_ps, limit_ns=None, free_ns=None, *, n_links=None, device="cuda"):
+    def __init__(self, graph_or_ctx, cost_ps, limit_ns=None, free_ns=None, *, n_links=None, device="cuda", series=None):
         import torch
 
         from .graph import _per_link_u64
@@ -72,6 +75,10 @@ class LinkQueueSession:
         cost = _per_link_u64(cost_ps, nl, "cost_ps")
         self.drop = limit_ns is not None
         self._cost = up(np.concatenate([cost, _per_link_u64(limit_ns, nl, "limit_ns")]) if self.drop else cost)
+        self.series = series
+        if series is not None:
+            series._check(nl, self.dev)
+            self._cost = series.device_cost(self._cost)  # (the header and the slot map behind the costs)
         # (the horizon rides behind the links' free times)
         self._free = up(np.concatenate([np.zeros(nl, np.uint64) if free_ns is None else _per_link_u64(free_ns, nl, "free_ns"),
                                         np.zeros(1, np.uint64)]))
@@ -193,6 +200,8 @@ class LinkQueueSession:
         nl2 = 2 * nl if self.drop else nl
         wait, done, ahead = room(n + P), room(n + P), room(n + P, torch.int32)
         free_out, busy, wmax, wsum, amax = room(nl), room(nl2), room(nl), room(nl), room(nl2, torch.int32)
+        if self.series is not None:
+            busy = self.series.device_busy(nl2)  # (the per-link values in front of the matrix the call adds into)
         self._free[nl] = torch.tensor(H - (1 << 64) if H >= 1 << 63 else H, dtype=i64)
         if not m_weight.numel():
             m_weight = room(0, torch.int32)
@@ -200,7 +209,7 @@ class LinkQueueSession:
         torch.cuda.synchronize(dev)
         lap("merge")
         flags = _capi.SG_ROUTE_OUT_DEVICE | _capi.SG_LINK_QUEUE_CARRY | _capi.SG_LINK_QUEUE_WINDOW | _capi.SG_LINK_QUEUE_PACKETS | \
-            (_capi.SG_LINK_QUEUE_DROP if self.drop else 0)
+            (_capi.SG_LINK_QUEUE_DROP if self.drop else 0) | (0 if self.series is None else _capi.SG_LINK_QUEUE_SERIES)
         check(self.ctx.handle, load().sg_link_queue(
             self.ctx.handle, flags, nl, ptr(m_off), n, ptr(m_enter), ptr(m_packet), ptr(m_weight), P, ptr(self._cost),
             ptr(self._free), ptr(wait), ptr(done), ptr(ahead), ptr(free_out), ptr(busy), ptr(wmax), ptr(wsum), ptr(amax)))

@@ -1472,8 +1472,12 @@ struct BkKnobs {
 static BkKnobs bk_knobs(const sg_net* net) {
   BkKnobs k;
   k.shape = bk_shape();
+  // The knob from 2 ns on: at 1 ns the bucket of latency 2^32 - 2, the largest a key holds, is
+  // 0xFFFFFFFE, k_sssp_bucket's NEXT_FAR, and b + lane wraps.  The default width comes to 1 ns only
+  // with 1-ns arcs and a mean arc below 256 ns (the cast truncates), where no path of a graph
+  // this search takes is that long.
   const double dl = knob_double("SG_BUCKET_DELTA", std::max<double>(std::max<uint32_t>(net->arc_lat_min, 1u),
-                                                                    net->arc_lat_mean / 128.0));
+                                                                    net->arc_lat_mean / 128.0), 2.0);
   k.delta = (uint32_t)std::max(1.0, std::min(4294967295.0, dl));
   k.ring = 2;
   for (const uint32_t want = (uint32_t)std::max(2, knob_int("SG_BUCKET_RING", (int)BK_R)); k.ring < BK_R && k.ring < want;)

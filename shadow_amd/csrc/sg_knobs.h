@@ -55,7 +55,7 @@
 //   SG_BUCKET_THREADS | 256 | 256, 1024 | test | bucketed search: threads per workgroup
 //   SG_BUCKET_HASH | 1024 threads ? 12 : 11 | 6 .. 14 | test | bucketed / banded search: log2 of the hash slots; small tables give up
 //   SG_BUCKET_CHUNKS | banded ? 384 : 1024 | 4 .. 65534 | test | bucketed / banded search: arena chunks per workgroup; small arenas give up
-//   SG_BUCKET_DELTA | max(smallest arc, mean arc / 128) | 1 .. 2^32-1 ns | test | bucketed search: bucket width
+//   SG_BUCKET_DELTA | max(smallest arc, mean arc / 128) | 2 .. 2^32-1 ns | test | bucketed search: bucket width; a set value below 2 is taken as 2 (at 1 ns the bucket of latency 2^32 - 2 is the kernel's far-step sentinel)
 //   SG_BUCKET_RING | 128 | 2 .. 128, a power of two | test | bucketed search: ring slots; small rings use the far lists
 //   SG_BUCKET_MODE | unset | queue | test | bucketed search: queue forces the general kernel over the exact-band one
 //   SG_BUCKET_PER_CU | 8 | >= 1 | tune | bucketed / banded search: workgroups per CU, at most
@@ -108,6 +108,14 @@ inline int knob_int(const char* name, int dflt, int lo, int hi) {
 inline double knob_double(const char* name, double dflt) {
   const char* s = getenv(name);
   return s && *s ? atof(s) : dflt;
+}
+
+// a set value raised to lo; unset or empty: the default as it is
+inline double knob_double(const char* name, double dflt, double lo) {
+  const char* s = getenv(name);
+  if (!s || !*s) return dflt;
+  const double v = atof(s);
+  return v < lo ? lo : v;
 }
 
 // a knob whose value starts with '0' (off switches that were never parsed as numbers)

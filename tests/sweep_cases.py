@@ -6,6 +6,7 @@ Case k of CASES takes each axis from a list by an index that is a function of k 
 indices are chosen so that the axes do not move in step (the node counts have period 12, the
 latency regimes 5, and the other three shift by one with every cycle of the node counts).
 Every random draw comes from default_rng(SEED0 + k): a case never changes with its neighbours.
+Beside the 40, EXTRA pins the seam cases of tests/seam_cases.py by name.
 """
 import functools
 
@@ -99,11 +100,15 @@ def _round(hosts, n_packets, seed, src_hosts=None):
     return pk, RC.mixed_status(n_packets, seed + 1)
 
 
-def _make(name, n, directed, degree, lat_regime, loss_regime, seed):
-    g = graph(n, directed, degree, lat_regime, loss_regime, seed)
+def _make(name, n, directed, degree, lat_regime, loss_regime, seed, g=None, block=None):
+    """With a ready graph `g` (built on graph()'s with these arguments) n is the graph's own;
+    `block(nodes)` then gives the second view's rows in place of [n // 3, n - n // 4)."""
+    if g is None:
+        g = graph(n, directed, degree, lat_regime, loss_regime, seed)
+    n = g["n"]
     rng = np.random.default_rng(seed + 100_000)
     nodes = rng.permutation(n).astype(np.uint32)
-    blocks = [(0, n)] + ([(n // 3, n - n // 4)] if n >= 3 else [])
+    blocks = [(0, n)] + ([block(nodes) if block else (n // 3, n - n // 4)] if n >= 3 else [])
     hosts = synth.make_hosts(3 * n, n)
     n_packets = min(4000, 40 * n)
     counts = np.where(rng.random((n, n)) < 0.3, rng.integers(1, 1 << 40, (n, n)), 0).astype(np.uint64)
@@ -119,11 +124,25 @@ def _make(name, n, directed, degree, lat_regime, loss_regime, seed):
                 axes=(n, directed, degree, lat_regime, loss_regime))
 
 
-# Cases pinned by name beside the 40: name -> _make's arguments.  (Rows with a wide cell beside
-# rows without any, where k_tree_lds sends single rows to the global path, needed no pin: k18 and
-# k28 are such cases, as test_sweep_ref_cpu.py asserts.)  A case that exposed a bug stays here
-# under its case number and stage.
-EXTRA = {}
+def _seam_args(name):
+    """_make's arguments for a case of tests/seam_cases.py (which builds on graph() above and is
+    therefore imported only when a case is made)."""
+    import seam_cases
+
+    return seam_cases.make_args(name)
+
+
+# Cases pinned by name beside the 40: name -> a call that gives _make's arguments after the name.
+# (Rows with a wide cell beside rows without any, where k_tree_lds sends single rows to the global
+# path, needed no pin: k18 and k28 are such cases, as test_sweep_ref_cpu.py asserts.)  A case that
+# exposed a bug stays here under its case number and stage.
+#
+# The seam cases: optima of exactly 2^32 - 4 .. 2^32 + 1 ns, where the searches' 32-bit keys
+# saturate; two of them dense.  These names are the only list of them; seam_cases.CASES holds
+# their parameters, and those of the two 603-node cases that case() makes for the chained-row
+# tests alone.
+SEAM = ("spur_us63", "spur_us200_lossy", "spur_dense", "under_ms129", "across_ms129", "under_dense")
+EXTRA = {name: functools.partial(_seam_args, name) for name in SEAM}
 NAMES = [f"k{k:02d}" for k in range(N_CASES)] + list(EXTRA)
 
 
@@ -135,7 +154,9 @@ def case(name):
     block's rows of a counts matrix (30 % nonzero, values below 2^40) and 2,000 (row, column)
     pairs, same-node pairs among them."""
     if name in EXTRA:
-        return _make(*EXTRA[name])
+        return _make(name, **EXTRA[name]())
+    if not (name[0] == "k" and name[1:].isdigit()):  # a seam case outside EXTRA
+        return _make(name, **_seam_args(name))
     k = int(name[1:])
     return _make(name, *axes(k), SEED0 + k)
 

@@ -426,6 +426,48 @@ def test_pack_refuses_wide_latency(oracle, ctx):
     _assert_same(want, got, ost, gst)
 
 
+def _seam_table():
+    """6 x 6, cells of 1-999 ns but for columns of 2^32 - 2 and 2^32 - 1 ns: the largest
+    latencies the packed form holds."""
+    rng = np.random.default_rng(11)
+    lat = rng.integers(1, 1000, size=(6, 6)).astype(np.uint64)
+    lat[:, 2] = np.uint64((1 << 32) - 2)
+    lat[:, 4] = np.uint64((1 << 32) - 1)
+    loss = (rng.random((6, 6), dtype=np.float32) * 0.3).astype(np.float32)
+    return lat, loss
+
+
+def _seam_round(oracle, ctx, lat, loss):
+    hosts = synth.make_hosts(40, 6)
+    start, end = T0 + 10**9, T0 + 10**9 + 10**6
+    pk = synth.make_packets(500, hosts, start, end, seed=3)
+    want, got, ost, gst, _ = _run_both(oracle, ctx, lat, loss, hosts, pk, end, end + 10**12, 0)
+    _assert_same(want, got, ost, gst)
+    ok = want["status"] == oracle.ST_DELIVERED
+    return (want["deliver_time"][ok] - pk["send_time"][ok]).astype(np.uint64)
+
+
+def test_pack_takes_latencies_up_to_2_32_minus_1(oracle, ctx):
+    """Cells of 2^32 - 2 and 2^32 - 1 ns and none above: pack() takes the table, and the round is
+    exact in both table forms, deliver times reaching send + 2^32 - 1."""
+    lat, loss = _seam_table()
+    assert int(lat.max()) == (1 << 32) - 1
+    t = _device_table(lat, loss)
+    assert t.pack() and t.path_key is not None
+    flight = _seam_round(oracle, ctx, lat, loss)
+    assert (flight == (1 << 32) - 1).any() and (flight == (1 << 32) - 2).any() and int(flight.max()) == (1 << 32) - 1
+
+
+def test_pack_refuses_a_latency_of_2_32(oracle, ctx):
+    """The same table with one cell of exactly 2^32 ns: pack() refuses it and the round is still exact."""
+    lat, loss = _seam_table()
+    lat[1, 5] = np.uint64(1) << np.uint64(32)
+    t = _device_table(lat, loss)
+    assert not t.pack() and t.path_key is None
+    flight = _seam_round(oracle, ctx, lat, loss)
+    assert (flight == (1 << 32) - 1).any() and (flight == 1 << 32).any() and int(flight.max()) == 1 << 32
+
+
 def test_c5_packet_count_round(oracle, ctx, table_form):
     """10M packets in one round (the C5 packet count) over 60k hosts: the region
     bucketing runs near its super-bucket limit (3750 of 4096).  The bucketing does

@@ -5,6 +5,12 @@ keys still in its LDS into that row's start (bounds, or exact seeds over a zero-
 Every case compares every cell of a table built into zero-poisoned device buffers with the CPU
 oracle, with the chain on and off, without a plan (SG_SSSP_SEEDS=0) and with the phases forced
 (SG_SSSP_SEEDS=2).  The graphs have 600-1,200 nodes: 2-5 rows per CU, so chains form.
+
+test_chains_at_the_seam runs tests/seam_cases.py's 603-node graphs, whose rows end exactly at the
+largest latency a 32-bit key holds, also without exact seeds and with a workgroup per row
+(measured on an MI355X: 0.07 and 0.03 s per case, twelve builds each; the counts vary a little
+from run to run: under_ms600 chained about 270 rows, 200 of them with exact seeds, without a
+plan and about 77 / 54 with the phases forced; under_unit600 about 232 / 137 and 22 / 9).
 """
 import numpy as np
 import pytest
@@ -150,6 +156,37 @@ def test_chain_behind_saturated_rows(oracle, ctx, monkeypatch, all_used):
             assert n_exact == 0
         else:
             assert n_exact > 0
+
+
+@pytest.mark.parametrize("name", ["under_ms600", "under_unit600"])
+def test_chains_at_the_seam(oracle, ctx, monkeypatch, name):
+    """tests/seam_cases.py's 600-node graphs: 167 and 237 of 603 rows have a maximum of exactly
+    2^32 - 2 ns, the largest latency a 32-bit key holds (a chain's `lw < LAT32_SAT - 1` and an exact
+    seed's `ub < LAT32_SAT` are one off it), 149 and 117 rows hold cells past 2^32 and go to the
+    wide kernel.  Every base arc of under_ms600 is lossless: its chains seed exact keys."""
+    import sweep_cases as SC
+
+    c = SC.case(name)
+    counts = _all_configs(oracle, ctx, monkeypatch, c["g"], c["nodes"], counted=True)
+    for (chain, seeds), (n_chained, n_exact) in counts.items():
+        if chain == "0":
+            assert n_chained == 0 and n_exact == 0, (chain, seeds)
+            continue
+        assert n_chained > 0, (chain, seeds)
+        if name == "under_ms600":
+            assert n_exact > 0, (chain, seeds)
+    # The launch without a plan, 603 rows on fewer CUs: SG_SSSP_EXACT=0 chains with bounds only;
+    # SG_SSSP_PERSIST=0 launches a workgroup per row, which chains nothing.
+    used = np.asarray(c["nodes"], dtype=np.uint32)
+    rows = (0, len(used))
+    want = _oracle(oracle, c["g"], used, rows)
+    for knob, chains in (("SG_SSSP_EXACT", True), ("SG_SSSP_PERSIST", False)):
+        with monkeypatch.context() as m:
+            _env(m, "1", "0")
+            m.setenv(knob, "0")
+            _same(_build(c["g"], used, rows, ctx), want)
+            n_chained, n_exact = _counted(c["g"], used, rows, ctx, want)
+            assert n_exact == 0 and (n_chained > 0) == chains, (knob, n_chained, n_exact)
 
 
 @pytest.mark.parametrize("spin", ["1", "40"])

@@ -5,6 +5,8 @@ packet statuses and the whole per-host state, across consecutive calls."""
 import numpy as np
 import pytest
 
+import codel_cases as cc
+import codel_ref as ref
 import lane_cases
 from shadow_amd import ShadowGpuError, _capi
 from shadow_amd.router import CoDelEvents, CoDelQueues
@@ -24,13 +26,8 @@ def _status(n):
 def _same_state(O, got, want):
     for k in KEYS:
         assert np.array_equal(got[k], want[k]), k
-    # live ring slots only: [head, tail) per host
-    cap = want["cap"]
-    lo = want["head"].astype(np.int64)
-    n = want["tail"].astype(np.int64) - lo
-    hh = np.repeat(np.arange(len(n)), n)
-    c = lo[hh] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
-    i = hh * cap + (c % cap)
+    # live ring slots only: [head, tail) per host, the counters taken modulo 2^32
+    i = ref.live_slots(want)
     for k in ("ring_pkt", "ring_ts", "ring_len"):
         assert np.array_equal(got[k][i], want[k][i]), k
 
@@ -46,21 +43,7 @@ def _run_both(O, q, ostate, gstat, ostat, host, kind, t, pkt, ln):
     return want
 
 
-def _host_times(host, gaps, t0):
-    """Per host (host sorted): t0 + the running sum of its own gaps (a segmented cumsum)."""
-    c = np.cumsum(gaps.astype(np.int64))
-    first = np.r_[True, host[1:] != host[:-1]]
-    base = np.maximum.accumulate(np.where(first, c - gaps, 0))
-    return (t0 + c - base).astype(np.uint64)
-
-
-def _stream(rng, H, E, t0, gap_ms, p_pop, n_pkt0=0):
-    host = np.sort(rng.integers(0, H, E)).astype(np.uint32)
-    kind = (rng.random(E) < p_pop).astype(np.uint8)
-    t = _host_times(host, rng.integers(0, gap_ms * MS, E), t0)
-    pkt = (n_pkt0 + np.arange(E)).astype(np.uint32)
-    ln = rng.integers(40, 1500, E).astype(np.uint32)
-    return host, kind, t, pkt, ln
+_host_times, _stream = cc.host_times, cc.stream   # drawn in codel_cases.py: the CPU tests run them too
 
 
 def test_reference_drop_many_sequence(oracle, ctx):
@@ -274,3 +257,130 @@ def test_bytes_below_ring_contents(oracle, ctx):
     t = (t0 + 10**6 + np.tile(np.arange(3), H) * 1000).astype(np.uint64)
     _run_both(oracle, q, os_, gstat, ostat, host, kind, t, np.zeros(3 * H, np.uint32), np.zeros(3 * H, np.uint32))
     _same_state(oracle, q.get_state(), os_)
+
+
+# ---- the boundary cases (codel_cases.py), one lane per case ---------------------------------------
+def _run_three(oracle, q, sm, so, gstat, mstat, ostat, ev):
+    """One call on the device, the oracle and the model (codel_ref.py): results, statuses, drops."""
+    want = _run_both(oracle, q, so, gstat, ostat, *ev)
+    assert np.array_equal(ref.run(sm, *ev, mstat), want)
+    assert np.array_equal(mstat, ostat)
+
+
+def _three_states(oracle, q, sm, so):
+    _same_state(oracle, q.get_state(), so)
+    _same_state(oracle, sm, so)
+    _same_state(oracle, so, q.get_state())   # and the device's live slots are the oracle's
+
+
+def _queues(ctx, st0):
+    q = CoDelQueues(len(st0["flags"]), st0["cap"], ctx=ctx)
+    assert q.cap == st0["cap"]
+    q.set_state(st0)
+    return q, ref.copy_state(st0), ref.copy_state(st0)
+
+
+@pytest.mark.parametrize("form", cc.FORMS)
+@pytest.mark.parametrize("layout", lane_cases.LAYOUTS)
+def test_boundary_cases(oracle, ctx, monkeypatch, layout, form):
+    """Every case of codel_cases.py in one form, one host per case, all of them in one call (two:
+    a twin's ring form pushes its elements in a call of its own); rings of 64 and, for the ring
+    family's other half, of 4.  Pop results, statuses, n_dropped and the whole state against the
+    oracle and the model, after each call."""
+    lane_cases.set_layout(monkeypatch, layout)
+    for cap in (64, 4):
+        cs = [c for c in cc.of_cap(cap) if cc.has_form(c, form)]
+        st0, calls, base = cc.build(cs, form, cap)
+        q, sm, so = _queues(ctx, st0)
+        gstat, mstat, ostat = _status(base[-1]), np.zeros(base[-1], np.uint8), np.zeros(base[-1], np.uint8)
+        for ev in calls:
+            _run_three(oracle, q, sm, so, gstat, mstat, ostat, ev)
+            _three_states(oracle, q, sm, so)
+        assert (ostat == 2).any() and (ostat == 1).any()
+
+
+def _by_host(*parts):
+    """Event columns of several sources as one call: grouped by ascending host, each host's in order."""
+    cols = [np.concatenate([p[i] for p in parts]) for i in range(5)]
+    o = np.argsort(cols[0], kind="stable")
+    return tuple(c[o] for c in cols)
+
+
+@pytest.mark.parametrize("layout", lane_cases.LAYOUTS)
+def test_boundary_cases_among_traffic(oracle, ctx, monkeypatch, layout):
+    """The cases of every form (rings of 64: ~1,000 hosts) in shuffled order on the even hosts,
+    the odd hosts between them carrying _stream traffic (~70 events each, so that an unset layout
+    launches the per-block choice: E > 2 x 1,024 events per block), and a last host with 1,500
+    events.  Lane-major chunks hold 16 events per host: a case of more events is walked in
+    several chunks, resumed from the state the last one left, its window's elements read back
+    from the ring; the long host's block walks contiguous chunks with the cases behind it."""
+    lane_cases.set_layout(monkeypatch, layout)
+    rng = np.random.default_rng(64)
+    cs, forms = zip(*[(c, f) for f in cc.FORMS for c in cc.of_cap(64) if cc.has_form(c, f)])
+    nc = len(cs)
+    H = 2 * nc + 1
+    st0, calls, base = cc.build(cs, forms, 64, hosts=2 * rng.permutation(nc), n_hosts=H)
+    E, p0 = 70 * nc, base[-1]
+    n_pkt = p0 + 2 * (E + 1500)
+    q, sm, so = _queues(ctx, st0)
+    gstat, mstat, ostat = _status(n_pkt), np.zeros(n_pkt, np.uint8), np.zeros(n_pkt, np.uint8)
+    t0 = T0 + 10**9
+    for c, ev in enumerate(calls):
+        h, kind, t, pkt, ln = _stream(rng, nc, E, t0, 3, 0.5, n_pkt0=p0)
+        big = _stream(rng, 1, 1500, t0, 1, 0.6, n_pkt0=p0 + E)   # more pops than pushes: 64 slots hold it
+        all_ev = _by_host(ev, (2 * h + 1, kind, t, pkt, ln), (big[0] + np.uint32(H - 1),) + big[1:])
+        assert np.bincount(all_ev[0]).max() >= 1500 and len(all_ev[0]) > 2 * 1024 * ((H + 63) // 64)
+        _run_three(oracle, q, sm, so, gstat, mstat, ostat, all_ev)
+        _three_states(oracle, q, sm, so)
+        t0, p0 = int(t.max()) + 1, p0 + E + 1500
+    assert (ostat[base[-1]:] == 2).any() and (ostat[base[-1]:] == 1).any()   # the traffic reached drop mode
+
+
+def test_boundary_cases_one_event_per_call(oracle, ctx):
+    """The entry and drop families (their twins too), ring form, one event of every case per run:
+    the state written back after every event is the state the next event starts from."""
+    cs = [c for c in cc.of_cap(64) if c["family"] in ("entry", "drop")]
+    st0, calls, base = cc.build(cs, "ring", 64)
+    q, sm, so = _queues(ctx, st0)
+    gstat, mstat, ostat = _status(base[-1]), np.zeros(base[-1], np.uint8), np.zeros(base[-1], np.uint8)
+    steps = 0
+    for ev in calls:
+        rank = np.arange(len(ev[0])) - np.searchsorted(ev[0], ev[0])   # an event's index within its host
+        for j in range(int(rank.max()) + 1 if len(rank) else 0):
+            _run_three(oracle, q, sm, so, gstat, mstat, ostat, tuple(a[rank == j] for a in ev))
+            steps += 1
+    _three_states(oracle, q, sm, so)
+    assert steps >= 20 and (ostat == 2).sum() >= sum(c["expect"].get("drops", 0) for c in cs)
+
+
+def test_state_roundtrip_every_field(ctx):
+    """set_state then get_state returns every field of every host and every ring slot bit for
+    bit, and so after an empty run: times with the high word set, counts above 2^32, every flag
+    combination, head / tail straddling 2^32."""
+    H, cap = 200, 8
+    rng = np.random.default_rng(8)
+    q = CoDelQueues(H, cap, ctx=ctx)
+    st = q.get_state()
+    u64 = lambda n: rng.integers(0, 2**64, n, dtype=np.uint64) | np.uint64(1 << 63)
+    st["flags"][:] = np.arange(H) % 8
+    for k in ("interval_end", "drop_next", "cur", "prev", "bytes"):
+        st[k][:] = u64(H)
+    st["cur"][:4] = np.array([2**32, 2**32 + 1, 2**64 - 1, 0], np.uint64)
+    st["prev"][:4] = np.array([2**32 + 1, 2**32, 0, 2**64 - 1], np.uint64)
+    st["head"][:] = rng.integers(0, 2**32, H, dtype=np.uint32)
+    st["head"][:6] = (2**32 - 1, 2**32 - 2, 2**32 - cap, 0, 2**31, 2**31 - 1)
+    st["tail"][:] = st["head"] + rng.integers(0, cap + 1, H).astype(np.uint32)   # wraps past 2^32
+    assert (st["tail"][:3] < st["head"][:3]).any()
+    st["ring_pkt"][:] = rng.integers(0, 2**32, H * cap, dtype=np.uint32)
+    st["ring_ts"][:] = u64(H * cap)
+    st["ring_len"][:] = rng.integers(0, 2**32, H * cap, dtype=np.uint32)
+    want = ref.copy_state(st)
+    q.set_state(st)
+    for _ in range(2):
+        got = q.get_state()
+        assert sorted(got) == sorted(want) and got["cap"] == cap
+        for k in want:
+            if k != "cap":
+                assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+        res, nd = q.run(CoDelEvents.from_numpy([], [], [], [], []), _status(1))
+        assert len(res) == 0 and nd == 0

@@ -547,6 +547,9 @@ void launch_zero2(sg_ctx* ctx, uint32_t* a, uint32_t na, uint32_t* b, uint32_t n
 // slab offsets fit 32 bits), and the wide (u64 latency) recomputation of the listed rows
 // (absolute row indices) every search falls back to
 constexpr int WORK_SHARDS = 64;  // relaxation counter shards (measurement only)
+// the LDS search's counters behind the shards: chained rows (2), the ring invariant (2), the pops by
+// class, then SG_SSSP_EARLY's two: rows that started under their bound rows' loads, merges onto dirty keys
+constexpr int WORK_SSSP_EARLY = WORK_SHARDS + 4 + SSSP_POP_WORDS;
 void shortest_paths_slab(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, uint32_t row_begin,
                          uint32_t row_end, uint64_t* out_lat, float* out_loss);
 void run_wide(sg_ctx* ctx, sg_net* net, const uint32_t* d_used, uint32_t n_used, const std::vector<uint32_t>& rows,

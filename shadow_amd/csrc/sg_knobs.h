@@ -40,6 +40,7 @@
 //   SG_SSSP_STEP_ARCS | 256 | >= 0 | tune | LDS search: arcs up to which a pop takes the arc-parallel step sized to them (0: never)
 //   SG_SSSP_PERSIST | 1 | 0, 1 | test | LDS search: 0 launches a workgroup per row
 //   SG_SSSP_CHAIN | 1 | 0, 1 | tune | LDS search: 0 takes rows in list order, none seeded from the row the workgroup just finished
+//   SG_SSSP_EARLY | 1 | 0, 1 | tune | LDS search: 0 ends every row's set-up before its search; 1 starts a chained row's search behind the LDS pass, its bound rows merged under it
 //   SG_SSSP_SPIN_MAX | 4194304 | >= 1 | test | LDS and bucketed searches: spin budget per wave; small values make searches give up
 //   SG_PLAN_DIAG | 0 | 0, 1 | diag | plan: phase sizes on stderr
 //   SG_DENSE_LAZY | 1 | 0, 1 | test | dense: 0 takes the T-cut search with seed rows

@@ -454,9 +454,30 @@ static void print_sssp_diag(sg_ctx* ctx, const sg_net* net, const unsigned long 
   double setup = 0;
   // chained against unchained rows (word 3, bit 22): rows, setup cycles, search cycles (set-up included)
   double cn[2] = {0, 0}, cs[2] = {0, 0}, cq[2] = {0, 0};
+  // how the search begins (words 13-15, sg_sssp.hip E_T0), per chained row with bound-row stamps: early
+  // rows (index 1) against the others: rows, cycles to the first and the fourth claim (rows with four),
+  // waves that held a claim in the first 16k cycles, cycles to the end of the last merge, merges onto dirty keys
+  double en[2] = {0, 0}, e1[2] = {0, 0}, e4[2] = {0, 0}, e4n[2] = {0, 0}, ew[2] = {0, 0}, em = 0, ed = 0;
+  double parts_n = 0;  // rows whose words 11 and 12 hold load-round parts
   for (uint32_t r = 0; r < n_diag; r++) {
-    for (int k = 0; k < DW; k++) a[k] += (double)h[(size_t)r * DW + k];
+    for (int k = 0; k < 13; k++) a[k] += (double)h[(size_t)r * DW + k];
     const unsigned long long w3 = h[(size_t)r * DW + 3];
+    if (h[(size_t)r * DW] != 0 && ((w3 >> 22) & 1)) {
+      const unsigned long long w13 = h[(size_t)r * DW + 13], w14 = h[(size_t)r * DW + 14], w15 = h[(size_t)r * DW + 15];
+      const int e = (int)((w15 >> 32) & 1);
+      en[e] += 1;
+      e1[e] += (double)(uint32_t)w14;
+      if ((uint32_t)w13) {
+        e4[e] += (double)(uint32_t)w13;
+        e4n[e] += 1;
+      }
+      ew[e] += (double)(w13 >> 32);
+      if (e) {
+        em += (double)(w14 >> 32);
+        ed += (double)(uint32_t)w15;
+      }
+    }
+    if (!((h[(size_t)r * DW + 15] >> 32) & 1)) parts_n += 1;
     setup += (double)(w3 >> 24);
     a[3] -= (double)(w3 >> 22 << 22);
     if (h[(size_t)r * DW] == 0) continue;  // a row of the list past this launch's phase
@@ -470,9 +491,16 @@ static void print_sssp_diag(sg_ctx* ctx, const sg_net* net, const unsigned long 
             cn[c], cs[c] / std::max(1.0, cn[c]), cq[c] / std::max(1.0, cn[c]));
   fprintf(stderr, "[sssp] mean setup (init + bound rows) %.0f cyc of the search\n", setup / n_diag);
   // the set-up's parts, thread 0's stamps (words 8-12)
+  // (the load-round parts over the rows that have them: an early row's loads run under its search)
   fprintf(stderr, "[sssp] setup parts: bound-row listing and load issue %.0f, LDS pass %.0f, barrier %.0f, first load "
-          "round %.0f, later rounds and closing barrier %.0f cyc\n", a[9] / n_diag, a[8] / n_diag, a[10] / n_diag,
-          a[11] / n_diag, a[12] / n_diag);
+          "round %.0f, later rounds and closing barrier %.0f cyc (%.0f rows)\n", a[9] / n_diag, a[8] / n_diag,
+          a[10] / n_diag, a[11] / std::max(1.0, parts_n), a[12] / std::max(1.0, parts_n), parts_n);
+  for (int e = 0; e < 2; e++)
+    fprintf(stderr, "[sssp] chained rows %s: %.0f, from the search's start: first claim %.0f cyc, fourth claim %.0f cyc "
+            "(%.0f rows), %.2f waves with a claim in the first 16k cyc\n", e ? "started under their loads" : "set up first",
+            en[e], e1[e] / std::max(1.0, en[e]), e4[e] / std::max(1.0, e4n[e]), e4n[e], ew[e] / std::max(1.0, en[e]));
+  fprintf(stderr, "[sssp] rows started under their loads: last wave merged %.0f cyc after the search's start, %.2f merges "
+          "onto dirty keys per row\n", em / std::max(1.0, en[1]), ed / std::max(1.0, en[1]));
   fprintf(stderr, "[sssp] per-wave cycles summed over a row's 16 waves: claim+wait %.0f, pop %.0f, steps %.0f "
           "(per pop: %.0f, %.0f)\n", a[5] / n_diag, a[6] / n_diag, a[7] / n_diag, a[6] / std::max(1.0, a[2]),
           a[7] / std::max(1.0, a[2]));
@@ -506,7 +534,8 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
   // the relaxation counters, then the chained rows' two: rows seeded in place, those with exact seeds
   // ... then the ring invariant's two: ring slots a row's end found non-empty, rows looked at
   // ... then, with SG_SSSP_DIAG, the pops by class (SSSP_POP_WORDS)
-  constexpr int WORK_WORDS = WORK_SHARDS + 4 + SSSP_POP_WORDS;
+  // ... then the early rows' two: rows that started under their bound rows' loads, merges onto dirty keys
+  constexpr int WORK_WORDS = WORK_SSSP_EARLY + 2;
   unsigned long long* work = ctx->count_work ? ctx->r_work.get<unsigned long long>(WORK_WORDS) : nullptr;
   if (work) SG_HIP(hipMemsetAsync(work, 0, WORK_WORDS * 8, st));
   // counting mode with SG_SSSP_DIAG: the pops of the launch just issued, by class (the counters run on)
@@ -670,6 +699,9 @@ static void shortest_paths_lds(sg_ctx* ctx, sg_net* net, const uint32_t* d_used,
     timer_set_counter(ctx, "sssp_chained", (double)w[WORK_SHARDS], w[WORK_SHARDS + 1]);
     // read_timer("sssp_ring_left"): (0, rows whose ring was looked at, slots found non-empty: 0 by the invariant)
     timer_set_counter(ctx, "sssp_ring_left", (double)w[WORK_SHARDS + 2], w[WORK_SHARDS + 3]);
+    // read_timer("sssp_early"): (0, rows whose search started under their bound rows' loads, merges of
+    // theirs that landed on a dirty key) -- sg_sssp.hip "Late seeds"
+    timer_set_counter(ctx, "sssp_early", (double)w[WORK_SSSP_EARLY + 1], w[WORK_SSSP_EARLY]);
     if (k.diag)
       fprintf(stderr, "[sssp] ring slots not empty at a row's end: %llu (%llu rows)\n", w[WORK_SHARDS + 2],
               w[WORK_SHARDS + 3]);

@@ -112,6 +112,36 @@
 // relaxed every arc, and a candidate is dropped only when it saturates) -- the induction runs
 // over those nodes alone.  A node whose optimum from t reaches LAT32_SAT starts at FKEY_INF
 // or above its optimum and ends saturated, which flags the row like any other.
+//
+// Late seeds (SG_SSSP_EARLY; the plain launches, a chained row that has bound rows and is not its
+// workgroup's first).  Such a row has a complete start row in LDS once the chained rewrite is done; the
+// plan's bound rows only lower keys further, and their 240 KB are bound by what one CU keeps in flight,
+// not by anything the search uses.  So the order of its start is: the LDS pass (rewrite, ctl, hb) and
+// its barrier; thread 0 writes the source's key, ring[0], TAIL and s_psat, and a barrier; then wave 0
+// enters the claim loop while waves 1 .. 15 issue the bound rows' loads (11 columns per thread and
+// round, every pair of bound rows) and merge them into key[].  A wave enters the claim loop only after
+// its own merge is complete, and the search ends at a workgroup barrier every wave must reach (the
+// quiescence barrier; a wave that arrives from its merge finds the queue quiescent or joins the
+// search), so no row ends, and no bucket advances, with a bound row unmerged.  A wave that gives up
+// leaves as before: the merging waves see ctl[ABORT] at their first claim and meet no barrier on the way.
+//   The merge runs beside relaxations and pops, so it is a 64-bit LDS compare-and-swap loop that keeps
+// the dirty bit: new = min(old & ~1, seed) | (old & 1), attempted only when the seed is below the key
+// read, retried when the word changed.  A plain min with the clean seed over a dirty, queued key would
+// clear the flag without a pop; a later improvement would append the node a second time, and the
+// ring's capacity (at most n queued) would no longer hold.  With the flag kept, "dirty from an
+// improvement until popped, queued exactly once" stands as written; a merge never queues (a clean key
+// stays clean, a dirty one is queued already, or lies at or beyond `split` and is found by the next
+// bucket advance like any dirty key a relaxation lowered below it).
+//   Exactness.  Every key is still a real path's value or above one.  The induction of "Exact seeds"
+// along an optimal path s = v0, .., vk now reads: (a) a node whose key reaches its optimum while dirty
+// -- by a relaxation, or by a merge onto a dirty key -- is popped afterwards holding it and relaxes its
+// successor; (b) a node that reaches its optimum clean did so by an exact seed through some s' (the
+// chain's, in the start row, or a bound row's, merged late); its successor's seed through the same s'
+// is at most the successor's optimum, and is in the start row or merged before the closing barrier,
+// whichever of the two lands first; (c) bound-only seeds are strictly above the optimum, as before, so
+// they never stand in for either.  The source's key (0, 0.0, dirty) survives its own column's merge:
+// every seed for it is a path s -> s' -> s of latency at least w > 0, never below the key read.
+// tests/test_sssp_late_seeds_cpu.py runs this argument as a model, merges at random points.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -209,7 +239,7 @@ __global__ void __launch_bounds__(NT)
                uint32_t* __restrict__ item_ctr, uint32_t n_items, uint32_t spin_max,
                const uint32_t* __restrict__ plan_ctl, int plan_ph, uint32_t* __restrict__ done,
                const SsspChainDesc* chain_desc, uint32_t* __restrict__ any_flag, int ident, uint32_t step_arcs,
-               unsigned long long* __restrict__ popc) {
+               unsigned long long* __restrict__ popc, int early_on) {
   constexpr int NW = NT / 64;
   constexpr int AUX = FLAG ? SSSP_SC1 : 0;  // bound rows and the output: sc1 in the flagged launch
   // Chained rows: persistent workgroups, never the flagged launch.  The claim words and the maps
@@ -243,6 +273,7 @@ __global__ void __launch_bounds__(NT)
   const bool pop_diag = COUNT && popc;
   __shared__ uint32_t ctl[8];  // TAIL
   constexpr int TAIL = 1;
+  constexpr int E_DIRTY = 0, E_T0 = 3, E_POPS = 4, E_WAVES = 5, E_T4 = 6, E_T1 = 7;  // counting build: see the set-up
   // (head << 32) | busy in one word: a claim advances head and counts its wave
   // busy in one CAS, so a failed claim attempt never touches busy
   __shared__ unsigned long long hb;
@@ -346,6 +377,8 @@ __global__ void __launch_bounds__(NT)
     //      bound to its start key is monotone, so the min of the keys is the key of the min);
     //   5. columns past GC x NT and bound rows past the second (SG_SSSP_BOUNDS > 2, in pairs)
     //      take a load round each: the same loop, without the LDS pass.
+    // An early row (see "Late seeds" in the header) runs step 3 alone here; steps 2, 4 and 5 are its
+    // waves' way into the claim loop, under the search.
     // The ring and own[] are not reset: see the invariant ahead of the row loop.
     //
     // The usable bound rows of list place b, written to s_ub / s_nub by one whole wave: a row
@@ -354,8 +387,9 @@ __global__ void __launch_bounds__(NT)
     //   Phased launches: the flags are those of earlier launches, so they can be read at any
     // time.  A persistent workgroup's later rows are listed by the wave that claims them, ahead
     // of that wave's output stores (at the row's start the two dependent loads would wait behind
-    // every wave's stores of the row before); s_ub is read during a set-up only, and barriers
-    // separate that from the claim.  A workgroup's first row is listed here by every wave for
+    // every wave's stores of the row before); s_ub is read during a set-up, or by an early
+    // row's waves before they enter the claim loop, and the search's closing barrier separates that
+    // from the claim.  A workgroup's first row is listed here by every wave for
     // itself (the same values into the same words), which waits for no other wave.
     //   Flagged launch: wave 0 polls here, at set-up time (an earlier poll would miss rows
     // published meanwhile), and alone: every column must see the same set of rows (the induction
@@ -424,12 +458,66 @@ __global__ void __launch_bounds__(NT)
       __syncthreads();
       if (dg) c_bar = clock64();
     };
-    if (!nb) {  // no bounds: the LDS pass alone
+    // A bound-row pair's wave-uniform values, read into scalar registers (so the descriptors are scalar too)
+    struct BoundPair {
+      bool on[2], exact[2];
+      uint32_t sr[2];
+    };
+    const __amdgpu_buffer_rsrc_t ru_set = __builtin_amdgcn_make_buffer_rsrc((void*)used, 0, (int)(n_used * 4u),
+                                                                            0x00020000);
+    // issue the loads of bound rows k, k + 1 for columns j0 + g * stride, g < GC
+    auto bound_loads = [&](auto gc, int k, uint32_t j0, uint32_t stride, BoundPair& p, auto& l, auto& f, auto& vv) {
+      constexpr int GC = decltype(gc)::value;
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        p.on[u] = k + u < nb;
+        p.sr[u] = p.on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][0]) : 0u;
+        p.exact[u] = p.on[u] && __builtin_amdgcn_readfirstlane(s_ub[k + u][2]);
+        const size_t rb = p.on[u] ? (size_t)(p.sr[u] - out_row0) * n_used : 0;
+        const __amdgpu_buffer_rsrc_t rl =
+            __builtin_amdgcn_make_buffer_rsrc((void*)(out_lat + rb), 0, (int)(p.on[u] ? n_used * 8u : 0u), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(out_loss + rb), 0, (int)(p.exact[u] ? n_used * 4u : 0u), 0x00020000);
+#pragma unroll
+        for (int g = 0; g < GC; g++) {
+          const uint32_t j = j0 + g * stride;
+          const auto x = __builtin_amdgcn_raw_buffer_load_b64(rl, j < n_used ? j * 8u : OOB, 0, AUX);
+          l[u][g] = ((uint64_t)x[1] << 32) | x[0];
+          f[u][g] = __builtin_amdgcn_raw_buffer_load_b32(rf, j < n_used ? j * 4u : OOB, 0, AUX);
+        }
+      }
+      if (!ident) {
+#pragma unroll
+        for (int g = 0; g < GC; g++) {
+          const uint32_t j = j0 + g * stride;
+          vv[g] = __builtin_amdgcn_raw_buffer_load_b32(ru_set, j < n_used ? j * 4u : OOB, 0, 0);
+        }
+      }
+    };
+    // column j's start key from the pair's rows: the smaller of their seeds, ~0 without one (the map from
+    // a bound to its start key is monotone, so the min of the keys is the key of the min)
+    auto bound_seed = [&](const BoundPair& p, const uint32_t* w, uint32_t j, uint64_t l0, uint64_t l1, uint32_t f0,
+                          uint32_t f1) {
+      uint64_t sd = ~0ull;
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        const uint64_t ub = (u ? l1 : l0) + w[u];  // w < 2^32: a wrap means >= 2^64
+        if (!p.on[u] || ub < w[u]) continue;
+        if (ub < LAT32_SAT - 1) sd = min(sd, ((ub + 1) << 32) | ((uint64_t)0x3F800000u << 1));
+        if (p.exact[u] && ub < LAT32_SAT && j != p.sr[u])  // exact: the path s -> s' then D[s'][v]
+          sd = min(sd, (ub << 32) | ((uint64_t)(u ? f1 : f0) << 1));
+      }
+      return sd;
+    };
+    // Early rows (SG_SSSP_EARLY; see "Late seeds" in the header): a chained row with bound rows, not the
+    // workgroup's first, starts its search behind the LDS pass; waves 1 .. NW - 1 load and merge the bound
+    // rows, each on its way into the claim loop.
+    const bool early = !FLAG && early_on && chain && nb > 0 && it > 0;
+    if (!nb || early) {  // no bounds, or their loads issued under the search: the LDS pass alone
       lds_pass();
+      if (COUNT && early && tid == 0) atomicAdd(&work[WORK_SSSP_EARLY], 1ull);
     } else {
       constexpr int GC = 10;  // columns per thread in flight (x 2 bound rows x 12 B)
-      const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)used, 0, (int)(n_used * 4u),
-                                                                          0x00020000);
       // load rounds: bound rows k, k + 1 for columns jb + tid + g NT, g < GC; the first round
       // carries the LDS pass between its loads and their merge
       int k = 0;
@@ -444,56 +532,21 @@ __global__ void __launch_bounds__(NT)
         uint32_t vv[GC];
         uint64_t l[2][GC];
         uint32_t f[2][GC];
-        bool on[2], exact[2];
-        uint32_t sr[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-          // (wave-uniform values: read into scalar registers, so the descriptors are scalar too)
-          on[u] = k + u < nb;
-          sr[u] = on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][0]) : 0u;
-          exact[u] = on[u] && __builtin_amdgcn_readfirstlane(s_ub[k + u][2]);
-          const size_t rb = on[u] ? (size_t)(sr[u] - out_row0) * n_used : 0;
-          const __amdgpu_buffer_rsrc_t rl =
-              __builtin_amdgcn_make_buffer_rsrc((void*)(out_lat + rb), 0, (int)(on[u] ? n_used * 8u : 0u), 0x00020000);
-          const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
-              (void*)(out_loss + rb), 0, (int)(exact[u] ? n_used * 4u : 0u), 0x00020000);
-#pragma unroll
-          for (int g = 0; g < GC; g++) {
-            const uint32_t j = j0 + g * NT;
-            const auto x = __builtin_amdgcn_raw_buffer_load_b64(rl, j < n_used ? j * 8u : OOB, 0, AUX);
-            l[u][g] = ((uint64_t)x[1] << 32) | x[0];
-            f[u][g] = __builtin_amdgcn_raw_buffer_load_b32(rf, j < n_used ? j * 4u : OOB, 0, AUX);
-          }
-        }
-        if (!ident) {
-#pragma unroll
-          for (int g = 0; g < GC; g++) {
-            const uint32_t j = j0 + g * NT;
-            vv[g] = __builtin_amdgcn_raw_buffer_load_b32(ru, j < n_used ? j * 4u : OOB, 0, 0);
-          }
-        }
+        BoundPair p;
+        bound_loads(std::integral_constant<int, GC>(), k, j0, (uint32_t)NT, p, l, f, vv);
         if (k == 0 && jb == 0) lds_pass();
         // one thread per column, so a plain read and write (a chained row's keys already hold its
         // first bound row, an earlier pair's its bounds: the smaller start wins)
         uint32_t w[2];
 #pragma unroll
-        for (int u = 0; u < 2; u++) w[u] = on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][1]) : 0u;
+        for (int u = 0; u < 2; u++) w[u] = p.on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][1]) : 0u;
 #pragma unroll
         for (int g = 0; g < GC; g++) {
           const uint32_t j = j0 + g * NT;
           if (j >= n_used) continue;
           const uint32_t v = ident ? j : vv[g];
-          const uint64_t k0 = key[v];
-          uint64_t kv = k0;
-#pragma unroll
-          for (int u = 0; u < 2; u++) {
-            const uint64_t ub = l[u][g] + w[u];  // w < 2^32: a wrap means >= 2^64
-            if (!on[u] || ub < w[u]) continue;
-            if (ub < LAT32_SAT - 1) kv = min(kv, ((ub + 1) << 32) | ((uint64_t)0x3F800000u << 1));
-            if (exact[u] && ub < LAT32_SAT && j != sr[u])  // exact: the path s -> s' then D[s'][v]
-              kv = min(kv, (ub << 32) | ((uint64_t)f[u][g] << 1));
-          }
-          if (kv != k0) key[v] = kv;
+          const uint64_t sd = bound_seed(p, w, j, l[0][g], l[1][g], f[0][g], f[1][g]);
+          if (sd < key[v]) key[v] = sd;
         }
         if (dg && !c_g0) c_g0 = clock64();
         jb += GC * NT;
@@ -503,14 +556,20 @@ __global__ void __launch_bounds__(NT)
         }
       } while (k < nb);
     }
-    if (ub_row) __syncthreads();
+    if (ub_row && !early) __syncthreads();  // (an early row: the LDS pass's barrier)
     const unsigned long long c_setup = dg ? clock64() : 0;
     if (tid == 0) {
       key[src] = 1ull;  // PathProperties::default(), dirty and queued
       ring[0] = (uint16_t)src;
       ctl[TAIL] = 1;
       s_psat = 0u;  // (read by every thread before the set-up's barrier; set again in this row's output)
+      // SG_SSSP_DIAG stamps shared by the waves, in ctl's free words (reset by the LDS pass): E_T0 the
+      // search's start (clock, low word), E_POPS the row's wave-pops, E_WAVES the waves that held a
+      // claim in its first 16k cycles, E_T4 / E_T1 the cycles to the fourth / first claim;
+      // E_DIRTY (counting build) the merges that landed on a dirty key
+      if (COUNT && diag) ctl[E_T0] = (uint32_t)clock64();
     }
+    if (COUNT && diag && lane == 0) red[wv] = 0u;  // an early row: the cycles to the end of the wave's merge
     uint32_t split = delta;  // delta >= 1
     const __amdgpu_buffer_rsrc_t arcs = __builtin_amdgcn_make_buffer_rsrc((void*)out_arc, 0, (int)(n_arcs * 12u),
                                                                           0x00020000);
@@ -586,6 +645,53 @@ __global__ void __launch_bounds__(NT)
     };
     __syncthreads();
 
+    if (early && wv != 0) {
+      // An early row's bound rows, under the search wave 0 has begun: the columns spread over the
+      // other waves (GE per thread and round: one round up to 10,560 columns), every bound-row pair
+      // loaded and merged before the wave enters the claim loop.  The search runs, so the merge is
+      // a compare-and-swap that keeps the dirty bit (see "Late seeds").
+      constexpr int GE = 11;
+      constexpr uint32_t NM = NT - 64;
+      uint32_t ts = (uint32_t)tid - 64u;
+      asm volatile("" : "+v"(ts));  // (opaque, per row: see the set-up's load rounds)
+      int k = 0;
+      uint32_t jb = 0;
+#pragma unroll 1
+      do {
+        const uint32_t j0 = jb + ts;
+        uint32_t vv[GE];
+        uint64_t l[2][GE];
+        uint32_t f[2][GE];
+        BoundPair p;
+        bound_loads(std::integral_constant<int, GE>(), k, j0, NM, p, l, f, vv);
+        uint32_t w[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) w[u] = p.on[u] ? __builtin_amdgcn_readfirstlane(s_ub[k + u][1]) : 0u;
+#pragma unroll
+        for (int g = 0; g < GE; g++) {
+          const uint32_t j = j0 + g * NM;
+          if (j >= n_used) continue;
+          const uint32_t v = ident ? j : vv[g];
+          const uint64_t sd = bound_seed(p, w, j, l[0][g], l[1][g], f[0][g], f[1][g]);
+          unsigned long long old = __hip_atomic_load(&key[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          while (sd < (old & ~1ull)) {
+            const unsigned long long prev = atomicCAS(&key[v], old, sd | (old & 1ull));
+            if (prev == old) {
+              if (COUNT && (old & 1ull)) atomicAdd(&ctl[E_DIRTY], 1u);
+              break;
+            }
+            old = prev;
+          }
+        }
+        jb += GE * NM;
+        if (jb >= n_used) {
+          jb = 0;
+          k += 2;
+        }
+      } while (k < nb);
+      if (COUNT && diag && lane == 0) red[wv] = (uint32_t)clock64() - ctl[E_T0];
+    }
+
     for (;;) {
       // ---- claim up to `claim` queued entries
       const unsigned long long tc0 = (COUNT && diag) ? clock64() : 0;
@@ -657,6 +763,12 @@ __global__ void __launch_bounds__(NT)
       }
       if (COUNT) n_pops++;
       const unsigned long long tc1 = (COUNT && diag) ? clock64() : 0;
+      if (COUNT && diag && lane == 0) {  // how the search begins: see E_T0
+        const uint32_t dt = (uint32_t)tc1 - ctl[E_T0], np = atomicAdd(&ctl[E_POPS], 1u);
+        if (np == 0u) ctl[E_T1] = dt;
+        if (np == 3u) ctl[E_T4] = dt;
+        if (dt < 16384u) atomicOr(&ctl[E_WAVES], 1u << wv);
+      }
       // ---- pop the claimed entries (a slot claimed before its writer stored it reads EMPTY)
       const bool on = lane < (int)k;
       uint32_t u = 0, a0 = 0, a1 = 0;
@@ -811,6 +923,7 @@ __global__ void __launch_bounds__(NT)
       for (uint32_t i = tid; i < cap; i += NT) left += ring[i] != RING_EMPTY;
       if (left) atomicAdd(&work[WORK_SHARDS + 2], (unsigned long long)left);
       if (tid == 0) atomicAdd(&work[WORK_SHARDS + 3], 1ull);
+      if (tid == 0 && early && ctl[E_DIRTY]) atomicAdd(&work[WORK_SSSP_EARLY + 1], (unsigned long long)ctl[E_DIRTY]);
     }
 
     // ---- write the row: columns in used order, diagonal = the raw self-loop (graph/mod.rs:210-217)
@@ -1024,8 +1137,17 @@ __global__ void __launch_bounds__(NT)
       diag[bi * SSSP_DIAG_WORDS + 8] = c_init - c_list;
       diag[bi * SSSP_DIAG_WORDS + 9] = c_list - c_start;
       diag[bi * SSSP_DIAG_WORDS + 10] = c_bar - c_list;
-      diag[bi * SSSP_DIAG_WORDS + 11] = c_g0 - c_bar;
-      diag[bi * SSSP_DIAG_WORDS + 12] = c_setup - c_g0;
+      diag[bi * SSSP_DIAG_WORDS + 11] = early ? 0ull : c_g0 - c_bar;
+      diag[bi * SSSP_DIAG_WORDS + 12] = early ? 0ull : c_setup - c_g0;
+      // how the search began, from its start behind the set-up (E_T0): cycles to the fourth claim | waves
+      // that held a claim in the first 16k cycles; cycles to the first claim | an early row's cycles to the
+      // end of its last wave's merge (overwritten by a bucket advance: one bucket only); an early row's
+      // merges onto dirty keys | early
+      uint32_t last_merge = 0;
+      for (int w = 1; w < NW; w++) last_merge = max(last_merge, red[w]);
+      diag[bi * SSSP_DIAG_WORDS + 13] = ctl[E_T4] | ((unsigned long long)__popc(ctl[E_WAVES]) << 32);
+      diag[bi * SSSP_DIAG_WORDS + 14] = ctl[E_T1] | ((unsigned long long)(early ? last_merge : 0u) << 32);
+      diag[bi * SSSP_DIAG_WORDS + 15] = ctl[E_DIRTY] | ((unsigned long long)early << 32);
     }
     if constexpr (FLAG) {
       // Flagged rows: every wave waits for its sc1 stores, then one lane publishes the row
@@ -1068,6 +1190,9 @@ struct SsspKnobs {
   // SG_SSSP_STEP_ARCS: a pop of at most this many arcs takes the arc-parallel step sized to them
   // (0: the lane path unless an entry's degree is past lane_deg)
   uint32_t step_arcs;
+  // SG_SSSP_EARLY: a chained row with bound rows starts its search behind the LDS pass, the bound rows
+  // loaded and merged under it ("Late seeds"); 0: every row's set-up ends before its search begins
+  bool early;
 };
 static SsspKnobs sssp_knobs() {
   SsspKnobs k;
@@ -1077,6 +1202,7 @@ static SsspKnobs sssp_knobs() {
   k.persist = !knob_off("SG_SSSP_PERSIST");
   k.spin_max = sssp_spin_max();
   k.step_arcs = (uint32_t)std::max(0, knob_int("SG_SSSP_STEP_ARCS", 256));
+  k.early = knob_int("SG_SSSP_EARLY", 1) != 0;
   return k;
 }
 
@@ -1114,7 +1240,7 @@ void launch_sssp_lds(sg_ctx* ctx, const sg_net* net, const SsspLdsLaunch& l) {
                        l.d_used, l.n_used, l.row_begin, l.row_begin, net->self_edge, net->e_lat, net->e_loss,
                        l.out_lat, l.out_loss, l.sat_row, l.delta, vec, l.work, l.diag, k.claim, k.idle_sleep,
                        k.lane_deg, l.blk_rows, l.ub_row, l.ub_w, item_ctr, rows, k.spin_max, l.plan_ctl, l.plan_ph,
-                       l.done, chain, ctx->apsp_ret + 4, (int)l.ident, k.step_arcs, pops);
+                       l.done, chain, ctx->apsp_ret + 4, (int)l.ident, k.step_arcs, pops, (int)k.early);
   };
   // <counting, threads, lane arcs, fill symbol, flagged>
   if (l.done) {  // the flagged one-launch plan

@@ -7,8 +7,9 @@ C ABI in include/shadow_gpu.h (libshadow_gpu.so):
   src/main/network/graph/mod.rs:183-252) -> `graph.NetworkGraph`, with the paths' trees
   (`graph.PathTree`) and the traffic they carried per link (`PathTree.link_load` from per-pair
   counters, `PathTree.link_load_round` from a round's packets, `NetworkGraph.links`), and what
-  a link rate would make each crossing wait (`link_queue`, `PathTree.link_queue_round`), also per
-  link and time bin (`LinkQueueSeries`);
+  a link rate would make each crossing wait (`link_queue`, `PathTree.link_queue_round`; the module
+  link_queue.py, which the function of that name hides as an attribute here), also per link and
+  time bin (`LinkQueueSeries`);
 * per-round packet delivery (Worker::send_packet, src/main/core/worker.rs:322-397)
   -> `worker.deliver_round`;
 * the packets in flight between a delivery round and their arrival (the per-host

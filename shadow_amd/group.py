@@ -28,6 +28,7 @@ from ._capi import ShadowGpuError, load
 from .dist import (HostPartition, SourceResult, Workspace, _stream_wait, gpu_bucket_phase, gpu_bucket_phase_padded,
                    gpu_pad_to_compact, gpu_source_phase, gpu_source_phase_padded, next_cap)
 from .graph import Context, NetworkGraph, RoutingInfo
+from .round_args import concat_weights, int_tensor, member_weights, series_out, watch_mask, with_capacity
 
 GROUP_MAX = 64  # members of one group (sg_group_create)
 
@@ -176,15 +177,8 @@ class Group:
             if len(status) != n:
                 raise ValueError(f"status: {len(status)} entries for {n} members")
             for m, s in enumerate(status):
-                if s is None:
-                    continue
-                s = getattr(s, "status", s)
-                if not isinstance(s, torch.Tensor):
-                    s = torch.from_numpy(np.ascontiguousarray(s, dtype=np.uint8))
-                s = s.to(device=devs[m]).contiguous()
-                if s.element_size() != 1 or s.numel() < len(packets[m]):
-                    raise ValueError(f"status[{m}]: {len(packets[m])} u8 entries, one per packet")
-                st[m] = s
+                if s is not None:
+                    st[m] = int_tensor(s, np.uint8, len(packets[m]), devs[m], f"status[{m}]", "status")
         pk = (_capi.sg_packets * n)(*[p.c_struct() for p in packets])
         u32s = lambda v: (C.c_uint32 * n)(*v)  # noqa: E731
         args = dict(nets=(C.c_void_p * n)(*[g._ensure_net().value for g in graphs]),
@@ -206,21 +200,9 @@ class Group:
         per member."""
         import torch
 
-        n = len(self.contexts)
         a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, False)
-        wt = None
-        if weight is not None:
-            if isinstance(weight, str):
-                if weight != "payload":
-                    raise ValueError('weight: None, "payload" or one array per member')
-                weight = [p.payload_len for p in packets]
-            wt = []
-            for m, w in enumerate(weight):
-                if w is not None and not isinstance(w, torch.Tensor):
-                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
-                wt.append(None if w is None else w.to(device=devs[m]).contiguous())
-                if wt[m] is not None and (wt[m].element_size() != 4 or wt[m].numel() < len(packets[m])):
-                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
+        wt = member_weights(weight, packets, devs)
+        if wt is not None:
             for d in devs:
                 torch.cuda.synchronize(d)
         n_links = len(graphs[root].links()[0])
@@ -261,39 +243,28 @@ class Group:
 
         a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, True)
         n_links = len(graphs[root].links()[0])
-        if watch is not None:
-            w = np.asarray(watch)
-            if w.dtype == np.bool_ or (w.dtype == np.uint8 and w.shape == (n_links,)):
-                if w.shape != (n_links,):
-                    raise ValueError(f"watch: a mask of {n_links} entries, one per link")
-                mask = w.astype(np.uint8)
-            else:
-                idx = w.astype(np.int64).ravel()
-                if len(idx) and (idx.min() < 0 or idx.max() >= n_links):
-                    raise ValueError(f"watch: link numbers below {n_links}")
-                mask = np.zeros(n_links, np.uint8)
-                mask[idx] = 1
-            watch = np.ascontiguousarray(mask)
+        watch = watch_mask(watch, n_links)
         d = devs[root]
         off = torch.zeros(n_links + 1, dtype=torch.int64, device=d)
         total = C.c_uint64()
-        cap = 8 * sum(len(p) for p in packets) + 64
-        while True:
-            pkt, hop = torch.zeros(cap, dtype=torch.int32, device=d), torch.zeros(cap, dtype=torch.int32, device=d)
-            mem = torch.zeros(cap, dtype=torch.uint8, device=d)
-            enter, leave = torch.zeros(cap, dtype=torch.int64, device=d), torch.zeros(cap, dtype=torch.int64, device=d)
+
+        def alloc(cap):  # (pkt, hop, mem, enter, leave)
+            return [torch.zeros(cap, dtype=dt, device=d) for dt in (torch.int32, torch.int32, torch.uint8, torch.int64, torch.int64)]
+
+        def call(arrays, cap):
+            pkt, hop, mem, enter, leave = arrays
             torch.cuda.synchronize(d)
             rc = load().sg_group_link_trace_packets(
                 self.handle, a["nets"], a["hosts"], a["nodes"].ctypes.data, len(a["nodes"]), a["row_begin"], a["row_end"],
                 a["pred"], a["lat"], a["packets"], a["status"], None if watch is None else watch.ctypes.data, None,
                 int(root), off.data_ptr(), pkt.data_ptr(), mem.data_ptr(), hop.data_ptr(), enter.data_ptr(),
                 leave.data_ptr(), cap, C.byref(total))
-            if rc != _capi.SG_ERR_CAPACITY or total.value <= cap:
-                break
-            cap = total.value
+            return rc, total.value
+
+        rc, t, (pkt, hop, mem, enter, leave) = with_capacity(sum(len(p) for p in packets), alloc, call)
         self._check(rc)
         del keep
-        return off, pkt, mem, hop, enter, leave, total.value
+        return off, pkt, mem, hop, enter, leave, t
 
     def link_queue_round(self, graphs, hosts, rows, packets, status=None, weight=None, *, cost_ps, watch=None,
                          free_ns=None, root: int = 0, carry=False, limit_ns=None, outcomes=None, series=None):
@@ -318,29 +289,13 @@ class Group:
         time, weight served and weight dropped per slot and time bin are added into its matrix there."""
         import torch
 
-        from .graph import _base_times, _exit_carried, _link_queue_tensors
+        from .link_queue import _base_times, _exit_carried, _link_queue_tensors
 
         tr = self._link_trace_tensors(graphs, hosts, rows, packets, status, watch, root)
         off, pkt, _, _, enter, _, t = tr
         dev = off.device
-        wt = None
-        if weight is not None:
-            if isinstance(weight, str):
-                if weight != "payload":
-                    raise ValueError('weight: None, "payload" or one array per member')
-                weight = [p.payload_len for p in packets]
-            if len(weight) != len(packets):
-                raise ValueError(f"weight: {len(weight)} entries for {len(packets)} members")
-            parts = []
-            for m, w in enumerate(weight):
-                if w is None:
-                    w = torch.ones(len(packets[m]), dtype=torch.int32)
-                elif not isinstance(w, torch.Tensor):
-                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
-                if w.element_size() != 4 or w.numel() < len(packets[m]):
-                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
-                parts.append(w.reshape(-1)[:len(packets[m])].view(torch.int32).to(dev))
-            wt = torch.cat(parts).contiguous() if parts else None
+        # (every member's weights straight onto root's device, where the queue runs)
+        wt = concat_weights(member_weights(weight, packets, [dev] * len(packets)), packets, dev)
         npk = sum(len(p) for p in packets)
         base, tails = None, ()
         if outcomes is not None:
@@ -367,32 +322,18 @@ class Group:
         batch."""
         import torch
 
-        from .graph import series_slots
+        from .link_queue import series_slots
 
         if at not in ("enter", "exit"):
             raise ValueError('at: "enter" or "exit"')
         a, devs, keep = self._round_inputs(graphs, hosts, rows, packets, status, True)
-        wt = None
-        if weight is not None:
-            if isinstance(weight, str):
-                if weight != "payload":
-                    raise ValueError('weight: None, "payload" or one array per member')
-                weight = [p.payload_len for p in packets]
-            wt = []
-            for m, w in enumerate(weight):
-                if w is not None and not isinstance(w, torch.Tensor):
-                    w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32))
-                wt.append(None if w is None else w.to(device=devs[m]).contiguous())
-                if wt[m] is not None and (wt[m].element_size() != 4 or wt[m].numel() < len(packets[m])):
-                    raise ValueError(f"weight[{m}]: {len(packets[m])} u32 entries, one per packet")
+        wt = member_weights(weight, packets, devs)
         n_links = len(graphs[root].links()[0])
         slot_map, n_slots = series_slots(slots, n_links)
         n_bins = int(n_bins)
         if out is not None:
-            series, outside = out
-            if (series.dtype != np.uint64 or outside.dtype != np.uint64 or series.shape != (n_slots, n_bins)
-                    or outside.shape != (n_slots, 2)):
-                raise ValueError(f"out: a previous result of this shape, u64 ({n_slots}, {n_bins}) and ({n_slots}, 2)")
+            # (a view that is not contiguous passes here: it is copied in below and written back at the end)
+            series, outside = series_out(out, n_slots, n_bins, contiguous=False)
             d_series = torch.from_numpy(np.ascontiguousarray(series).view(np.int64)).to(devs[root])
             d_out = torch.from_numpy(np.ascontiguousarray(outside).view(np.int64)).to(devs[root])
         else:

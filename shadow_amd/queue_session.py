@@ -9,6 +9,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import check, load
+from .link_queue import _base_times, _per_link_u64
+from .round_args import int_tensor
 
 _UMAX = 0xFFFFFFFFFFFFFFFF
 _IN_FLIGHT = 0xFFFFFFFD
@@ -66,8 +68,6 @@ class LinkQueueSession:
     def __init__(self, graph_or_ctx, cost_ps, limit_ns=None, free_ns=None, *, n_links=None, device="cuda", series=None):
         import torch
 
-        from .graph import _per_link_u64
-
         self.ctx = getattr(graph_or_ctx, "ctx", graph_or_ctx)
         self.n_links = int(len(graph_or_ctx.links()[0]) if hasattr(graph_or_ctx, "links") else n_links)
         nl, self.dev = self.n_links, torch.device(device)
@@ -120,17 +120,7 @@ class LinkQueueSession:
             if count:
                 raise ValueError(f"{what}: {count} entries")
             return torch.zeros(0, dtype=t_dtype, device=self.dev)
-        if isinstance(x, torch.Tensor):
-            x = x.to(self.dev).reshape(-1)
-            if x.is_floating_point() or x.element_size() != np.dtype(np_dtype).itemsize:
-                raise ValueError(f"{what}: a {np.dtype(np_dtype).name} array")
-            x = x.view(t_dtype)
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).ravel().view(
-                np.int64 if t_dtype == torch.int64 else np.int32)).to(self.dev)
-        if x.numel() < count:
-            raise ValueError(f"{what}: {count} entries")
-        return x[:count]
+        return int_tensor(x, np_dtype, count, self.dev, what)[:count]
 
     def advance(self, link_off, enter, packet, weight, base, horizon_ns):
         """One round: its trace (link_off: n_links + 1 u64 offsets; enter u64 and packet u32 per
@@ -266,8 +256,6 @@ class LinkQueueSession:
         device), then advance(); the records' indices are the trace's.  deliveries: the round's Deliveries (status and the base times),
         weight and watch as in PathTree.link_queue_round."""
         off, n, enter, pkt, weight = tree.link_trace_device(hosts, packets, deliveries, weight, watch)[:5]
-        from .graph import _base_times
-
         base = _base_times(deliveries, len(packets), self.dev)
         if weight is None:
             import torch

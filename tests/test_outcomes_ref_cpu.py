@@ -153,7 +153,7 @@ def test_case_sizes():
 def test_real_traces_against_the_host_fold(oracle, name):
     """A fully watched trace: the carried outcome of every packet that arrived is the carried exit
     of its last record, as the host-side fold over the record arrays gives it."""
-    from shadow_amd.graph import LinkQueueCarriedDropped, _exit_carried
+    from shadow_amd.link_queue import LinkQueueCarriedDropped, _exit_carried
 
     r = OC.real_trace(oracle, name)
     c, res, tr = r["case"], r["res"], r["tr"]

@@ -69,7 +69,7 @@ def windowed(ctx, q, window_ns, max_calls, check=None):
     """One windowed solve of the leg's trace: (ms, calls, iterations, active, pending left)."""
     import torch
 
-    from shadow_amd.graph import _step_windows
+    from shadow_amd.link_queue import _step_windows
     from shadow_amd.queue_session import LinkQueueSession
 
     n, P = q.total, q.b.P
